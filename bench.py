@@ -6,19 +6,29 @@ A "step" = one frame of the hot path over resident inputs: frr_clear + frr_draw 
 binning -> tile raster/resolve) [+ the RCCL image gather when N > 1].  Inputs (the triangle
 list, textures) are in HBM before the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W [--workload headline|cfg2|cfg3|cfg4|cfg5] [--also cfg4,cfg5]
+  python bench.py --gpus N --steps K --warmup W [--workload headline|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+                  [--full [--also cfg4,cfg5] [--cpu-baseline-seconds S]]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline figure needs: set-up, one counted frame (the Mfrag/s numerator), W warm-up
+frames, K timed frames, and the JSON line.  `--dump-outputs DIR` then writes the image the last timed frame left behind
+(what frr_readback returns: color, depth, tri_id) as DIR/<name>.npy in float32/float64, a fixed seeded pixel sample of it
+when the whole image would exceed 64 MB; the inputs are generated from fixed seeds, so two builds compare output for output.
+
+`--full` adds everything else the benchmark measures and checks: the serial frame period and the roofline of the
+dominant kernel (profiled loops of their own), the CPU oracle baseline and parity counts, the timed frame's image
+against the committed golden digests, the multi-GPU image check, and the further workloads of `--also`.
 
 Multi-GPU: one process per GPU; the framebuffer is partitioned into N contiguous blocks of 32-px tile
 rows (frr_set_partition_layout: blocked), geometry is replicated, and the only collective is the RCCL
 gather of the owned slabs (depth for depth-only workloads, colour + depth for shaded ones) to rank 0 per
-frame, read straight from the render targets and overlapped with the next frames.  Before the timed region
-rank 0 renders the same frame unpartitioned; the gathered image of the LAST timed frame must equal it byte
-for byte (depth bits, RGBA8, and -- in one extra check frame -- triangle ids).  Total work is fixed =>
-"scaling": "strong".
+frame, read straight from the render targets and overlapped with the next frames.  With `--full`, rank 0
+renders the same frame unpartitioned before the timed region; the gathered image of the LAST timed frame must
+equal it byte for byte (depth bits, RGBA8, and -- in one extra check frame -- triangle ids).  Total work is
+fixed => "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  `--also` (default: the 4096^2
-and the 4K textured configs north_star's scaling target is quoted on) runs further workloads after the primary
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  With `--full`, `--also` (default: the
+4096^2 and the 4K textured configs north_star's scaling target is quoted on) runs further workloads after the primary
 one, fewer steps each, and reports them under "secondary" with the same fields.
 """
 import argparse
@@ -48,6 +58,7 @@ ISO_LAUNCHES = 16           # launches of the dominant kernel timed one frame at
 SIMDS, CLOCK_GHZ = 1024, 2.4   # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, 2400 MHz max clock (the VALU-issue bound is priced at the max clock)
 DEFAULT_FIF = int(os.environ.get("FRR_FRAMES_IN_FLIGHT", "2"))   # what f_renderer_amd.Renderer sets from the environment (dev runs)
 DEFAULT_OVERLAP = int(os.environ.get("FRR_OVERLAP", "2"))
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: at most this much in all (larger images are sampled)
 
 
 def parse_args():
@@ -56,8 +67,14 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="random_1M_tris_1920x1080_depth", choices=sorted(WORKLOADS) + sorted(ALIASES))
-    ap.add_argument("--also", default="cfg4,cfg5",
-                    help="comma-separated further workloads reported under 'secondary' (fewer steps each); 'none' disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed frame as DIR/<name>.npy (float32/float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: serial period, roofline, CPU baseline, "
+                         "golden digests, multi-GPU image check, the --also workloads")
+    ap.add_argument("--also", default=None,
+                    help="--full only: comma-separated further workloads reported under 'secondary' (fewer steps each; "
+                         "default cfg4,cfg5); 'none' disables")
     ap.add_argument("--in-flight", action="store_true",
                     help="N = 1 only: also time two contexts on two streams rendering alternate frames (extra key "
                          "two_frames_in_flight; off by default so that a kernel trace of the default command holds "
@@ -68,8 +85,13 @@ def parse_args():
                     help="N > 1: wait for each frame's gather before rendering the next one (default: the gathers of "
                          "frames i-1, i-2 overlap the rendering of frame i into other target sets)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0,
-                    help="approximate CPU time budget of the oracle baseline leg (rank 0, N=1 only); 0 disables")
-    return ap.parse_args()
+                    help="--full: approximate CPU time budget of the oracle baseline leg (rank 0, N=1 only); 0 disables")
+    args = ap.parse_args()
+    if args.also is not None and not args.full:
+        ap.error("--also needs --full")
+    if args.also is None:
+        args.also = "cfg4,cfg5"
+    return args
 
 
 def source_sha():
@@ -152,6 +174,25 @@ def cpu_baseline(cfg, budget_s):
             "note": "row bands over host threads via the sub-window argument (renderer.rs:270-271); every band repeats "
                     "the geometry of all triangles, which is what the reference's per-triangle API offers; not the baseline"}
     return base, counters, best
+
+
+def dump_outputs(out_dir, image, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: {name: array [H, W, ...]} -> out_dir/<name>.npy, as float32 where that is exact (floats, 8- and
+    16-bit integers), else float64 (32-bit ids).  Whole arrays when they fit `budget`; otherwise the same fixed, seeded
+    sample of pixels from every array, and the sampled pixel numbers as pixel_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    exact32 = lambda a: a.dtype.kind == "f" or a.dtype.itemsize <= 2  # noqa: E731
+    conv = {k: a.astype(np.float32 if exact32(a) else np.float64) for k, a in image.items()}
+    budget -= 1024 * (len(conv) + 1)   # (.npy headers)
+    if sum(a.nbytes for a in conv.values()) > budget:
+        first = next(iter(conv.values()))
+        npx = first.shape[0] * first.shape[1]
+        per_px = sum(a.nbytes for a in conv.values()) / npx + 8
+        idx = np.sort(np.random.default_rng(0).choice(npx, size=int(budget // per_px), replace=False))
+        conv = {k: a.reshape((npx,) + a.shape[2:])[idx] for k, a in conv.items()}
+        conv["pixel_index"] = idx.astype(np.float64)
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def two_frames_in_flight(torch, run, steps):
@@ -330,10 +371,24 @@ class Run:
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    def run(self, steps, warmup, primary):
+    def last_image(self):
+        """Rank 0: what the last timed frame left behind, as a caller receives it -> {name: numpy array}.  N = 1: the
+        context's targets (frr_readback); N > 1: the gathered planes (RGBA8 of shaded workloads, depth)."""
+        if self.gathers is None:
+            c_, d_, t_ = self.r.readback()
+            return {"color": c_, "depth": d_.reshape(self.H, self.W), "tri_id": t_.reshape(self.H, self.W)}
+        H, out = self.H, {}
+        planes = list(self.final)
+        if self.shaded:
+            out["color"] = planes.pop(0)[:H].contiguous().cpu().numpy().view(np.uint8).reshape(H, self.W, 4)
+        out["depth"] = planes.pop(0)[:H].contiguous().cpu().numpy()
+        return out
+
+    def run(self, steps, warmup, primary, full=False, keep_image=False):
         torch, dist, r = self.torch, self.dist, self.r
+        self.image = None
         with torch.cuda.stream(self.stream):
-            ref = self.reference_image() if (self.gathers is not None and self.rank == 0) else None
+            ref = self.reference_image() if (full and self.gathers is not None and self.rank == 0) else None
             # one counted frame: the exact covered-fragment count of this rank's tiles (the Mfrag/s
             # numerator).  The statistic is then switched off: maintaining it forbids the tile kernel's
             # whole-triangle early-z (outputs are identical either way, tests/test_gpu_earlyz.py).
@@ -354,7 +409,7 @@ class Run:
             # primary roofline figure.  (In the timed region below the library keeps two frames in flight: there the
             # kernel shares the chip with the next frame's geometry + binning, and consecutive tile kernels may overlap.)
             self._raster_iso, self._serial_ms = (0.0, 0), None
-            if self.gathers is None:
+            if full and self.gathers is None:
                 r.set_option("frames_in_flight", 1)
                 r.set_option("overlap", 0)
                 for _ in range(3):
@@ -375,18 +430,16 @@ class Run:
                     self.step()
                 r.sync()
 
-            r.profile_reset()
-            r.profile_enable(True, kernels=["k_raster"], period=PROF_PERIOD)
             elapsed = self.timed_loop(steps)
-            raster_ms, raster_n = r.profile_get("k_raster")
-            r.profile_enable(False)
             stats = r.stats()
+            if keep_image and self.rank == 0:
+                self.image = self.last_image()
 
             # N = 1: the image the LAST timed frame left in the targets against the committed digests of the oracle's
             # frame (tests/golden/frames.json: data only, nothing of oracle/ runs here)
             self._golden_match = None
             gold = golden_counts(self.cfg_name)
-            if self.world == 1 and gold:
+            if full and self.world == 1 and gold:
                 sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
                 if self.gathers is None:
                     c_, d_, t_ = r.readback()
@@ -396,11 +449,21 @@ class Run:
                     c_, d_, t_ = (x[s_last][:H].contiguous().cpu().numpy() for x in (self.color, self.depth, self.tri_id))
                 self._golden_match = bool(sha(d_) == gold["sha256_depth"] and sha(t_) == gold["sha256_tri_id"] and sha(c_) == gold["sha256_rgba8"])
 
+            # the dominant kernel in the conditions of the timed region (two frames in flight), in a loop of its own:
+            # its launches are bracketed by HIP events every PROF_PERIOD-th time, which the timed frames must not pay
+            raster_ms, raster_n = 0.0, 0
+            if full:
+                r.profile_reset()
+                r.profile_enable(True, kernels=["k_raster"], period=PROF_PERIOD)
+                self.timed_loop(steps)
+                raster_ms, raster_n = r.profile_get("k_raster")
+                r.profile_enable(False)
+
             # multi-GPU image check on rank 0: the gathered image of the LAST timed frame == the unpartitioned render,
             # byte for byte; triangle ids through one extra (untimed) frame's gather
             image_equal = None
             render_us = gather_us = None
-            if self.gathers is not None:
+            if full and self.gathers is not None:
                 s = self.step(gather=False)
                 self.r.frame_fence(self.stream.cuda_stream)
                 ids_final = self.gather_ids([self.tri_id[s]])
@@ -549,11 +612,12 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
 
     primary = ALIASES.get(args.workload, args.workload)
-    also = [] if args.also.strip().lower() in ("", "none") else [ALIASES.get(a.strip(), a.strip()) for a in args.also.split(",")]
+    also = [] if not args.full or args.also.strip().lower() in ("", "none") else [ALIASES.get(a.strip(), a.strip()) for a in args.also.split(",")]
     also = [a for a in also if a in WORKLOADS and a != primary]
 
     run = Run(args, torch, dist, rank, world, local_rank, primary)
-    line = run.run(args.steps, args.warmup, True)
+    line = run.run(args.steps, args.warmup, True, full=args.full, keep_image=args.dump_outputs is not None)
+    image = run.image
     if rank == 0:
         H = run.H
         head = {"metric": "Mtri/s (and Mfrag/s), 1M-triangle frame @1920x1080" if run.cfg_name == "headline" else "Mtri/s (and Mfrag/s) per frame",
@@ -564,7 +628,7 @@ def main():
         line = head
         gold = golden_counts(run.cfg_name)
         f_pass, n_setup = (gold["frag_zpass"], gold["tris_setup"]) if gold else (None, None)
-        if world == 1 and args.cpu_baseline_seconds > 0:
+        if args.full and world == 1 and args.cpu_baseline_seconds > 0:
             cpu, oc, best = cpu_baseline(run.cfg, args.cpu_baseline_seconds)
             line["cpu_baseline"] = cpu
             line["cpu_best_effort"] = best
@@ -572,7 +636,8 @@ def main():
                                                and (gold is None or (gold["frag_zpass"] == oc["frag_zpass"] and gold["frag_covered"] == oc["frag_covered"])))
             line["speedup_vs_cpu_1core"] = round(line["value"] / cpu["value"], 1)
             f_pass, n_setup = oc["frag_zpass"], oc["tris_setup"]
-        run.roofline(line, f_pass, n_setup)
+        if args.full:
+            run.roofline(line, f_pass, n_setup)
     if rank == 0 and world == 1 and dist is None and args.in_flight:
         extra = two_frames_in_flight(torch, run, args.steps)
         if extra:
@@ -584,7 +649,7 @@ def main():
     for name in also:
         steps2 = max(4, min(args.steps, 50))
         r2 = Run(args, torch, dist, rank, world, local_rank, name)
-        o = r2.run(steps2, min(args.warmup, 3), False)
+        o = r2.run(steps2, min(args.warmup, 3), False, full=True)
         if rank == 0:
             gold = golden_counts(r2.cfg_name)
             if gold:
@@ -599,6 +664,8 @@ def main():
         os.dup2(saved_stdout_fd, 1)
         os.close(saved_stdout_fd)
     if rank == 0:
+        if image is not None:
+            dump_outputs(args.dump_outputs, image)
         if secondary:
             line["secondary"] = secondary
         print(json.dumps(line), flush=True)

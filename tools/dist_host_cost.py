@@ -7,7 +7,7 @@ os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER
 os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1"); os.environ.setdefault("LOCAL_RANK", "0")
 import torch, torch.distributed as dist
 import bench
-sys.argv = ["bench.py", "--force-dist", "--also", "none", "--cpu-baseline-seconds", "0", "--workload", sys.argv[1] if len(sys.argv) > 1 else "cfg2"]
+sys.argv = ["bench.py", "--force-dist", "--workload", sys.argv[1] if len(sys.argv) > 1 else "cfg2"]
 args = bench.parse_args()
 torch.cuda.set_device(0)
 dist.init_process_group("nccl", rank=0, world_size=1)

@@ -6,14 +6,14 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/final4; [ -z "$PART2" ] && rm -rf $O; mkdir -p $O
 if [ -z "$PART2" ]; then
-python bench.py > $O/bench.json 2> $O/bench.err || exit 1
-FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0 python bench.py --cpu-baseline-seconds 0 > $O/bench_serial.json 2>> $O/bench.err || exit 1   # one frame at a time, one stream (round 2's mode)
+python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0 python bench.py --full --cpu-baseline-seconds 0 > $O/bench_serial.json 2>> $O/bench.err || exit 1   # one frame at a time, one stream (round 2's mode)
 # kernel trace + stats of the default command (two frames in flight); the counter passes, workgroup shapes and tile timelines
 # look at kernels one frame at a time on one stream (FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0): comparable with round 2
 for w in headline cfg4 cfg5; do
-  rocprofv3 --kernel-trace --stats -d $O/kt_$w --output-format csv -- python3 bench.py --workload $w --also none --steps 20 --warmup 3 --cpu-baseline-seconds 0 > $O/kt_$w.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats -d $O/kt_$w --output-format csv -- python3 bench.py --full --workload $w --also none --steps 20 --warmup 3 --cpu-baseline-seconds 0 > $O/kt_$w.log 2>&1 || exit 1
   export FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0
-  FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0 rocprofv3 --kernel-trace --stats -d $O/kts_$w --output-format csv -- python3 bench.py --workload $w --also none --steps 20 --warmup 3 --cpu-baseline-seconds 0 > $O/kts_$w.log 2>&1 || exit 1
+  FRR_FRAMES_IN_FLIGHT=1 FRR_OVERLAP=0 rocprofv3 --kernel-trace --stats -d $O/kts_$w --output-format csv -- python3 bench.py --full --workload $w --also none --steps 20 --warmup 3 --cpu-baseline-seconds 0 > $O/kts_$w.log 2>&1 || exit 1
   FRAMES=4 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch_$w --output-format csv -- python3 tools/pmc_frame.py $w > $O/f_$w.log 2>&1 || exit 1
   FRAMES=4 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write_$w --output-format csv -- python3 tools/pmc_frame.py $w > $O/w_$w.log 2>&1 || exit 1
   FRAMES=4 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_WAIT_ANY -d $O/sq1_$w --output-format csv -- python3 tools/pmc_frame.py $w > $O/s1_$w.log 2>&1 || exit 1
