@@ -153,6 +153,8 @@ struct FrameState {
     int geom_vs = -1;              // VS of the latest frr_geometry
     uint64_t geom_ntris = 0;
     const float *geom_mesh = nullptr; uint64_t geom_mesh_gen = 0, geom_duni_hash = 0;   // ... its mesh and (a digest of) its uniforms: DrawSig
+    uint64_t geom_tex_epoch = 0, geom_sync_epoch = 0;  // ... the texture uploads and (device-bound mesh) the frr_sync calls before it: DrawSig
+    uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
 };
 
 struct Cmd {
@@ -170,14 +172,16 @@ struct Cmd {
 };
 
 // What decides how much of the work lists (fan space, (triangle, tile) records) a raster pass and its geometry pass need.
+// Everything the geometry pass reads can change what it emits: the mesh (its registration, and for a device-bound one the
+// frr_sync calls since -- the caller may rewrite it in place then), the uniforms (a user VS may read any field, texture
+// pointers and sizes included) and the texture contents (frr_texture_upload count).
 struct DrawSig {
-    const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint32_t join_epoch;
+    const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
     int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset;
 };
 inline bool same_sig(const DrawSig &a, const DrawSig &b) { return memcmp(&a, &b, sizeof a) == 0; }
-inline uint64_t fnv1a(const void *p, size_t n)
+inline uint64_t fnv1a(const void *p, size_t n, uint64_t h = 1469598103934665603ull)
 {
-    uint64_t h = 1469598103934665603ull;
     for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
     return h;
 }
@@ -232,6 +236,8 @@ struct frr_ctx {
     // host_bad, and repairs (finish(): grow + replay) if the pass or its geometry overflowed.  A proven pass is not waited for.
     std::vector<DrawSig> proven;
     uint64_t mesh_gen = 0;          // meshes registered so far (Mesh::gen)
+    uint64_t tex_epoch = 0;         // frr_texture_upload calls so far (DrawSig: a user VS may sample a texture)
+    uint64_t sync_epoch = 0;        // frr_sync calls so far (DrawSig of a device-bound mesh: rewritten in place behind one?)
     hipEvent_t ev_verify = nullptr;
     bool verify_pending = false;
     DrawSig verify_sig;
@@ -240,9 +246,13 @@ struct frr_ctx {
     bool exported[2] = {false, false};
     hipStream_t export_stream[2] = {nullptr, nullptr};
     hipEvent_t ev_export = nullptr;
-    // frr_frame_wait: the next kernel that writes the frame targets waits for this event
-    hipEvent_t ev_wait = nullptr;
-    bool wait_pending = false;
+    // frr_frame_wait: one event per stream handed in (recorded on it), pending until a target write issued after the latest
+    // frr_frame_wait consumes them; every target write until then -- a deferred clear of an earlier frame or binding too --
+    // waits for all of them.  Events are reused (wait_pool).
+    struct FrameWait { hipStream_t stream; hipEvent_t ev; };
+    std::vector<FrameWait> waits;
+    std::vector<hipEvent_t> wait_pool;
+    uint32_t wait_serial = 0;       // frr_frame_wait calls so far
     size_t fan_hint = 0;       // fan capacity asked for by a draw that overflowed
     int bin_g = 0;             // option bin_chunks: override the number of binning chunks (dev)
     uint32_t ent_slot_override = 0; // option tile_slot_records: per-tile slot of bins2 in records (tests of the overflow arena)
@@ -606,15 +616,27 @@ template <int K, int PS> void launch_raster(frr_ctx *c, const RasterArgs &a, uin
     }
 }
 
-// the clear itself (k_clear), on the caller's stream
-int clear_now(frr_ctx *c, uint32_t packed, float depth)
+// frr_frame_wait: the target write about to go on `ts` waits for every pending stream; `consume`: the write was issued
+// after the latest frr_frame_wait (the one the waits are for), so later writes follow it and need not wait themselves
+int apply_waits(frr_ctx *c, hipStream_t ts, bool consume)
+{
+    for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(ts, w.ev, 0));
+    if (consume) {
+        for (const frr_ctx::FrameWait &w : c->waits) c->wait_pool.push_back(w.ev);
+        c->waits.clear();
+    }
+    return FRR_OK;
+}
+
+// the clear itself (k_clear), on the caller's stream; `issued_after_waits`: the frr_clear came after the latest frr_frame_wait
+int clear_now(frr_ctx *c, uint32_t packed, float depth, bool issued_after_waits)
 {
     const FrameState &f = c->fs;
     const uint32_t n = c->W * c->H, n4 = n / 4;
     hipStream_t ts = tstream_of(c);
     if (ts == c->tstream2) c->t2_dirty = c->t2_xdirty = true;
     if (ts == c->tstream1) c->t1_dirty = c->t1_xdirty = true;
-    if (c->wait_pending) { HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_wait, 0)); c->wait_pending = false; }   // frr_frame_wait
+    { int rc = apply_waits(c, ts, issued_after_waits); if (rc != FRR_OK) return rc; }
     {
         ProfScope p(c, KID_CLEAR, ts);
         uint32_t grid = std::min<uint32_t>((n4 + 255) / 256, 2048);
@@ -633,7 +655,7 @@ int settle_targets(frr_ctx *c)
 {
     FrameState &f = c->fs;
     if (f.clear_pending) {
-        int rc = clear_now(c, f.clear_rgba, f.clear_depth);
+        int rc = clear_now(c, f.clear_rgba, f.clear_depth, f.clear_wait_serial == c->wait_serial);
         if (rc != FRR_OK) return rc;
         f.clear_pending = f.unowned_debt = false;
     } else if (f.unowned_debt) {
@@ -641,6 +663,8 @@ int settle_targets(frr_ctx *c)
         if (own.blocked) blocked_rows(f.debt_tiles_y, f.rank, f.world, &own.brow0, &own.brow1);
         if (tstream_of(c) == c->tstream2) c->t2_dirty = c->t2_xdirty = true;
         if (tstream_of(c) == c->tstream1) c->t1_dirty = c->t1_xdirty = true;
+        // (the rest of a clear issued with an earlier draw: it follows the pending waits, the next frame's writes consume them)
+        { int rc = apply_waits(c, tstream_of(c), false); if (rc != FRR_OK) return rc; }
         hipLaunchKernelGGL(k_clear_unowned_rows, dim3(c->H), dim3(256), 0, tstream_of(c), (uint32_t *)f.color, (uint32_t *)f.depth,
                            f.tri_id, c->W, c->H, own, f.clear_rgba, f.clear_depth);
         HIP_TRY(c, hipGetLastError());
@@ -743,8 +767,17 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     f.geom_nblocks = nblocks;
     f.geom_seq = cmd.seq;
     f.geom_vs = m.vs; f.geom_ntris = nt;
-    f.geom_mesh = m.dev; f.geom_mesh_gen = m.gen;   // (the uniforms' float fields: the struct has padding in front of its texture pointer)
-    f.geom_duni_hash = fnv1a(&cmd.duni, offsetof(DevUniforms, flat_color) + sizeof cmd.duni.flat_color) ^ (fnv1a(cmd.duni.user, sizeof cmd.duni.user) * 31u);
+    f.geom_mesh = m.dev; f.geom_mesh_gen = m.gen;
+    {   // (field ranges without padding: the struct has some in front of its texture pointer)
+        const DevUniforms &du = cmd.duni;
+        uint64_t h = fnv1a(&du, offsetof(DevUniforms, flat_color) + sizeof du.flat_color);
+        h = fnv1a(&du.tex, offsetof(DevUniforms, tex_h) + sizeof du.tex_h - offsetof(DevUniforms, tex), h);
+        h = fnv1a(du.user, sizeof du.user, h);
+        h = fnv1a(du.slot_tex, offsetof(DevUniforms, slot_h) + sizeof du.slot_h - offsetof(DevUniforms, slot_tex), h);
+        f.geom_duni_hash = h;
+    }
+    f.geom_tex_epoch = c->tex_epoch;
+    f.geom_sync_epoch = m.owned ? 0 : c->sync_epoch;   // (a host-uploaded mesh cannot change under the library)
     f.tris_in += nt; f.draws += 1;
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
@@ -870,6 +903,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         DrawSig sig;
         memset(&sig, 0, sizeof sig);
         sig.mesh = f.geom_mesh; sig.mesh_gen = f.geom_mesh_gen; sig.ntris = f.geom_ntris; sig.duni_hash = f.geom_duni_hash; sig.join_epoch = c->join_epoch;
+        sig.tex_epoch = f.geom_tex_epoch; sig.sync_epoch = f.geom_sync_epoch;
         sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
         sig.blocked = f.part_blocked ? 1 : 0; sig.filter = f.geom_filter.active ? 1 : 0; sig.fy0 = f.geom_filter.y0; sig.fy1 = f.geom_filter.y1;
         sig.gset = f.gset; sig.bset = bi;
@@ -882,10 +916,9 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         }
     }
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // the tile kernel runs on the targets' stream, after the binning
-    if (c->wait_pending) {   // frr_frame_wait: the targets' next writer follows what the caller's stream held
-        HIP_TRY(c, hipStreamWaitEvent(tstream_of(c), c->ev_wait, 0));
-        c->wait_pending = false;
-    }
+    // frr_frame_wait: the targets' next writer follows what those streams held (a replay re-issues an earlier write: it
+    // waits too, but leaves the waits to the write they were asked for)
+    if ((rc = apply_waits(c, tstream_of(c), !c->in_replay)) != FRR_OK) return rc;
     if (grid && um) {
         hipStream_t ts = tstream_of(c);
         ProfScope p(c, KID_RASTER, ts);
@@ -1092,8 +1125,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     ok = ok && hipEventCreateWithFlags(&c->ev_t2, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_t1, hipEventDisableTiming) == hipSuccess;
     for (auto &e : c->ev_bin) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_verify, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_export, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&c->ev_wait, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->ev_verify, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_export, hipEventDisableTiming) == hipSuccess;
     if (!ok) { frr_destroy(c); return FRR_ERR_NOMEM; }
     c->fs.color = c->own_color[0]; c->fs.depth = c->own_depth[0]; c->fs.tri_id = c->own_tri_id[0];
     {
@@ -1153,7 +1185,9 @@ void frr_destroy(frr_ctx *c)
     if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
     for (auto &e : c->ev_bin) if (e) (void)hipEventDestroy(e);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (hipEvent_t e : {c->ev_verify, c->ev_export, c->ev_wait}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_verify, c->ev_export}) if (e) (void)hipEventDestroy(e);
+    for (const frr_ctx::FrameWait &w : c->waits) (void)hipEventDestroy(w.ev);
+    for (hipEvent_t e : c->wait_pool) (void)hipEventDestroy(e);
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
     // (back to the pool in the reverse order of their typical acquisition, so that the next ctx gets them in the same roles)
     release_stream(c->device, c->gstream);
@@ -1351,6 +1385,7 @@ int frr_texture_upload(frr_ctx *c, int slot, const uint8_t *rgba, uint32_t w, ui
     if (h < w) return fail(c, FRR_ERR_UNSUPPORTED, "texture height < width: sample_2d clamps y with width (renderer.rs:523) and would index out of bounds");
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // the draws issued so far sample the old texture
+    c->tex_epoch += 1;                                     // ... and a user VS may sample it: no pass is proven for the new one
     Texture &t = c->tex[slot];
     if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
     size_t bytes = (size_t)w * h * 4;
@@ -1483,9 +1518,10 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
             HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_export, 0));
         }
     }
-    if (c->clear_eager) { f.clear_pending = false; return clear_now(c, packed, depth); }
+    if (c->clear_eager) { f.clear_pending = false; return clear_now(c, packed, depth, true); }
     f.clear_rgba = packed; f.clear_depth = depth;
     f.clear_pending = true;
+    f.clear_wait_serial = c->wait_serial;
     return FRR_OK;
 }
 
@@ -1578,15 +1614,27 @@ int frr_frame_wait(frr_ctx *c, void *stream)
 {
     if (!c) return FRR_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventRecord(c->ev_wait, stream ? (hipStream_t)stream : c->stream));
-    c->wait_pending = true;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    frr_ctx::FrameWait *w = nullptr;
+    for (frr_ctx::FrameWait &p : c->waits) if (p.stream == st) w = &p;   // (the same stream again: the later record covers both)
+    if (!w) {
+        hipEvent_t e = nullptr;
+        if (!c->wait_pool.empty()) { e = c->wait_pool.back(); c->wait_pool.pop_back(); }
+        else HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->waits.push_back({st, e});
+        w = &c->waits.back();
+    }
+    HIP_TRY(c, hipEventRecord(w->ev, st));
+    c->wait_serial += 1;
     return FRR_OK;
 }
 
 int frr_sync(frr_ctx *c)
 {
     if (!c) return FRR_ERR_INVALID;
-    return finish(c);
+    const int rc = finish(c);
+    c->sync_epoch += 1;   // the caller may rewrite a device-bound mesh in place now: its passes are verified again (DrawSig)
+    return rc;
 }
 
 int frr_readback(frr_ctx *c, uint8_t *rgba, float *depth, uint32_t *tri_id)

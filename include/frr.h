@@ -147,7 +147,9 @@ typedef struct frr_stats {
  * tile kernels, on the library's streams.  A caller that rewrites such a mesh in place therefore (1) orders the rewrite
  * BEHIND the draws issued so far -- frr_frame_fence(ctx, the stream it rewrites on) -- and (2) binds the mesh again
  * (frr_mesh_bind_device: the library's streams then wait for that stream once) before the next draw.  frr_sync in place
- * of (1) and (2) is always sufficient. */
+ * of (1) and (2) is always sufficient: frr_sync before the rewrite, and again after it when the rewrite is on a stream
+ * other than the ctx's or the next draw follows it without a host wait.  (The library does not trust what it learnt
+ * about a device-bound mesh's passes across a frr_sync: the next pass of it is verified again -- frr_frame_fence.) */
 int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ctx **out);
 void frr_destroy(frr_ctx *ctx);
 const char *frr_last_error(const frr_ctx *ctx);
@@ -256,13 +258,19 @@ int frr_draw(frr_ctx *ctx, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t 
  * The frames it fences are whole: like the reference's draw (renderer.rs:269-384 has no failure path) a draw of this
  * library cannot fail -- a raster pass whose need of the internal work lists is not known to fit is checked on the host,
  * and repaired, before frr_raster / frr_draw returns (the call then waits for the pass's binning launch, not for its tile
- * kernel; a pass that repeats a mesh, uniforms, window and partition already seen to fit is not waited for).
+ * kernel; a pass that repeats a mesh registration, uniforms -- texture pointers and sizes included --, window and partition
+ * already seen to fit, with no frr_texture_upload since and, for a device-bound mesh, no frr_sync since, is not waited
+ * for).
  * `stream` has to stay alive until the second frr_clear from now when it fenced the ctx's OWN targets (that frr_clear
  * records an event on it: frr_target_ptrs). */
 int frr_frame_fence(frr_ctx *ctx, void *stream);
 /* The reverse edge: the next kernel that WRITES the frame targets (the pending frr_clear, the next tile kernel) waits for
  * what `stream` (NULL = the ctx's stream) holds now -- e.g. an exchange that still reads a caller-bound target set which is
  * about to be bound for a new frame under option bound_targets_in_flight, where no frame work runs on the ctx's stream.
+ * Calls add up: after frr_frame_wait on several streams that write waits for all of them.  "That write" is the first one
+ * issued after the call (a frr_clear or frr_raster / frr_draw from then on); a write issued before it that the library
+ * performs later -- a deferred clear of the targets bound before, run by frr_bind_targets -- waits too, but does not
+ * take the wait away from it.
  * (The ctx's OWN targets need no such call: the library orders a set's next frame behind whatever was queued on the stream
  * the set's pointers were handed to by frr_target_ptrs / frr_frame_fence, up to the frr_clear that starts that frame.) */
 int frr_frame_wait(frr_ctx *ctx, void *stream);
