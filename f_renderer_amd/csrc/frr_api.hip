@@ -95,6 +95,21 @@ struct UserModule {
     hipFunction_t geom = nullptr, clip = nullptr, sweep = nullptr, span[2][6] = {};
 };
 
+// One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
+struct FrameStream {
+    hipStream_t st = nullptr;
+    hipEvent_t ev = nullptr;   // joins it into a caller's stream (fence_stream)
+    bool dirty = false;        // it holds work `stream` has not waited for
+    bool xdirty = false;       // ... that the stream of the latest frr_frame_fence (frr_ctx::xfence) has not waited for
+    uint32_t joined = 0;       // the join_epoch in which it last waited for `stream` (gstream_join)
+};
+// The tile kernel that last read a workspace set: the second stream waits for it before it overwrites the set.
+struct ReaderFence {
+    hipEvent_t ev = nullptr; bool pending = false; // fires when the latest tile kernel that reads this set is done
+    hipStream_t stream = nullptr;                  // ... on this stream
+    bool recorded = false;                         // the event was recorded right behind that kernel
+};
+
 // Workspace of one geometry pass / one raster pass.  There are two of each, used alternately (parity of the pass), so
 // that the geometry + binning kernels of pass n + 1 can run on the ctx's second stream while the tile kernel of pass n
 // still reads what pass n left (frr_device.h: GeomTab / BinTab are the device-side halves of the same scheme).
@@ -109,17 +124,13 @@ struct GeomSet {
     uint4 *pbox = nullptr; size_t pbox_cap = 0;
     uint32_t *bcount = nullptr; size_t bcount_cap = 0;          // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
     uint2 *clipq = nullptr; size_t clipq_cap = 0;               // [input triangles] the clip kernel's queue (GeomArgs::clipq)
-    hipEvent_t reader_ev = nullptr; bool reader_pending = false; // fires when the latest tile kernel that reads this set is done
-    hipStream_t reader_stream = nullptr;                         // ... on this stream
-    bool reader_recorded = false;                                // the event was recorded right behind that kernel
+    ReaderFence reader;
 };
 struct BinSet {
     uint4 *bins = nullptr; size_t bin_cap = 0;   // 16-byte cull records, one per (triangle, tile) pair
     uint4 *bins2 = nullptr; size_t bin2_cap = 0; // the same in near-first order per tile (tile kernel pre-pass)
     uint32_t *bin_matrix = nullptr; size_t bin_matrix_cap = 0; // [G][ntiles] per-chunk tile histograms
-    hipEvent_t reader_ev = nullptr; bool reader_pending = false;
-    hipStream_t reader_stream = nullptr;
-    bool reader_recorded = false;
+    ReaderFence reader;
 };
 
 struct GeomFilter { bool active; int32_t y0, y1; int rank, world; bool blocked; };
@@ -197,17 +208,17 @@ struct frr_ctx {
     int overlap = 2;                // option overlap: 0 never use gstream, 1 always, 2 (default) for passes with varyings (exec_geometry)
     bool g_used = false;            // some pass has run on gstream since the streams were last drained (cross-stream events are needed)
     // The ctx's own frame targets: TWO sets.  A frame that starts with frr_clear on own targets takes the other set and
-    // its tile kernels the other tile stream (tstream2 for set 1), so that the tile kernel of frame n + 1 fills the drain
+    // its tile kernels the other tile stream (tstream[1] for set 1), so that the tile kernel of frame n + 1 fills the drain
     // of frame n's (2,040 tiles on 1,536 workgroup slots end with a third of the chip idle).  Nobody can look at own targets
     // except through this library (frr_readback, frr_target_ptrs, which join the streams first), so the only visible
     // change is that frr_target_ptrs' pointers are those of the CURRENT frame.  Caller-bound targets: one set, one stream.
     uint8_t *own_color[2] = {}; float *own_depth[2] = {}; uint32_t *own_tri_id[2] = {};
-    hipStream_t tstream2 = nullptr;  // everything of the frames that use own target set 1 (or, option bound_targets_in_flight, of every other frame)
-    hipStream_t tstream1 = nullptr;  // option bound_targets_in_flight: the frames in between (the caller's stream then carries no frame work at all)
-    hipEvent_t ev_t2 = nullptr, ev_t1 = nullptr;   // join them into a caller's stream
-    bool t2_dirty = false, t1_dirty = false;       // they hold work `stream` has not waited for
-    bool t2_xdirty = false, t1_xdirty = false;     // ... that the stream of the latest frr_frame_fence has not waited for
-    hipStream_t xfence = nullptr;                  //     (that stream)
+    // The private frame streams, by target set index (tstream_of).  [1]: everything of the frames that use own target set 1
+    // (or, option bound_targets_in_flight, of every other frame); [0], option bound_targets_in_flight: the frames in between
+    // (the caller's stream then carries no frame work at all).  [1] is acquired first (frr_clear), and calls that go over
+    // both go over [1] first.
+    FrameStream tstream[2];
+    hipStream_t xfence = nullptr;    // the stream of the latest frr_frame_fence (FrameStream::xdirty)
     bool bound_in_flight = false;    // option bound_targets_in_flight: frames on caller-bound targets alternate between the two private streams too;
                                      // the caller binds another target set for each of two consecutive frames and fences its reads (frr_frame_fence)
     int frames_in_flight = 2;        // option frames_in_flight (1: one target set, everything on the caller's stream)
@@ -221,7 +232,7 @@ struct frr_ctx {
     uint64_t bin_serial = 0;
     // inputs the caller wrote on `stream` (a device-bound mesh) must be visible to the ctx's private streams: every bind
     // starts a new epoch, and a private stream waits for `stream` once per epoch before its next geometry pass
-    uint32_t join_epoch = 1, joined_g = 0, joined_t1 = 0, joined_t2 = 0;
+    uint32_t join_epoch = 1, joined_g = 0;   // (joined_g: gstream's; a frame stream's is FrameStream::joined)
     // command log since the last synchronisation point / frr_clear (finish(): replay)
     std::vector<Cmd> log;
     uint32_t next_seq = 1, epoch = 1;
@@ -305,7 +316,6 @@ int fail(frr_ctx *c, int code, const std::string &msg)
     } while (0)
 
 
-// the stream of everything that touches the current frame targets
 bool own_targets(const frr_ctx *c)
 {
     const FrameState &f = c->fs;
@@ -313,15 +323,17 @@ bool own_targets(const frr_ctx *c)
 }
 // do consecutive frames (frr_clear) alternate between two streams / target sets / workspace sets / lanes?
 bool frames_alternate(const frr_ctx *c) { return c->frames_in_flight == 2 && (own_targets(c) || c->bound_in_flight); }
+// the stream of everything that touches the current frame targets: `stream`, or the current target set's c->tstream[tset]
 hipStream_t tstream_of(const frr_ctx *c)
 {
-    if (c->bound_in_flight && !own_targets(c) && c->tstream1 && c->tstream2) return c->fs.tset ? c->tstream2 : c->tstream1;
-    return (c->tstream2 && c->fs.tset == 1 && own_targets(c)) ? c->tstream2 : c->stream;
+    const hipStream_t t = c->tstream[c->fs.tset].st;
+    if (own_targets(c)) return t && c->fs.tset == 1 ? t : c->stream;
+    return c->bound_in_flight && c->tstream[0].st && c->tstream[1].st ? t : c->stream;
 }
 // the stream of the latest geometry pass and of the binning that follows it: the second stream, or the targets' stream
 hipStream_t gstream_of(const frr_ctx *c) { return c->fs.on_g ? c->gstream : tstream_of(c); }
 // do passes ever run beside each other on this ctx (workspace sets then carry events)?
-bool multi_stream(const frr_ctx *c) { return c->g_used || c->tstream2 != nullptr || c->tstream1 != nullptr; }
+bool multi_stream(const frr_ctx *c) { return c->g_used || c->tstream[0].st || c->tstream[1].st; }
 
 // the ctx's own target set t (the second one is allocated on first use)
 int ensure_own_set(frr_ctx *c, int t)
@@ -338,36 +350,29 @@ int ensure_own_set(frr_ctx *c, int t)
 // all streams idle
 int drain(frr_ctx *c)
 {
-    if (c->gstream) HIP_TRY(c, hipStreamSynchronize(c->gstream));
-    if (c->tstream2) HIP_TRY(c, hipStreamSynchronize(c->tstream2));
-    if (c->tstream1) HIP_TRY(c, hipStreamSynchronize(c->tstream1));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->t2_dirty = c->t1_dirty = c->t2_xdirty = c->t1_xdirty = false;
+    for (hipStream_t st : {c->gstream, c->tstream[1].st, c->tstream[0].st, c->stream}) if (st) HIP_TRY(c, hipStreamSynchronize(st));
+    for (FrameStream &t : c->tstream) t.dirty = t.xdirty = false;
     c->g_used = false;
-    for (GeomSet &S : c->gset) S.reader_pending = false;
-    for (BinSet &B : c->bset) B.reader_pending = false;
+    for (int i = 0; i < 2; ++i) c->gset[i].reader.pending = c->bset[i].reader.pending = false;
     return FRR_OK;
 }
 // a caller's stream waits for the ctx's frame streams: what is enqueued on it next sees every frame issued so far
 int fence_stream(frr_ctx *c, hipStream_t st)
 {
     const bool own = st == c->stream;
-    if (!own && st != c->xfence) { c->xfence = st; c->t1_xdirty = c->tstream1 != nullptr; c->t2_xdirty = c->tstream2 != nullptr; }
-    if (c->tstream2 && (own ? c->t2_dirty : c->t2_xdirty)) {
-        HIP_TRY(c, hipEventRecord(c->ev_t2, c->tstream2));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_t2, 0));
-    }
-    if (c->tstream1 && (own ? c->t1_dirty : c->t1_xdirty)) {
-        HIP_TRY(c, hipEventRecord(c->ev_t1, c->tstream1));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_t1, 0));
-    }
-    if (own) c->t2_dirty = c->t1_dirty = false;
-    else {
-        c->t2_xdirty = c->t1_xdirty = false;
-        if (!(c->bound_in_flight && c->tstream1)) {   // (frames may have run on the ctx's stream itself)
-            HIP_TRY(c, hipEventRecord(c->ev_join, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(st, c->ev_join, 0));
+    if (!own && st != c->xfence) { c->xfence = st; for (FrameStream &t : c->tstream) t.xdirty = t.st != nullptr; }
+    for (int i = 1; i >= 0; --i) {
+        FrameStream &t = c->tstream[i];
+        bool &unjoined = own ? t.dirty : t.xdirty;   // (set only while t.st exists)
+        if (unjoined) {
+            HIP_TRY(c, hipEventRecord(t.ev, t.st));
+            HIP_TRY(c, hipStreamWaitEvent(st, t.ev, 0));
         }
+        unjoined = false;
+    }
+    if (!own && !(c->bound_in_flight && c->tstream[0].st)) {   // (frames may have run on the ctx's stream itself)
+        HIP_TRY(c, hipEventRecord(c->ev_join, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_join, 0));
     }
     return FRR_OK;
 }
@@ -387,15 +392,15 @@ template <typename T> int ensure(frr_ctx *c, T *&p, size_t &cap, size_t need)
 
 // ---- cross-stream ordering (no-ops when everything runs on one stream) ----------------------------------------------
 // the second stream waits until the latest tile kernel that reads a workspace set is done
-template <class SET> int gstream_wait_readers(frr_ctx *c, SET &S)
+int gstream_wait_readers(frr_ctx *c, ReaderFence &r)
 {
-    if (!S.reader_pending) return FRR_OK;
-    S.reader_pending = false;
-    if (S.reader_stream == gstream_of(c)) return FRR_OK;   // same stream: already in order
+    if (!r.pending) return FRR_OK;
+    r.pending = false;
+    if (r.stream == gstream_of(c)) return FRR_OK;   // same stream: already in order
     // (the event may not have been recorded at the launch: then now, after whatever else the reader's stream has been given
     // since -- more than needed, and right for the rare change of pattern this serves)
-    if (!S.reader_recorded) HIP_TRY(c, hipEventRecord(S.reader_ev, S.reader_stream));
-    HIP_TRY(c, hipStreamWaitEvent(gstream_of(c), S.reader_ev, 0));
+    if (!r.recorded) HIP_TRY(c, hipEventRecord(r.ev, r.stream));
+    HIP_TRY(c, hipStreamWaitEvent(gstream_of(c), r.ev, 0));
     return FRR_OK;
 }
 // the stream of the geometry pass about to be issued waits for everything the caller's stream holds so far (mesh data
@@ -404,7 +409,7 @@ int gstream_join(frr_ctx *c)
 {
     hipStream_t st = gstream_of(c);
     if (st == c->stream) return FRR_OK;
-    uint32_t &joined = st == c->gstream ? c->joined_g : (st == c->tstream1 ? c->joined_t1 : c->joined_t2);
+    uint32_t &joined = st == c->gstream ? c->joined_g : c->tstream[c->fs.tset].joined;   // (tstream_of)
     if (joined == c->join_epoch) return FRR_OK;
     HIP_TRY(c, hipEventRecord(c->ev_join, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_join, 0));
@@ -420,19 +425,18 @@ int tstream_wait_gstream(frr_ctx *c)
     HIP_TRY(c, hipStreamWaitEvent(tstream_of(c), e, 0));
     return FRR_OK;
 }
-// a tile kernel has just been launched: the workspace sets it reads are busy until it is done
-int tile_launched(frr_ctx *c, GeomSet &gs, BinSet &bs)
+// a tile kernel has just been launched on `ts`: the workspace sets it reads are busy until it is done
+int tile_launched(frr_ctx *c, hipStream_t ts, GeomSet &gs, BinSet &bs)
 {
-    hipStream_t ts = tstream_of(c);
-    if (ts == c->tstream2) c->t2_dirty = c->t2_xdirty = true;
-    if (ts == c->tstream1) c->t1_dirty = c->t1_xdirty = true;
     if (!multi_stream(c)) return FRR_OK;   // everything has run on one stream so far
     // Frames in flight give every frame stream its own workspace sets: the next writer of a set is on the reader's stream, and
     // no event is needed (should the pattern change, gstream_wait_readers records one late).  With geometry + binning on the
     // second stream the event is what lets that stream run beside the NEXT tile kernel: recorded right here.
     const bool eager = c->g_used;
-    gs.reader_pending = bs.reader_pending = true; gs.reader_stream = bs.reader_stream = ts; gs.reader_recorded = bs.reader_recorded = eager;
-    if (eager) { HIP_TRY(c, hipEventRecord(gs.reader_ev, ts)); HIP_TRY(c, hipEventRecord(bs.reader_ev, ts)); }
+    for (ReaderFence *r : {&gs.reader, &bs.reader}) {
+        r->pending = true; r->stream = ts; r->recorded = eager;
+        if (eager) HIP_TRY(c, hipEventRecord(r->ev, ts));
+    }
     return FRR_OK;
 }
 
@@ -590,9 +594,8 @@ SpanShape span_shape(const frr_ctx *c, uint32_t grid, uint64_t ntris, int ps_id)
     return {4, 6};
 }
 
-template <int K, int PS> void launch_raster(frr_ctx *c, const RasterArgs &a, uint32_t grid, const SpanShape sh, const DevUniforms &du, bool count_frags)
+template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const RasterArgs &a, uint32_t grid, const SpanShape sh, const DevUniforms &du, bool count_frags)
 {
-    hipStream_t ts = tstream_of(c);
     ProfScope p(c, KID_RASTER, ts);
     if (c->raster_sweep) {
         hipLaunchKernelGGL((k_raster<K, PS>), dim3(grid), dim3(256), 0, ts, a, du);
@@ -616,11 +619,15 @@ template <int K, int PS> void launch_raster(frr_ctx *c, const RasterArgs &a, uin
     }
 }
 
-// frr_frame_wait: the target write about to go on `ts` waits for every pending stream; `consume`: the write was issued
-// after the latest frr_frame_wait (the one the waits are for), so later writes follow it and need not wait themselves
-int apply_waits(frr_ctx *c, hipStream_t ts, bool consume)
+// Every launch that writes the frame targets goes on the stream this returns (*ts, the targets' stream).  The write follows
+// every stream of a pending frr_frame_wait, and its stream, if a frame stream, is dirty until fence_stream joins it.
+// `consume`: the write was issued after the latest frr_frame_wait (the one the waits are for), so later writes follow it
+// and need not wait themselves.
+int target_write(frr_ctx *c, bool consume, hipStream_t *ts)
 {
-    for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(ts, w.ev, 0));
+    *ts = tstream_of(c);
+    if (*ts != c->stream) c->tstream[c->fs.tset].dirty = c->tstream[c->fs.tset].xdirty = true;
+    for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(*ts, w.ev, 0));
     if (consume) {
         for (const frr_ctx::FrameWait &w : c->waits) c->wait_pool.push_back(w.ev);
         c->waits.clear();
@@ -628,15 +635,13 @@ int apply_waits(frr_ctx *c, hipStream_t ts, bool consume)
     return FRR_OK;
 }
 
-// the clear itself (k_clear), on the caller's stream; `issued_after_waits`: the frr_clear came after the latest frr_frame_wait
+// the clear itself (k_clear), on the targets' stream; `issued_after_waits`: the frr_clear came after the latest frr_frame_wait
 int clear_now(frr_ctx *c, uint32_t packed, float depth, bool issued_after_waits)
 {
     const FrameState &f = c->fs;
     const uint32_t n = c->W * c->H, n4 = n / 4;
-    hipStream_t ts = tstream_of(c);
-    if (ts == c->tstream2) c->t2_dirty = c->t2_xdirty = true;
-    if (ts == c->tstream1) c->t1_dirty = c->t1_xdirty = true;
-    { int rc = apply_waits(c, ts, issued_after_waits); if (rc != FRR_OK) return rc; }
+    hipStream_t ts;
+    { int rc = target_write(c, issued_after_waits, &ts); if (rc != FRR_OK) return rc; }
     {
         ProfScope p(c, KID_CLEAR, ts);
         uint32_t grid = std::min<uint32_t>((n4 + 255) / 256, 2048);
@@ -661,11 +666,10 @@ int settle_targets(frr_ctx *c)
     } else if (f.unowned_debt) {
         RowOwner own = {f.rank, f.world, f.part_blocked ? 1 : 0, 0, 0};
         if (own.blocked) blocked_rows(f.debt_tiles_y, f.rank, f.world, &own.brow0, &own.brow1);
-        if (tstream_of(c) == c->tstream2) c->t2_dirty = c->t2_xdirty = true;
-        if (tstream_of(c) == c->tstream1) c->t1_dirty = c->t1_xdirty = true;
         // (the rest of a clear issued with an earlier draw: it follows the pending waits, the next frame's writes consume them)
-        { int rc = apply_waits(c, tstream_of(c), false); if (rc != FRR_OK) return rc; }
-        hipLaunchKernelGGL(k_clear_unowned_rows, dim3(c->H), dim3(256), 0, tstream_of(c), (uint32_t *)f.color, (uint32_t *)f.depth,
+        hipStream_t ts;
+        { int rc = target_write(c, false, &ts); if (rc != FRR_OK) return rc; }
+        hipLaunchKernelGGL(k_clear_unowned_rows, dim3(c->H), dim3(256), 0, ts, (uint32_t *)f.color, (uint32_t *)f.depth,
                            f.tri_id, c->W, c->H, own, f.clear_rgba, f.clear_depth);
         HIP_TRY(c, hipGetLastError());
         f.unowned_debt = false;
@@ -743,7 +747,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     // second stream: after whatever the caller's stream holds that this pass may read (first use), and after the tile
     // kernel that last read this workspace
     if ((rc = gstream_join(c)) != FRR_OK) return rc;
-    if ((rc = gstream_wait_readers(c, S)) != FRR_OK) return rc;
+    if ((rc = gstream_wait_readers(c, S.reader)) != FRR_OK) return rc;
     GeomArgs g;
     g.in = m.dev; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
     g.fan_cap = (uint32_t)fan_cap;
@@ -877,7 +881,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         a.bin_cap = (uint32_t)std::min<size_t>(B.bin_cap, 0xBFFFFFFFu);
         if ((rc = ensure(c, B.bins2, B.bin2_cap, (size_t)ltiles * SL + a.bin_cap)) != FRR_OK) return rc;
         a.bins2 = B.bins2;
-        if ((rc = gstream_wait_readers(c, B)) != FRR_OK) return rc;   // the tile kernel that last read this workspace
+        if ((rc = gstream_wait_readers(c, B.reader)) != FRR_OK) return rc;   // the tile kernel that last read this workspace
         {
             ProfScope p(c, KID_BIN_SEG, gs);
             hipLaunchKernelGGL(k_bin_seg, dim3(G + do_scan), dim3(BIN_WG), lds, gs, a, ltiles, B.bin_matrix, stage_cap,
@@ -888,8 +892,8 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     } else {
         // fallback for frames with more tiles than fit LDS counters: global atomics (one set of tile tables: after every
         // tile kernel so far)
-        for (GeomSet &G2 : c->gset) if ((rc = gstream_wait_readers(c, G2)) != FRR_OK) return rc;
-        for (BinSet &B2 : c->bset) if ((rc = gstream_wait_readers(c, B2)) != FRR_OK) return rc;
+        for (GeomSet &G2 : c->gset) if ((rc = gstream_wait_readers(c, G2.reader)) != FRR_OK) return rc;
+        for (BinSet &B2 : c->bset) if ((rc = gstream_wait_readers(c, B2.reader)) != FRR_OK) return rc;
         if ((rc = scan_now(c)) != FRR_OK) return rc;
         const uint32_t bin_grid = (uint32_t)std::min<uint64_t>((f.geom_ntris + f.geom_fan_cap + 255) / 256, 2048);
         { ProfScope p(c, KID_BIN_COUNT, gs); hipLaunchKernelGGL(k_bin<false>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom_fan_cap); }
@@ -918,9 +922,9 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // the tile kernel runs on the targets' stream, after the binning
     // frr_frame_wait: the targets' next writer follows what those streams held (a replay re-issues an earlier write: it
     // waits too, but leaves the waits to the write they were asked for)
-    if ((rc = apply_waits(c, tstream_of(c), !c->in_replay)) != FRR_OK) return rc;
+    hipStream_t ts;
+    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
     if (grid && um) {
-        hipStream_t ts = tstream_of(c);
         ProfScope p(c, KID_RASTER, ts);
         int shi = 4;
         for (int k = 0; k < 6; ++k) if (kSpanShapes[k][0] == sh.nw && kSpanShapes[k][1] == sh.occ) shi = k;
@@ -931,15 +935,15 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         else (void)hipModuleLaunchKernel(um->span[cmd.count_frags ? 1 : 0][shi], grid, 1, 1, (unsigned)kSpanShapes[shi][0] * 64u, 1, 1, 0, ts, args, nullptr);
     } else if (grid) {
         switch (ps_id) {
-        case FRR_PS_DEPTH: launch_raster<0, FRR_PS_DEPTH>(c, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_FLAT: launch_raster<0, FRR_PS_FLAT>(c, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_COLOR: launch_raster<3, FRR_PS_COLOR>(c, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_PHONG: launch_raster<8, FRR_PS_PHONG>(c, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_BLINN: launch_raster<8, FRR_PS_BLINN>(c, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_DEPTH: launch_raster<0, FRR_PS_DEPTH>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_FLAT: launch_raster<0, FRR_PS_FLAT>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_COLOR: launch_raster<3, FRR_PS_COLOR>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_PHONG: launch_raster<8, FRR_PS_PHONG>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_BLINN: launch_raster<8, FRR_PS_BLINN>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
         }
     }
     HIP_TRY(c, hipGetLastError());
-    if ((rc = tile_launched(c, S, B)) != FRR_OK) return rc;
+    if ((rc = tile_launched(c, ts, S, B)) != FRR_OK) return rc;
     if (fuse) {
         f.clear_pending = false;
         // the tile rows of other ranks missed this clear: owed to the ctx's own targets (frr_readback shows the
@@ -1120,9 +1124,9 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     ok = ok && hipMalloc((void **)&c->tile_counts, (c->max_tiles + 1) * 4) == hipSuccess &&
          hipMalloc((void **)&c->tile_offsets, (c->max_tiles + 1) * 4) == hipSuccess &&
          hipMalloc((void **)&c->tile_cursor, (c->max_tiles + 1) * 4) == hipSuccess;
-    for (GeomSet &S : c->gset) ok = ok && hipEventCreateWithFlags(&S.reader_ev, hipEventDisableTiming) == hipSuccess;
-    for (BinSet &B : c->bset) ok = ok && hipEventCreateWithFlags(&B.reader_ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_t2, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_t1, hipEventDisableTiming) == hipSuccess;
+    for (GeomSet &S : c->gset) ok = ok && hipEventCreateWithFlags(&S.reader.ev, hipEventDisableTiming) == hipSuccess;
+    for (BinSet &B : c->bset) ok = ok && hipEventCreateWithFlags(&B.reader.ev, hipEventDisableTiming) == hipSuccess;
+    for (int i = 1; i >= 0; --i) ok = ok && hipEventCreateWithFlags(&c->tstream[i].ev, hipEventDisableTiming) == hipSuccess;
     for (auto &e : c->ev_bin) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_verify, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_export, hipEventDisableTiming) == hipSuccess;
@@ -1160,10 +1164,7 @@ void frr_destroy(frr_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->gstream) (void)hipStreamSynchronize(c->gstream);
-    if (c->tstream2) (void)hipStreamSynchronize(c->tstream2);
-    if (c->tstream1) (void)hipStreamSynchronize(c->tstream1);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipStream_t st : {c->gstream, c->tstream[1].st, c->tstream[0].st, c->stream}) if (st) (void)hipStreamSynchronize(st);
     prof_collect(c);
     for (auto &m : c->meshes) if (m.used && m.owned) (void)hipFree((void *)m.dev);
     for (auto &t : c->tex) if (t.dev) (void)hipFree(t.dev);
@@ -1179,10 +1180,9 @@ void frr_destroy(frr_ctx *c)
     if (c->dbg_tiles) (void)hipFree(c->dbg_tiles);
 #endif
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (GeomSet &S : c->gset) if (S.reader_ev) (void)hipEventDestroy(S.reader_ev);
-    for (BinSet &B : c->bset) if (B.reader_ev) (void)hipEventDestroy(B.reader_ev);
-    if (c->ev_t2) (void)hipEventDestroy(c->ev_t2);
-    if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
+    for (GeomSet &S : c->gset) if (S.reader.ev) (void)hipEventDestroy(S.reader.ev);
+    for (BinSet &B : c->bset) if (B.reader.ev) (void)hipEventDestroy(B.reader.ev);
+    for (int i = 1; i >= 0; --i) if (c->tstream[i].ev) (void)hipEventDestroy(c->tstream[i].ev);
     for (auto &e : c->ev_bin) if (e) (void)hipEventDestroy(e);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (hipEvent_t e : {c->ev_verify, c->ev_export}) if (e) (void)hipEventDestroy(e);
@@ -1190,9 +1190,7 @@ void frr_destroy(frr_ctx *c)
     for (hipEvent_t e : c->wait_pool) (void)hipEventDestroy(e);
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
     // (back to the pool in the reverse order of their typical acquisition, so that the next ctx gets them in the same roles)
-    release_stream(c->device, c->gstream);
-    release_stream(c->device, c->tstream1);
-    release_stream(c->device, c->tstream2);
+    for (hipStream_t st : {c->gstream, c->tstream[0].st, c->tstream[1].st}) release_stream(c->device, st);
     if (c->own_stream) release_stream(c->device, c->stream);
     delete c;
 }
@@ -1492,15 +1490,15 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
         // for the previous frame's tile kernel to drain; the old set's content is dead (the clear overwrites everything)
         const int t = f.tset ^ 1;
         { const int rc = ensure_own_set(c, t); if (rc != FRR_OK) return rc; }
-        if (!c->tstream2 && acquire_stream(c->device, &c->tstream2) != hipSuccess) return fail(c, FRR_ERR_HIP, "frame stream");
+        if (!c->tstream[1].st && acquire_stream(c->device, &c->tstream[1].st) != hipSuccess) return fail(c, FRR_ERR_HIP, "frame stream");
         f.tset = t;
         f.color = c->own_color[t]; f.depth = c->own_depth[t]; f.tri_id = c->own_tri_id[t];
         f.lane = t;    // ... and its own device tables: nothing the two frames' bookkeeping threads write is shared
     } else if (frames_alternate(c)) {
         // caller-bound targets, option bound_targets_in_flight: the caller has bound another target set for this frame;
         // the frame takes the other private stream, workspace set and lane
-        bool ok = (c->tstream2 || acquire_stream(c->device, &c->tstream2) == hipSuccess) &&
-                  (c->tstream1 || acquire_stream(c->device, &c->tstream1) == hipSuccess);
+        bool ok = (c->tstream[1].st || acquire_stream(c->device, &c->tstream[1].st) == hipSuccess) &&
+                  (c->tstream[0].st || acquire_stream(c->device, &c->tstream[0].st) == hipSuccess);
         if (!ok) return fail(c, FRR_ERR_HIP, "frame streams");
         f.tset ^= 1;
         f.lane = f.tset;
