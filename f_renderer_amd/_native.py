@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("FRR_LIB") or os.path.join(_HERE, "libfrr_hip.so")  # FRR_LIB: developer override
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h")]
 _HDR = os.path.join(_ROOT, "include", "frr.h")
 
 HIPCC_FLAGS = [
@@ -140,6 +140,7 @@ SIGNATURES = {
     "frr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "frr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "frr_profile_set_period": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "frr_tile_order_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "frr_profile_reset": (C.c_int, [C.c_void_p]),
     "frr_profile_get": (C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_float), _P(C.c_uint32)]),
     "frr_set_identity": (None, [_P(C.c_float)]),

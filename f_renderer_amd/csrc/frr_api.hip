@@ -1,6 +1,7 @@
 // frr_api.hip -- host side of libfrr_hip.so: the C ABI of include/frr.h over the kernels in
 // frr_kernels.h.  gfx950 only; no CPU fallback (every compute entry point needs the device).
 #include "frr_kernels.h"
+#include "frr_tile_order.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -130,6 +131,9 @@ struct BinSet {
     uint4 *bins = nullptr; size_t bin_cap = 0;   // 16-byte cull records, one per (triangle, tile) pair
     uint4 *bins2 = nullptr; size_t bin2_cap = 0; // the same in near-first order per tile (tile kernel pre-pass)
     uint32_t *bin_matrix = nullptr; size_t bin_matrix_cap = 0; // [G][ntiles] per-chunk tile histograms
+    uint32_t *tile_cost = nullptr; size_t tile_cost_cap = 0;   // [ntiles] records per tile of the latest tile kernel on this set
+    uint32_t *tile_perm = nullptr; size_t tile_perm_cap = 0;   // [ntiles] block -> tile order of the current pass (option tile_order)
+    bool cost_known = false; TileOrderKey cost_key = {};       // tile_cost was written by a pass with this key (frr_tile_order.h)
     ReaderFence reader;
 };
 
@@ -286,6 +290,8 @@ struct frr_ctx {
     int raster_nw = 0;         // option raster_nw: force 3 / 4 / 6 / 8 / 16 waves per tile workgroup (dev)
     int raster_occ = 0;        // option raster_occ: force the 6- or 8-waves-per-SIMD build of the tile kernel (dev)
     bool raster_sweep = false; // option raster_sweep: brute-force tile kernel instead of the span kernel
+    int tile_order = TILE_ORDER_FIXED;   // option tile_order: which block of the tile kernel takes which tile (frr_tile_order.h)
+    uint64_t ordered_passes = 0;   // raster passes whose tile kernel took a built order (frr_tile_order_passes)
 #ifdef FRR_DEBUG_COUNTERS
     unsigned long long *dbg_tiles = nullptr; // FRR_DEBUG_TILES: per-tile timeline of the latest tile kernel
 #endif
@@ -832,6 +838,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     a.dbg_tiles = c->dbg_tiles;
 #endif
     a.seg = nullptr; a.nseg = 0;
+    a.tile_perm = nullptr; a.tile_cost = nullptr;
     const int owned_rows = a.blocked ? a.brow1 - a.brow0 : (a.tiles_y > a.rank ? (a.tiles_y - a.rank + a.world - 1) / a.world : 0);
     const uint32_t grid = (uint32_t)a.tiles_x * owned_rows;
     if (a.tiles_x >= 2 && a.tiles_x < 65536 && grid < 65536u) a.tiles_x_magic = (uint32_t)(0x100000000ull / (uint64_t)a.tiles_x + 1ull);
@@ -858,10 +865,28 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         uint32_t G = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((f.geom_ntris + BIN_WG - 1) / BIN_WG, 1), BIN_MAX_G);
         if (c->bin_g > 0) G = (uint32_t)std::min(c->bin_g, BIN_MAX_G);
         G = std::min<uint32_t>(G, sh.nw == 3 ? 256u : (uint32_t)sh.nw * 64u); // the tile kernel reads one segment per thread (three waves: wave 0 reads a second one)
-        // (+ one workgroup that scans the geometry kernel's block sums, unless an earlier launch has; a binning workgroup
-        // fills a CU's LDS, so the launch stays within 256 workgroups: a 257th would wait for a whole one to finish)
-        int do_scan = f.scan_pending ? 1 : 0;
-        if (do_scan && G > 255u) G = 255u;
+        // Option tile_order 1: the tile kernel records each tile's records in tile_cost; a later pass over the same grid on
+        // this set orders its blocks heaviest first by them (build_tile_perm).  Measured no faster than the fixed order
+        // (DESIGN.md section 5), so off by default: then nothing is recorded and nothing built.
+        const size_t cost_cap0 = B.tile_cost_cap;
+        if ((rc = ensure(c, B.tile_cost, B.tile_cost_cap, ltiles)) != FRR_OK) return rc;
+        if ((rc = ensure(c, B.tile_perm, B.tile_perm_cap, ltiles)) != FRR_OK) return rc;
+        if (B.tile_cost_cap != cost_cap0) {   // new memory: no costs recorded yet (and defined ones until a tile kernel writes them)
+            B.cost_known = false;
+            HIP_TRY(c, hipMemsetAsync(B.tile_cost, 0, (size_t)ltiles * sizeof(uint32_t), gs));
+        }
+        const TileOrderKey okey = {grid, a.tiles_x, x0, x1, y0, y1, a.rank, a.world, a.blocked, sh.nw};
+        const bool ordered = tile_order_built(c->tile_order, c->in_replay, okey, B.cost_known, B.cost_key);
+        const bool record = c->tile_order == TILE_ORDER_HEAVY_FIRST;
+        a.tile_cost = record ? B.tile_cost : nullptr;
+        a.tile_perm = ordered ? B.tile_perm : nullptr;
+        const uint32_t perm_seed = c->tile_order == TILE_ORDER_RANDOM ? (uint32_t)fnv1a(&cmd.seq, sizeof cmd.seq) | 1u : 0u;
+        // (+ one workgroup that scans the geometry kernel's block sums, unless an earlier launch has, and builds the order;
+        // a binning workgroup fills a CU's LDS, so the launch stays within 256 workgroups: a 257th would wait for a whole
+        // one to finish)
+        const int do_scan = f.scan_pending ? 1 : 0;
+        const uint32_t extra = (do_scan || ordered) ? 1u : 0u;
+        if (extra && G > 255u) G = 255u;
         if ((rc = ensure(c, B.bin_matrix, B.bin_matrix_cap, (size_t)BIN_MAX_G * ((size_t)c->max_tiles + 1))) != FRR_OK) return rc;
         // dynamic LDS: tile counters + as many staged 16-B records as fit (a chunk emits ~1.8 records per triangle)
         constexpr size_t kLdsBudget = 160 * 1024 - 1024; // the kernel's static LDS is < 1 KB
@@ -884,9 +909,14 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         if ((rc = gstream_wait_readers(c, B.reader)) != FRR_OK) return rc;   // the tile kernel that last read this workspace
         {
             ProfScope p(c, KID_BIN_SEG, gs);
-            hipLaunchKernelGGL(k_bin_seg, dim3(G + do_scan), dim3(BIN_WG), lds, gs, a, ltiles, B.bin_matrix, stage_cap,
-                               f.geom_fan_cap, S.block_sums, S.block_prefix, f.geom_nblocks, do_scan);
+            hipLaunchKernelGGL(k_bin_seg, dim3(G + extra), dim3(BIN_WG), lds, gs, a, ltiles, B.bin_matrix, stage_cap,
+                               f.geom_fan_cap, S.block_sums, S.block_prefix, f.geom_nblocks, do_scan, perm_seed);
         }
+        // The tile kernel launched below writes every tile's cost -- unless the pass is cancelled (a list overflowed): then
+        // the costs stay what an earlier pass (or the zeroing above) left, and the replay of the pass writes them.  Any values
+        // give a permutation (build_tile_perm); only how well it orders depends on them.
+        B.cost_known = record; B.cost_key = okey;
+        if (ordered) ++c->ordered_passes;
         f.scan_pending = false;
         f.bpars[f.lane] = q; f.bset = bi;
     } else {
@@ -1174,7 +1204,7 @@ void frr_destroy(frr_ctx *c)
                                 c->cnt, c->tile_counts, c->tile_offsets, c->tile_cursor};
     for (GeomSet &S : c->gset) for (void *p : {(void *)S.block_sums, (void *)S.block_prefix, (void *)S.tinfo, (void *)S.fanbase, (void *)S.fan_okey, (void *)S.recs,
                                                (void *)S.vary, (void *)S.pbox, (void *)S.bcount, (void *)S.clipq}) ptrs.push_back(p);
-    for (BinSet &B : c->bset) for (void *p : {(void *)B.bins, (void *)B.bins2, (void *)B.bin_matrix}) ptrs.push_back(p);
+    for (BinSet &B : c->bset) for (void *p : {(void *)B.bins, (void *)B.bins2, (void *)B.bin_matrix, (void *)B.tile_cost, (void *)B.tile_perm}) ptrs.push_back(p);
     for (void *p : ptrs) if (p) (void)hipFree(p);
 #ifdef FRR_DEBUG_COUNTERS
     if (c->dbg_tiles) (void)hipFree(c->dbg_tiles);
@@ -1213,6 +1243,7 @@ int frr_set_option(frr_ctx *c, const char *name, int64_t v)
     else if (n == "fan_capacity") { if (v < 0) return fail(c, FRR_ERR_INVALID, "fan_capacity >= 0"); c->fan_cap_init = (size_t)v; }
     else if (n == "overlap") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "overlap: 0, 1 or 2"); c->overlap = (int)v; }
     else if (n == "bound_targets_in_flight") c->bound_in_flight = v != 0;
+    else if (n == "tile_order") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "tile_order: 0, 1 or 2"); c->tile_order = (int)v; }
     else if (n == "frames_in_flight") { if (v != 1 && v != 2) return fail(c, FRR_ERR_INVALID, "frames_in_flight: 1 or 2"); c->frames_in_flight = (int)v; }
     else return fail(c, FRR_ERR_INVALID, "unknown option");
     return FRR_OK;
@@ -1754,6 +1785,12 @@ int frr_profile_enable(frr_ctx *c, int enable)
     if (!c) return FRR_ERR_INVALID;
     prof_collect(c);
     c->prof_mask = enable < 0 ? 0xFFFFFFFFu : (uint32_t)enable;
+    return FRR_OK;
+}
+int frr_tile_order_passes(frr_ctx *c, uint64_t *passes)
+{
+    if (!c || !passes) return FRR_ERR_INVALID;
+    *passes = c->ordered_passes;
     return FRR_OK;
 }
 int frr_profile_set_period(frr_ctx *c, uint32_t period)

@@ -223,6 +223,8 @@ struct RasterArgs {
     uint4 *bins;                      // one 16-byte cull record {tri, zub, bbox.x, bbox.y} per (triangle, tile) pair, CSR by tile
     uint4 *bins2;                     // the same records in near-first order per tile (written by the tile kernel's pre-pass)
     uint32_t bin_cap;
+    uint32_t *tile_perm;              // segmented binning: [ntiles] the tile block b takes (option tile_order; built by the binning launch), or null: xcd_remap
+    uint32_t *tile_cost;              // segmented binning: [ntiles] each tile's records, for the order of a later pass (or null)
     uint8_t *color;
     float *depth;
     uint32_t *tri_id;

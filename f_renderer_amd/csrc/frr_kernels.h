@@ -864,6 +864,61 @@ __global__ __launch_bounds__(1024) void k_tile_scan(RasterArgs a, uint32_t ntile
 }
 
 // ---------------------------------------------------------------------------------------------
+// Heavy-first tile order (option tile_order).  The tile kernel's blocks are dealt round-robin to the 8 XCDs and
+// xcd_remap gives XCD x a contiguous run of tiles; in that order the heavy tiles that happen to sit late in a run start
+// last and set the end of the launch.  build_tile_perm keeps each XCD's run and sorts it by descending cost -- the
+// records each tile had in the latest pass over the same grid (RasterArgs::tile_cost) -- so that block x + 8k takes the
+// k-th heaviest tile of run x.  A counting sort on PERM_BKT cost buckets per run, by one workgroup of BIN_WG threads:
+// the order within a bucket is whatever the LDS atomics make it.  seed != 0 (tests): one run of all tiles, by a hash of
+// (seed, tile) -- a random order.  The result is a permutation of [0, ntiles) whatever the costs hold.
+// ---------------------------------------------------------------------------------------------
+constexpr int PERM_BKT = 256;
+constexpr int PERM_LDS_WORDS = 8 * PERM_BKT + 8 + BIN_WG / 64;   // bucket counters, per-run maxima, per-wave sums
+
+__device__ __forceinline__ uint32_t perm_hash(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ void build_tile_perm(const uint32_t *cost, uint32_t *perm, uint32_t ntiles, uint32_t seed, uint32_t *s /*[PERM_LDS_WORDS]*/)
+{
+    uint32_t *const s_cnt = s, *const s_max = s + 8 * PERM_BKT, *const s_w = s_max + 8;
+    const uint32_t nrun = seed ? 1u : 8u;
+    const uint32_t q = ntiles / 8u, r = ntiles % 8u, split = r * (q + 1u);   // run x: [start(x), start(x) + q + (x < r)), as xcd_remap
+    auto run_of = [&](uint32_t t) -> uint32_t { return nrun == 1u ? 0u : t < split ? t / (q + 1u) : r + (t - split) / q; };
+    auto start_of = [&](uint32_t x) -> uint32_t { return x < r ? x * (q + 1u) : split + (x - r) * q; };
+    auto cost_of = [&](uint32_t t) -> uint32_t { return seed ? perm_hash(seed ^ perm_hash(t)) : cost[t]; };
+    auto bucket_of = [&](uint32_t t, uint32_t x) -> uint32_t { // heaviest first: bucket 0 (any value in range would do)
+        const float scale = (float)PERM_BKT / ((float)s_max[x] + 1.0f);
+        return x * PERM_BKT + (PERM_BKT - 1) - min((uint32_t)((float)cost_of(t) * scale), (uint32_t)(PERM_BKT - 1));
+    };
+    for (uint32_t i = threadIdx.x; i < 8u * PERM_BKT + 8u; i += BIN_WG) s[i] = 0u;
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < ntiles; t += BIN_WG) atomicMax(&s_max[run_of(t)], cost_of(t));
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < ntiles; t += BIN_WG) atomicAdd(&s_cnt[bucket_of(t, run_of(t))], 1u);
+    __syncthreads();
+    // exclusive scan of the 8 * PERM_BKT counters, two per thread: the runs' ranges come out at their starts
+    static_assert(8 * PERM_BKT == 2 * BIN_WG, "two counters per thread");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t v0 = s_cnt[2 * threadIdx.x], v1 = s_cnt[2 * threadIdx.x + 1], sum = v0 + v1;
+    const uint32_t inc = wave_incl_scan_dpp(sum);
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t wbase = 0;
+    for (int k = 0; k < w; ++k) wbase += s_w[k];
+    s_cnt[2 * threadIdx.x] = wbase + inc - sum;
+    s_cnt[2 * threadIdx.x + 1] = wbase + inc - sum + v0;
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < ntiles; t += BIN_WG) {
+        const uint32_t x = run_of(t);
+        const uint32_t p = atomicAdd(&s_cnt[bucket_of(t, x)], 1u);       // position among all tiles, in [start(x), start(x + 1))
+        const uint32_t b = nrun == 1u ? p : x + 8u * (p - start_of(x));  // the block xcd_remap would have given position p
+        if (b < ntiles) perm[b] = t;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // K2' binning in ONE launch, without per-entry global atomics (default path): a segmented LDS
 // multi-split.  Workgroup g of G owns a contiguous chunk of the setup triangles and
 //   1. histograms the chunk over the tiles in LDS (ds_add);
@@ -879,20 +934,27 @@ __global__ __launch_bounds__(1024) void k_tile_scan(RasterArgs a, uint32_t ntile
 // ---------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(BIN_WG) void k_bin_seg(RasterArgs a, uint32_t ntiles, uint32_t *__restrict__ seg,
-                                                    uint32_t stage_cap, uint32_t fan_cap, const uint32_t *block_sums, uint32_t *block_prefix, uint32_t nblocks, int do_scan)
+                                                    uint32_t stage_cap, uint32_t fan_cap, const uint32_t *block_sums, uint32_t *block_prefix, uint32_t nblocks, int do_scan,
+                                                    uint32_t perm_seed)
 {
     const uint32_t first_bad = seq_first_bad(a.cnt);   // (tested once the histogram is zeroed: nothing is written before)
     extern __shared__ __attribute__((aligned(16))) uint32_t s_hist[]; // [ntiles], then the staging records
     uint4 *s_stage = reinterpret_cast<uint4 *>(s_hist + ((ntiles + 3u) & ~3u));
     __shared__ uint32_t s_w[2][BIN_WG / 64];
     __shared__ uint32_t s_base;
-    const uint32_t g = blockIdx.x, G = gridDim.x - (uint32_t)do_scan;
-    const bool scan_wg = do_scan && blockIdx.x == gridDim.x - 1;
-    if (!scan_wg) for (uint32_t t = threadIdx.x; t < ((ntiles + 3u) & ~3u); t += BIN_WG) s_hist[t] = 0u;   // (padded to four: bin_scan_relative)
+    const bool extra = do_scan || a.tile_perm;
+    const uint32_t g = blockIdx.x, G = gridDim.x - (uint32_t)extra;
+    const bool extra_wg = extra && blockIdx.x == gridDim.x - 1;
+    if (!extra_wg) for (uint32_t t = threadIdx.x; t < ((ntiles + 3u) & ~3u); t += BIN_WG) s_hist[t] = 0u;   // (padded to four: bin_scan_relative)
     if (seq_is_cancelled(first_bad, a.seq, a.epoch, false)) return;
-    // do_scan: the launch's LAST workgroup scans the geometry kernel's block sums instead (the tile kernel's resolve
-    // needs the prefix for triangle ids; here it costs no launch and sits on nobody's critical path)
-    if (scan_wg) { geom_scan(block_sums, block_prefix, nblocks, a.cnt, a.lane, a.gpar, fan_cap, a.geom_seq, a.epoch); return; }
+    // The launch's LAST workgroup (do_scan, or a pass that orders its tiles) scans the geometry kernel's block sums (the
+    // tile kernel's resolve needs the prefix for triangle ids) and builds the pass's tile order (build_tile_perm) instead
+    // of a chunk: here neither costs a launch or sits on anybody's critical path
+    if (extra_wg) {
+        if (do_scan) geom_scan(block_sums, block_prefix, nblocks, a.cnt, a.lane, a.gpar, fan_cap, a.geom_seq, a.epoch);
+        if (a.tile_perm) build_tile_perm(a.tile_cost, a.tile_perm, ntiles, perm_seed, s_hist);
+        return;
+    }
     if (g == 0 && threadIdx.x == 0) bin_bookkeeping(a.cnt, a.lane, a.bpar, a.frame_no);
     __syncthreads();
     // a workgroup's chunk: a range of geometry blocks (their dense entries) and a range of the used fan entries

@@ -96,7 +96,13 @@ struct TileCtx {
 __device__ __forceinline__ TileCtx tile_ctx(const RasterArgs &a)
 {
     TileCtx c;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    // which tile this block takes: the pass's heavy-first order if the binning launch built one (option tile_order), else
+    // xcd_remap.  Only that changes: everything keyed by tile (segment column, bins2 slot, cost, debug rows) uses c.ltile.
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    if (a.tile_perm) {
+        const uint32_t p = a.tile_perm[blockIdx.x];
+        if (p < gridDim.x) bid = (int)p;   // (always, for a permutation built for this grid: never an index out of range)
+    }
     // bid / tiles_x by multiplication (scalar unit): exact for bid, tiles_x < 2^16 (tiles_x_magic = 2^32 / tiles_x + 1; 0: divide)
     const int trow = a.tiles_x_magic ? (int)__builtin_amdgcn_readfirstlane((int)__umulhi((uint32_t)bid, a.tiles_x_magic)) : bid / a.tiles_x;
     const int tx = bid - trow * a.tiles_x;
@@ -622,6 +628,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
         __syncthreads();
         const uint32_t w0 = s_w4[0], w1 = s_w4[1], w2 = s_w4[2], w3 = s_w4[3];
         const uint32_t total = __builtin_amdgcn_readfirstlane((w0 + w1) + (w2 + w3)); // wave-uniform, and the compiler should know
+        if (threadIdx.x == 0 && a.tile_cost) a.tile_cost[c.ltile] = total;            // the cost a later pass orders this tile by
         if (total == 0u) { tile_fill_clear(a, c); return; }
         if (threadIdx.x < BIN_MAX_G) {
             s_segpre[threadIdx.x] = (w > 0 ? w0 : 0u) + (w > 1 ? w1 : 0u) + (w > 2 ? w2 : 0u) + inc - cn;
@@ -1008,11 +1015,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
         atomicAdd(d + 20, 1ull); // waves that ran the main loop
         if (a.dbg_tiles && w == 0) {
             // timeline of this workgroup: start / main loop / end on the 100 MHz clock, where it ran, how much it had to do
-            unsigned long long *tl = a.dbg_tiles + (size_t)blockIdx.x * 8;
+            unsigned long long *tl = a.dbg_tiles + (size_t)c.ltile * 8;   // (by tile; tl[7] carries the block)
             tl[0] = d_rt0; tl[1] = d_rt1; tl[2] = d_rt2; tl[3] = __builtin_amdgcn_s_memrealtime();
             tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32); // HW_ID, XCC_ID
             tl[5] = (unsigned long long)(c.end - c.beg) | ((unsigned long long)(uint32_t)c.tile << 32);
-            tl[6] = d_t[1] + d_t[3] + d_t[4] + d_t[5]; tl[7] = d_t[0];
+            tl[6] = d_t[1] + d_t[3] + d_t[4] + d_t[5]; tl[7] = d_t[0] | ((unsigned long long)blockIdx.x << 32);
         }
     }
 #endif

@@ -120,7 +120,7 @@ def _options_from_env():
     for var, name in (("FRR_RASTER_NW", "raster_nw"), ("FRR_RASTER_OCC", "raster_occ"), ("FRR_BIN_G", "bin_chunks"),
                       ("FRR_ENT_SLOT", "tile_slot_records"), ("FRR_BIN_CAP", "bin_capacity"), ("FRR_FAN_CAP", "fan_capacity"),
                       ("FRR_CLIP_QUEUE", "clip_queue"), ("FRR_OVERLAP", "overlap"), ("FRR_FRAMES_IN_FLIGHT", "frames_in_flight"),
-                      ("FRR_BOUND_IN_FLIGHT", "bound_targets_in_flight")):
+                      ("FRR_BOUND_IN_FLIGHT", "bound_targets_in_flight"), ("FRR_TILE_ORDER", "tile_order")):
         if e.get(var):
             o[name] = int(e[var])
     if e.get("FRR_CLEAR") == "eager":
@@ -157,6 +157,12 @@ class Renderer:
         self.last_warning = None
         for name, value in _options_from_env().items():
             self.set_option(name, value)
+
+    def tile_order_passes(self):
+        """Raster passes so far whose tile kernel took a built tile order (option tile_order; tests)."""
+        n = C.c_uint64()
+        self._check(self._lib.frr_tile_order_passes(self._ctx, C.byref(n)))
+        return int(n.value)
 
     def set_option(self, name, value):
         """Development / test switches of the library (include/frr.h: frr_set_option); none changes a result."""

@@ -315,7 +315,12 @@ int frr_event_elapsed_ms(frr_ctx *ctx, int a, int b, float *ms);
  *                             (k_geom_clip, one wavefront each over the whole chip) instead of by their block; 0: never;
  *                             -1 (default): when the counters last read back (frr_sync, frr_readback, frr_get_stats)
  *                             showed a block with more than 16 clipped inputs
- *   "clear_eager"             1: frr_clear runs its own kernel at once instead of riding on the next full-window draw */
+ *   "clear_eager"             1: frr_clear runs its own kernel at once instead of riding on the next full-window draw
+ *   "tile_order"              which workgroup of the tile kernel takes which tile (segmented binning): 0 (default) the fixed order
+ *                             by position; 1 heaviest first -- each XCD's run of neighbouring tiles by descending records in the
+ *                             latest pass over the same grid on the same workspace (the fixed order on a first pass, after a new
+ *                             window / partition / workgroup shape, on replays, and always above 4,096 tiles; measured no faster
+ *                             than 0); 2 a seeded random permutation (tests) */
 int frr_set_option(frr_ctx *ctx, const char *name, int64_t value);
 /* per-kernel accumulated device time (ms) and launch count since frr_profile_reset.  `mask`:
  * 0 = off, -1 = every kernel, else OR of (1 << index) with index in the order k_clear,
@@ -327,6 +332,8 @@ int frr_profile_enable(frr_ctx *ctx, int mask);
  * stream ~4 us, which matters when the whole frame is 150 us; frr_profile_get then reports the sampled
  * launches. */
 int frr_profile_set_period(frr_ctx *ctx, uint32_t period);
+/* raster passes since frr_create whose tile kernel took a built block -> tile order (option "tile_order" 1 or 2; tests) */
+int frr_tile_order_passes(frr_ctx *ctx, uint64_t *passes);
 int frr_profile_reset(frr_ctx *ctx);
 int frr_profile_get(frr_ctx *ctx, const char *kernel, float *total_ms, uint32_t *launches);
 

@@ -63,4 +63,5 @@ print("max concurrent workgroups per CU: min %d  median %d  max %d; workgroups p
     min(mx), int(np.median(mx)), max(mx), min(np.bincount(np.unique(cu, return_inverse=True)[1])), max(np.bincount(np.unique(cu, return_inverse=True)[1]))))
 late = start > 5.0
 print(f"workgroups starting after 5 us: {int(late.sum())}; their mean duration {np.mean((end - start)[late]) if late.any() else 0:.1f} vs early {np.mean((end - start)[~late]):.1f} us")
+print(f"  mean records: {np.mean(nent[late]) if late.any() else 0:.0f} late vs {np.mean(nent[~late]):.0f} early")
 r.stats()
