@@ -58,7 +58,7 @@ constexpr int kSpanShapes[6][2] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIG
 struct UserShader {
     int nf = 0, K = 0;
     std::vector<char> code;
-    std::string geom, clip, sweep, span[2][6];   // lowered kernel names ([count fragments][shape]; sweep: the brute-force tile kernel)
+    std::string geom, clip, sweep, entries, span[2][6];   // lowered kernel names ([count fragments][shape]; sweep: the brute-force tile kernel)
 };
 std::mutex g_shader_mu;
 std::vector<UserShader *> g_shaders;      // id = FRR_SHADER_USER_BASE + index; never shrinks
@@ -93,7 +93,7 @@ void release_stream(int device, hipStream_t st)
 
 struct UserModule {
     hipModule_t mod = nullptr;
-    hipFunction_t geom = nullptr, clip = nullptr, sweep = nullptr, span[2][6] = {};
+    hipFunction_t geom = nullptr, clip = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {};
 };
 
 // One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
@@ -534,6 +534,7 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
     HIP_TRY(c, hipModuleGetFunction(&m.geom, m.mod, us->geom.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.clip, m.mod, us->clip.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.sweep, m.mod, us->sweep.c_str()));
+    HIP_TRY(c, hipModuleGetFunction(&m.entries, m.mod, us->entries.c_str()));
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) HIP_TRY(c, hipModuleGetFunction(&m.span[cnt][sh], m.mod, us->span[cnt][sh].c_str()));
     *out = &(c->user_modules[id] = m);
@@ -954,7 +955,27 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     // waits too, but leaves the waits to the write they were asked for)
     hipStream_t ts;
     if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
-    if (grid && um) {
+    // x0 < 0: the depth stride x1 is smaller than the window's width and pixels of neighbouring rows share depth entries,
+    // which only a resolve per ENTRY reproduces (k_raster_entries).  On a partitioned ctx the pixels of an entry belong to
+    // different ranks, each with a depth buffer of its own: there the tile kernels run as for any window.
+    const bool shared_entries = ww > (int64_t)x1 && f.world <= 1;
+    if (grid && shared_entries) {
+        ProfScope p(c, KID_RASTER, ts);
+        const unsigned eg = (unsigned)((((wh - 1) * (int64_t)x1 + ww) + 255) / 256);
+        if (um) {
+            RasterArgs ra = a; DevUniforms d = cmd.duni;
+            void *args[] = {&ra, &d};
+            (void)hipModuleLaunchKernel(um->entries, eg, 1, 1, 256, 1, 1, 0, ts, args, nullptr);
+        } else {
+            switch (ps_id) {
+            case FRR_PS_DEPTH: hipLaunchKernelGGL((k_raster_entries<0, FRR_PS_DEPTH>), dim3(eg), dim3(256), 0, ts, a, cmd.duni); break;
+            case FRR_PS_FLAT: hipLaunchKernelGGL((k_raster_entries<0, FRR_PS_FLAT>), dim3(eg), dim3(256), 0, ts, a, cmd.duni); break;
+            case FRR_PS_COLOR: hipLaunchKernelGGL((k_raster_entries<3, FRR_PS_COLOR>), dim3(eg), dim3(256), 0, ts, a, cmd.duni); break;
+            case FRR_PS_PHONG: hipLaunchKernelGGL((k_raster_entries<8, FRR_PS_PHONG>), dim3(eg), dim3(256), 0, ts, a, cmd.duni); break;
+            case FRR_PS_BLINN: hipLaunchKernelGGL((k_raster_entries<8, FRR_PS_BLINN>), dim3(eg), dim3(256), 0, ts, a, cmd.duni); break;
+            }
+        }
+    } else if (grid && um) {
         ProfScope p(c, KID_RASTER, ts);
         int shi = 4;
         for (int k = 0; k < 6; ++k) if (kSpanShapes[k][0] == sh.nw && kSpanShapes[k][1] == sh.occ) shi = k;
@@ -1465,6 +1486,8 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     std::vector<std::string> exprs = {"frr::k_geom_single<" + U + ">", "frr::k_geom_clip<" + U + ">"};
     const std::string sweep_expr = "frr::k_raster<" + Ks + ", " + U + ">";   // the brute-force tile kernel (option raster_sweep)
     (void)hiprtcAddNameExpression(prog, sweep_expr.c_str());
+    const std::string entries_expr = "frr::k_raster_entries<" + Ks + ", " + U + ">";   // windows whose rows share depth entries (x0 < 0)
+    (void)hiprtcAddNameExpression(prog, entries_expr.c_str());
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh)
             exprs.push_back("frr::k_raster_span<" + Ks + ", " + U + ", " + (cnt ? "true" : "false") + ", " + std::to_string(kSpanShapes[sh][0]) + ", " + std::to_string(kSpanShapes[sh][1]) + ">");
@@ -1482,7 +1505,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     }
     bool ok = true;
     auto lowered = [&](const std::string &e) { const char *n = nullptr; ok = ok && hiprtcGetLoweredName(prog, e.c_str(), &n) == HIPRTC_SUCCESS && n; return std::string(n ? n : ""); };
-    us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->sweep = lowered(sweep_expr);
+    us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
     size_t cs = 0;

@@ -385,6 +385,80 @@ __global__ __launch_bounds__(256) void k_raster(RasterArgs a, DevUniforms u)
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_raster_entries: the exact path for windows whose rows SHARE depth entries.  With x0 < 0 the depth stride x1 is smaller
+// than the window's width, so the window pixels (ex + k x1, ey - k), k = 0, 1, ..., all address depth entry ey * x1 + ex
+// (renderer.rs:362).  The reference runs their fragments through that entry in submission order -- triangle by triangle,
+// and within a triangle row by row (:322-324), i.e. larger k first -- and a pixel's colour is that of ITS last fragment
+// that passed.  No per-pixel argmax gives that, so one thread takes one depth ENTRY and replays the reference's loop for it:
+// every triangle of the pass in emission order, every pixel of the entry, the sequential depth test (NaN rule included).
+// Entries are independent of each other.  Brute force (entries x triangles): such windows are rare and small.
+// ---------------------------------------------------------------------------------------------
+template <int K, int PS>
+__global__ __launch_bounds__(256) void k_raster_entries(RasterArgs a, DevUniforms u)
+{
+    if (seq_cancelled(a.cnt, a.seq, a.epoch, true)) return;
+    const GeomTab *g = gtab_of(a);
+    const uint32_t n = g->n_emit, tri_base = g->tri_base;
+    const long long nent = (long long)(a.win_h - 1) * a.dstride + a.win_w;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nent) return;
+    const int ex = (int)(e % a.dstride), ey = (int)(e / a.dstride);
+    const int kmax = (a.win_w - 1 - ex) / a.dstride;
+    float depth = a.depth[e];
+    uint32_t id = 0u, n_cov = 0u, n_nan = 0u;
+    bool wrote = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t t = slot_of_emission(a, i);
+        const RasterRec *__restrict__ r = a.recs + t;
+        const float s0x = r->s[0], s0y = r->s[1], s1x = r->s[2], s1y = r->s[3], s2x = r->s[4], s2y = r->s[5];
+        const int p0x = f32_as_i32(s0x + 0.5f), p0y = f32_as_i32(s0y + 0.5f), p1x = f32_as_i32(s1x + 0.5f), p1y = f32_as_i32(s1y + 0.5f);
+        const int p2x = f32_as_i32(s2x + 0.5f), p2y = f32_as_i32(s2y + 0.5f);
+        const int bx0 = clampi(min(p0x, min(p1x, p2x)), a.x0, a.x1), bx1 = clampi(max(p0x, max(p1x, p2x)), a.x0, a.x1);
+        const int by0 = clampi(min(p0y, min(p1y, p2y)), a.y0, a.y1), by1 = clampi(max(p0y, max(p1y, p2y)), a.y0, a.y1);
+        if (bx1 <= bx0 || by1 <= by0) continue;
+        const uint32_t A01 = 0u - (uint32_t)(p1y - p0y), B01 = (uint32_t)(p1x - p0x);
+        const uint32_t A12 = 0u - (uint32_t)(p2y - p1y), B12 = (uint32_t)(p2x - p1x);
+        const uint32_t A20 = 0u - (uint32_t)(p0y - p2y), B20 = (uint32_t)(p0x - p2x);
+        const uint32_t fl = r->flags;
+        const int thr01 = (fl & 2u) ? 0 : -1, thr12 = (fl & 4u) ? 0 : -1, thr20 = (fl & 8u) ? 0 : -1;
+        const float r0 = r->rhw[0], r1 = r->rhw[1], r2 = r->rhw[2];
+        for (int k = kmax; k >= 0; --k) {
+            const int lx = ex + k * a.dstride, ly = ey - k;
+            if (ly < 0 || ly >= a.win_h) continue;
+            const int cx = a.x0 + lx, cy = a.y0 + ly;
+            if (cx < bx0 || cx >= bx1 || cy < by0 || cy >= by1) continue;
+            const int E01 = (int)(A01 * (uint32_t)(cx - p0x) + B01 * (uint32_t)(cy - p0y));
+            const int E12 = (int)(A12 * (uint32_t)(cx - p1x) + B12 * (uint32_t)(cy - p1y));
+            const int E20 = (int)(A20 * (uint32_t)(cx - p2x) + B20 * (uint32_t)(cy - p2y));
+            if (!((E01 > thr01) & (E12 > thr12) & (E20 > thr20))) continue;
+            ++n_cov;
+            const Frag f = frag_eval(s0x, s0y, s1x, s1y, s2x, s2y, r0, r1, r2, cx, cy);
+            if (!f.valid) continue;                                             // :352-354
+            if (f.rhw != f.rhw) ++n_nan;
+            if (f.rhw < depth) continue;                                        // :363-365
+            depth = f.rhw; id = tri_base + i; wrote = true;                     // :366
+            if constexpr (PS != FRR_PS_DEPTH) {
+                const float w = recip_exact(f.rhw != 0.0f ? f.rhw : 1.0f);      // :368
+                const float c0 = r0 * f.a * w, c1 = r1 * f.b * w, c2 = r2 * f.c * w;
+                float in[K > 0 ? K : 1];
+                if constexpr (K > 0) {
+                    const float *v = a.vary + (size_t)t * (3 * K);
+#pragma unroll
+                    for (int q = 0; q < K; ++q) in[q] = v[q] * c0 + v[K + q] * c1 + v[2 * K + q] * c2;
+                }
+                float col[4];
+                run_ps<PS>(u, in, col, nullptr);
+                reinterpret_cast<uint32_t *>(a.color)[(size_t)ly * a.cstride + lx] =
+                    quantize_u8(col[0]) | (quantize_u8(col[1]) << 8) | (quantize_u8(col[2]) << 16) | (quantize_u8(col[3]) << 24);
+            }
+        }
+    }
+    if (wrote) { a.depth[e] = depth; a.tri_id[e] = id; }
+    if (n_cov) atomicAdd(&a.cnt->lane[a.lane].gtab[a.gpar].frag_covered, (unsigned long long)n_cov);
+    if (n_nan) atomicAdd(&a.cnt->lane[a.lane].gtab[a.gpar].frag_nan, (unsigned long long)n_nan);
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_raster_span
 // ---------------------------------------------------------------------------------------------
 constexpr int SPAN_SAFE = 8191; // |spi| and window coordinates up to this keep every edge value < 2^30 (and twice an edge delta in 16 bits)

@@ -188,7 +188,9 @@ typedef enum frr_xfer_kind { FRR_XFER_SEND = 0, FRR_XFER_RECV = 1, FRR_XFER_COPY
 typedef struct frr_xfer {
     int32_t kind;     /* frr_xfer_kind */
     int32_t peer;     /* SEND: root; RECV: the sending rank; COPY: root itself */
-    uint64_t offset;  /* first element, in the rank's render target AND in the final image (same layout) */
+    uint64_t offset;  /* first element, in the rank's render target AND in the final image (same layout), counted from the
+                         WINDOW's first row: row 0 of the plane is pixel row y0 of the screen (a window is addressed locally,
+                         renderer.rs:323; frr_raster below), so the plan depends on y1 - y0 only */
     uint64_t count;   /* elements */
 } frr_xfer;
 int frr_exchange_plan(int32_t y0, int32_t y1, uint32_t row_elems, int rank, int world, int blocked, int root, frr_xfer *ops, int cap);
@@ -242,7 +244,11 @@ int frr_geometry(frr_ctx *ctx, int mesh, uint64_t *ntris_setup);
 /* Loop B (phong.rs:361-381): Renderer::rasterization of the triangles of the last frr_geometry
  * with width_range=(x0,x1), height_range=(y0,y1) (renderer.rs:270-271).  As in the reference the
  * window is addressed locally: pixel (cx,cy) lands at colour (cx-x0, cy-y0) with row stride
- * `width` and at depth index (cy-y0)*x1 + (cx-x0) (renderer.rs:323,326,362,381). */
+ * `width` and at depth index (cy-y0)*x1 + (cx-x0) (renderer.rs:323,326,362,381).
+ * With x0 < 0 the stride x1 is smaller than the window's width, so pixels of neighbouring rows share one depth entry; the
+ * reference runs their fragments through it in submission order, and so does this library (one thread per entry instead
+ * of the tile kernels: exact, and slow for large windows).  On a partitioned ctx the pixels of an entry may belong to
+ * different ranks: the ranks' images of such a window do not stitch to the reference's. */
 int frr_raster(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
 /* frr_geometry + frr_raster.  On a partitioned ctx (frr_set_partition, world > 1) the setup list frr_draw builds
  * keeps only the triangles that touch this rank's tile rows of THIS window: a later frr_raster with another

@@ -318,6 +318,26 @@ def rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tid, fb_width):
         a, b, c = a * inv, b * inv, c * inv
         rhw = (v[0]["rhw"] * a + v[1]["rhw"] * b) + v[2]["rhw"] * c
         idx = (cys - hr[0]).astype(np.int64) * wr[1] + (cxs - wr[0])
+        if wr[1] < wr[1] - wr[0]:
+            # x0 < 0: the depth stride is smaller than the window's width and two fragments of ONE triangle may share a depth
+            # entry (renderer.rs:362), so the test of the later one sees the earlier one's store: fragment by fragment, in
+            # the reference's raster order (rows, then columns, :322-324)
+            rgba = None
+            if ps_id != PS_DEPTH:
+                w = F(1.0) / np.where(rhw != 0.0, rhw, F(1.0))
+                c0, c1, c2 = v[0]["rhw"] * a * w, v[1]["rhw"] * b * w, v[2]["rhw"] * c * w
+                ctx = (v[0]["ctx"][None, :] * c0[:, None] + v[1]["ctx"][None, :] * c1[:, None]) + v[2]["ctx"][None, :] * c2[:, None] \
+                    if K else np.zeros((idx.size, 0), F)
+                rgba = quantize(pixel_shader(ps_id, u, ctx.astype(F)))
+            flat = color.reshape(-1, 4)
+            for j in range(idx.size):
+                if not ok[j] or rhw[j] < depth[idx[j]]:
+                    continue
+                depth[idx[j]] = rhw[j]
+                tri_id[idx[j]] = tid
+                if rgba is not None:
+                    flat[int(cys[j] - hr[0]) * fb_width + int(cxs[j] - wr[0])] = rgba[j]
+            return ncov
         passed = ok & ~(rhw < depth[idx])
         idx, rhw, a, b, c = idx[passed], rhw[passed], a[passed], b[passed], c[passed]
         depth[idx] = rhw
