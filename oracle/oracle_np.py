@@ -46,17 +46,28 @@ def total_key(x):
     return i
 
 
+def f32_max(a, b):
+    """Rust's f32::max, elementwise: a NaN operand yields the OTHER operand (NaN only when both are), as frr_oracle.c's
+    f32_max and frr_exact.h's f32_max_ref spell it out.  np.maximum and Python's max() do not: np.maximum returns the NaN,
+    max(nan, 0) returns whichever came first."""
+    a, b = np.asarray(a, F), np.asarray(b, F)
+    with np.errstate(invalid="ignore"):
+        r = np.where(a != a, b, np.where(b != b, a, np.where(a > b, a, b)))
+    return r.astype(F) if r.ndim else F(r)
+
+
 class Uniforms:
-    def __init__(self, model=None, view=None, proj=None, view_pos=(0, 0, 0), flat_color=(1, 1, 1, 1), tex=None):
+    def __init__(self, model=None, view=None, proj=None, view_pos=(0, 0, 0), flat_color=(1, 1, 1, 1), tex=None,
+                 light_pos=(1.2, 1.0, 2.0), light_color=(1.0, 1.0, 1.0), ambient=0.1, specular=0.5):
         eye4 = np.eye(4, dtype=F).reshape(-1)
         self.model = eye4 if model is None else np.asarray(model, F).reshape(-1)
         self.view = eye4 if view is None else np.asarray(view, F).reshape(-1)
         self.proj = eye4 if proj is None else np.asarray(proj, F).reshape(-1)
         self.view_pos = np.asarray(view_pos, F)
-        self.light_pos = np.array([1.2, 1.0, 2.0], F)          # phong.rs:129
-        self.light_color = np.array([1.0, 1.0, 1.0], F)        # phong.rs:128
-        self.ambient = F(0.1)                                  # phong.rs:131
-        self.specular = F(0.5)                                 # phong.rs:132
+        self.light_pos = np.asarray(light_pos, F)              # phong.rs:129 (the defaults are the reference's constants)
+        self.light_color = np.asarray(light_color, F)          # phong.rs:128
+        self.ambient = F(ambient)                              # phong.rs:131
+        self.specular = F(specular)                            # phong.rs:132
         self.flat_color = np.asarray(flat_color, F)
         self.tex = None if tex is None else np.ascontiguousarray(tex, np.uint8)
 
@@ -124,7 +135,7 @@ def vertex_shader(vs_id, u, vin):
     else:                                                      # Gouraud: per-vertex Lambert
         n = normalize3(vin[5:8])
         l = normalize3(u.light_pos - world[:3])
-        diff = max(dot3(n, l), F(0.0))
+        diff = f32_max(dot3(n, l), F(0.0))                     # f32::max as phong.rs:138 uses it (the Gouraud pair itself is ours)
         ctx = (u.light_color * u.ambient + F(diff) * u.light_color).astype(F)
     return mat_vec(mvp, p).astype(F), ctx
 
@@ -152,9 +163,11 @@ def sample_2d(tex, uv):                                        # renderer.rs:516
     return ((c11 + c12) + c21) + c22
 
 
-def pixel_shader(ps_id, u, ctx):
+def pixel_shader(ps_id, u, ctx, debug=None):
     """ctx [n,K] -> rgba [n,4] (float32).  ps_id may be a callable (u, ctx) -> rgba: a closure written for one test, the way
-    the reference takes its pixel shader (renderer.rs:273,283)."""
+    the reference takes its pixel shader (renderer.rs:273,283).  debug: a dict that receives the lighting intermediates of
+    PS_PHONG / PS_BLINN, one row per pixel (normal, light_dir, view_dir, spec_vec / spec_dir: the reflection or the half vector before and
+    after its normalisation, diff, spec: before powi, tex, light: the sum that multiplies the texel)."""
     n = ctx.shape[0]
     if callable(ps_id):
         return np.asarray(ps_id(u, ctx), F)
@@ -166,21 +179,29 @@ def pixel_shader(ps_id, u, ctx):
     ambient = u.light_color * u.ambient                         # phong.rs:134
     nrm = normalize3(normal)
     l = normalize3(u.light_pos - wpos)
-    diff = np.maximum(dot3(nrm, l), F(0.0))
+    diff = f32_max(dot3(nrm, l), F(0.0))                        # phong.rs:138: f32::max, a NaN dot gives 0.0
     diffuse = diff[:, None] * u.light_color
     v = normalize3(u.view_pos - wpos)
     if ps_id == PS_PHONG:
         L = -l
         t = F(2.0) * dot3(L, nrm)                               # vector_util.rs:6
-        r = normalize3(t[:, None] * nrm - L)
-        s = np.maximum(dot3(v, r), F(0.0))
+        rv = t[:, None] * nrm - L
+        r = normalize3(rv)
+        s = f32_max(dot3(v, r), F(0.0))                         # phong.rs:143: f32::max again
     else:
-        s = np.maximum(dot3(nrm, normalize3(l + v)), F(0.0))
+        rv = l + v
+        r = normalize3(rv)
+        s = f32_max(dot3(nrm, r), F(0.0))                       # Blinn's half vector through the same max as phong.rs:143
+    if debug is not None:
+        debug.update(normal=nrm, light_dir=l, view_dir=v, spec_vec=rv, spec_dir=r, diff=diff, spec=s)
     for _ in range(5):                                          # powi(32)
         s = s * s
     specular = (u.specular * s)[:, None] * u.light_color
     tex = sample_2d(u.tex, uv)
-    rgb = tex[:, :3] * ((ambient + diffuse) + specular)
+    light = (ambient + diffuse) + specular
+    if debug is not None:
+        debug.update(tex=tex, light=light)
+    rgb = tex[:, :3] * light
     return np.concatenate([rgb, (tex[:, 3] * F(1.0))[:, None]], axis=1).astype(F)
 
 
@@ -279,7 +300,9 @@ def _clamp(v, lo, hi):
     return lo if v < lo else (hi if v > hi else v)
 
 
-def rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tid, fb_width):
+def rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tid, fb_width, debug=None):
+    """debug: a dict name -> [len(depth), ...] float32 array; the fragments that pass the z-test leave their interpolated
+    `ctx` and the pixel shader's intermediates at their depth index (full-frame windows, x0 >= 0)."""
     K = tri[0]["ctx"].shape[0]
     xs = [v["spi"][0] for v in tri]
     ys = [v["spi"][1] for v in tri]
@@ -347,15 +370,22 @@ def rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tid, fb_width):
             c0, c1, c2 = v[0]["rhw"] * a * w, v[1]["rhw"] * b * w, v[2]["rhw"] * c * w
             ctx = (v[0]["ctx"][None, :] * c0[:, None] + v[1]["ctx"][None, :] * c1[:, None]) + v[2]["ctx"][None, :] * c2[:, None] \
                 if K else np.zeros((idx.size, 0), F)
-            rgba = quantize(pixel_shader(ps_id, u, ctx.astype(F)))
+            dbg = None if debug is None else {}
+            rgba = quantize(pixel_shader(ps_id, u, ctx.astype(F), dbg))
+            if debug is not None:
+                for name, val in dict(dbg, ctx=ctx.astype(F)).items():
+                    val = np.asarray(val, F)
+                    if name not in debug:
+                        debug[name] = np.full((depth.size,) + val.shape[1:], np.nan, F)
+                    debug[name][idx] = val
             ix = (cxs - wr[0])[passed]
             iy = (cys - hr[0])[passed]
             color.reshape(-1, 4)[iy.astype(np.int64) * fb_width + ix] = rgba
     return ncov
 
 
-def draw(width, height, vs_inputs, vs_id, ps_id, u, color, depth, tri_id, window=None, tri_id_base=0):
-    """Loops A and B of phong.rs:319-381.  Returns (n_setup, covered fragments)."""
+def draw(width, height, vs_inputs, vs_id, ps_id, u, color, depth, tri_id, window=None, tri_id_base=0, debug=None):
+    """Loops A and B of phong.rs:319-381.  Returns (setup list, covered fragments).  debug: see rasterization."""
     nf = VS_NF[vs_id]
     vin = np.asarray(vs_inputs, F).reshape(-1, 3, nf)
     wr, hr = ((0, width), (0, height)) if window is None else ((window[0], window[1]), (window[2], window[3]))
@@ -364,5 +394,5 @@ def draw(width, height, vs_inputs, vs_id, ps_id, u, color, depth, tri_id, window
         setup.extend(geometry_processing(width, height, vin[t], vs_id, u))
     cov = 0
     for i, tri in enumerate(setup):
-        cov += rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tri_id_base + i, width)
+        cov += rasterization(wr, hr, tri, ps_id, u, color, depth, tri_id, tri_id_base + i, width, debug)
     return setup, cov
