@@ -234,7 +234,9 @@ int frr_vs_num_varyings(int vs_id);
  * work is deferred: the next full-framebuffer frr_raster / frr_draw performs the clear inside its tile
  * kernel; every other call that can observe the targets or the statistics (frr_readback, frr_sync,
  * frr_get_stats, frr_target_ptrs, frr_bind_targets, a sub-window raster) settles it first, so the
- * observable behaviour is that of an immediate clear.  (Option clear_eager makes it immediate.) */
+ * observable behaviour is that of an immediate clear.  (Option clear_eager makes it immediate.)
+ * `depth` may be any f32, NaN included: a fragment is rejected only where `rhw < depth` holds (renderer.rs:363), so a
+ * NaN lets the first fragment of every pixel pass whatever its rhw, and stays where no fragment lands. */
 int frr_clear(frr_ctx *ctx, const uint8_t rgba[4], float depth);
 
 /* Loop A (phong.rs:321-331): Renderer::geometry_processing over every input triangle of `mesh`,
