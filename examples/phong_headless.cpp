@@ -5,7 +5,8 @@
 //   phong_headless <mesh.f32> <ntris> <tex.rgba> <tex_size> <W> <H> <out.rgba> [<out.ppm>]
 //       mesh.f32: ntris x 3 x 8 float32 (pos3, uv2, normal3 = VSInput, phong.rs:49-54)
 //   phong_headless --assets <model.obj> <diffuse.tga> <W> <H> <out.rgba> [<out.ppm>]
-//       the reference's own asset formats: Model::new (obj_loader.rs:15-97) + init_vertex_input (phong.rs:187-201)
+//       the reference's own asset formats: Model::new (obj_loader.rs:15-97), uploaded as an indexed mesh (the expansion of
+//       init_vertex_input, phong.rs:187-201, is the GPU's gather)
 //       and FrameBuffer::load_file (renderer.rs:427-471, BGRA storage)
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
 //       loaders only (no GPU): what the two loaders produce, for the CPU-side check against the Python mirror
@@ -50,9 +51,10 @@ int main(int argc, char **argv)
     const char *out_rgba = argv[a0 + 2], *out_ppm = argc > a0 + 3 ? argv[a0 + 3] : nullptr;
     try {
         std::vector<std::array<frr::VSInput, 3>> vin;
+        frr::Model::Indexed indexed;                                          // --assets: the Model as it is, not expanded
         frr::FrameBuffer diffuse(1, 1);
         if (assets) {
-            vin = frr::Model(argv[2]).vertex_inputs();                        // phong.rs:166, 187-201
+            indexed = frr::Model(argv[2]).indexed_inputs();                   // phong.rs:166; :187-201 happens on the GPU
             diffuse = frr::FrameBuffer::load_file(argv[3]);                   // phong.rs:167
         } else {
             const uint64_t ntris = std::strtoull(argv[2], nullptr, 10);
@@ -79,7 +81,8 @@ int main(int argc, char **argv)
         renderer.uniforms.texture_slot = 0;                                                     // PSUniform.place
         renderer.set_uniforms();
 
-        frr::Mesh mesh = renderer.upload_mesh(vin, FRR_VS_PHONG);
+        frr::Mesh mesh = assets ? renderer.upload_mesh_indexed(indexed, FRR_VS_PHONG) : renderer.upload_mesh(vin, FRR_VS_PHONG);
+        if (assets) std::printf("indexed: nverts=%zu ntris=%zu\n", indexed.vertices.size(), indexed.faces.size());
         frr::FrameBuffer frame_buffer = frr::FrameBuffer::create(W, H);                         // phong.rs:207
 
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317

@@ -118,6 +118,8 @@ SIGNATURES = {
     "frr_target_ptrs": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
     "frr_mesh_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
+    "frr_mesh_upload_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
+    "frr_mesh_bind_device_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_free": (C.c_int, [C.c_void_p, C.c_int]),
     "frr_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "frr_set_uniforms": (C.c_int, [C.c_void_p, _P(Uniforms)]),

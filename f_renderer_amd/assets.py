@@ -87,6 +87,22 @@ class Model:
                 out[i, j, 5:8] = self.normal(i, j)
         return out
 
+    def indexed_inputs(self):
+        """The same mesh without the expansion: (vertices float32 [V, 8], faces uint32 [F, 3]) for
+        Renderer.upload_mesh_indexed.  One vertex record per distinct (v, vt, vn) triple of the faces, in first-use order;
+        `vertices[faces].reshape(F, 3, 8)` equals `vertex_inputs()` bit for bit (normals normalised as `normal()` does)."""
+        seen, records = {}, []
+        faces = np.zeros((self.faces_len(), 3), np.uint32)
+        for i in range(self.faces_len()):
+            for j in range(3):
+                key = self.faces[i][j]
+                if key not in seen:
+                    seen[key] = len(records)
+                    records.append(np.concatenate([self.vert(i, j), self.uv_at(i, j), self.normal(i, j)]).astype(F))
+                faces[i, j] = seen[key]
+        vertices = np.array(records, F).reshape(len(records), 8)
+        return vertices, faces
+
 
 def texture_from_image(pixels):
     """renderer.rs:435-464: uint8 [h,w,3] (Rgb8) or [h,w,4] (Rgba8), top row first -> FrameBuffer

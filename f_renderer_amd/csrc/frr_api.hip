@@ -41,8 +41,10 @@ const char *const kKernelNames[KID_COUNT] = {"k_clear", "k_geom", "k_geom_scan",
                                              "k_raster", "k_bin_seg"};
 
 struct Mesh {
-    const float *dev = nullptr;
-    bool owned = false, used = false;
+    const float *dev = nullptr;    // [ntris][3][NF], or with idx: the vertex array [nverts][NF]
+    const uint32_t *idx = nullptr; // indexed mesh (frr_mesh_upload_indexed): [ntris][3] vertex numbers, all < nverts when registered
+    uint64_t nverts = 0;
+    bool owned = false, used = false;   // owned: dev AND idx are the library's allocations (a host upload); else both are the caller's
     uint64_t ntris = 0;
     int vs = 0;
     uint64_t gen = 0;   // which registration of the ctx this is (DrawSig: a later mesh may live at a freed one's address)
@@ -58,7 +60,7 @@ constexpr int kSpanShapes[6][2] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIG
 struct UserShader {
     int nf = 0, K = 0;
     std::vector<char> code;
-    std::string geom, clip, sweep, entries, span[2][6];   // lowered kernel names ([count fragments][shape]; sweep: the brute-force tile kernel)
+    std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel)
 };
 std::mutex g_shader_mu;
 std::vector<UserShader *> g_shaders;      // id = FRR_SHADER_USER_BASE + index; never shrinks
@@ -93,7 +95,7 @@ void release_stream(int device, hipStream_t st)
 
 struct UserModule {
     hipModule_t mod = nullptr;
-    hipFunction_t geom = nullptr, clip = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {};
+    hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {};
 };
 
 // One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
@@ -190,6 +192,8 @@ struct Cmd {
 // Everything the geometry pass reads can change what it emits: the mesh (its registration, and for a device-bound one the
 // frr_sync calls since -- the caller may rewrite it in place then), the uniforms (a user VS may read any field, texture
 // pointers and sizes included) and the texture contents (frr_texture_upload count).
+// (An indexed mesh needs no field of its own: its index list and vertex count belong to its registration, mesh_gen, and
+// binding it again after a rewrite is a new registration.)
 struct DrawSig {
     const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
     int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset;
@@ -533,6 +537,8 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
     HIP_TRY(c, hipModuleLoadData(&m.mod, us->code.data()));
     HIP_TRY(c, hipModuleGetFunction(&m.geom, m.mod, us->geom.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.clip, m.mod, us->clip.c_str()));
+    HIP_TRY(c, hipModuleGetFunction(&m.geom_idx, m.mod, us->geom_idx.c_str()));
+    HIP_TRY(c, hipModuleGetFunction(&m.clip_idx, m.mod, us->clip_idx.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.sweep, m.mod, us->sweep.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.entries, m.mod, us->entries.c_str()));
     for (int cnt = 0; cnt < 2; ++cnt)
@@ -543,12 +549,20 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
 
 constexpr uint32_t kClipGrid = 2048;      // workgroups of k_geom_clip (four wavefronts each, one triangle per wavefront and step)
 
-template <int VS> void launch_geometry(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
+// (IDX, an indexed mesh, is a template flag and not a null test in the kernels: the instantiations for expanded meshes keep
+// their code)
+template <int VS, bool IDX> void launch_geometry_as(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
 {
     hipStream_t st = gstream_of(c);
     ProfScope p(c, KID_GEOM, st);
-    hipLaunchKernelGGL(k_geom_single<VS>, dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
-    if (g.use_clipq) hipLaunchKernelGGL(k_geom_clip<VS>, dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
+    hipLaunchKernelGGL((k_geom_single<VS, IDX>), dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
+    if (g.use_clipq) hipLaunchKernelGGL((k_geom_clip<VS, IDX>), dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
+}
+
+template <int VS> void launch_geometry(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
+{
+    if (g.idx) launch_geometry_as<VS, true>(c, g, nblocks, du);
+    else launch_geometry_as<VS, false>(c, g, nblocks, du);
 }
 
 // the geometry kernel for the VS of the mesh
@@ -559,8 +573,8 @@ void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const
         ProfScope p(c, KID_GEOM, st);
         DevUniforms d = du;
         void *args[] = {&g, &d};
-        (void)hipModuleLaunchKernel(um->geom, nblocks, 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
-        if (g.use_clipq) (void)hipModuleLaunchKernel(um->clip, std::min<uint32_t>(kClipGrid, nblocks * 4u), 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
+        (void)hipModuleLaunchKernel(g.idx ? um->geom_idx : um->geom, nblocks, 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
+        if (g.use_clipq) (void)hipModuleLaunchKernel(g.idx ? um->clip_idx : um->clip, std::min<uint32_t>(kClipGrid, nblocks * 4u), 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
         return;
     }
     switch (vs) {
@@ -756,7 +770,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if ((rc = gstream_join(c)) != FRR_OK) return rc;
     if ((rc = gstream_wait_readers(c, S.reader)) != FRR_OK) return rc;
     GeomArgs g;
-    g.in = m.dev; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
+    g.in = m.dev; g.idx = m.idx; g.nverts = (uint32_t)m.nverts; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
     g.fan_cap = (uint32_t)fan_cap;
     g.seq = cmd.seq; g.epoch = c->epoch; g.frame_no = f.frame_no;
     g.part_rank = f.rank; g.part_world = cmd.filter ? f.world : 1; g.part_y0 = cmd.fy0; g.part_y1 = cmd.fy1;
@@ -1217,7 +1231,7 @@ void frr_destroy(frr_ctx *c)
     (void)hipSetDevice(c->device);
     for (hipStream_t st : {c->gstream, c->tstream[1].st, c->tstream[0].st, c->stream}) if (st) (void)hipStreamSynchronize(st);
     prof_collect(c);
-    for (auto &m : c->meshes) if (m.used && m.owned) (void)hipFree((void *)m.dev);
+    for (auto &m : c->meshes) if (m.used && m.owned) { (void)hipFree((void *)m.dev); if (m.idx) (void)hipFree((void *)m.idx); }
     for (auto &t : c->tex) if (t.dev) (void)hipFree(t.dev);
     if (c->host_bad) (void)hipHostFree(c->host_bad);
     for (auto &um : c->user_modules) if (um.second.mod) (void)hipModuleUnload(um.second.mod);
@@ -1388,9 +1402,9 @@ int frr_target_ptrs(frr_ctx *c, void **color, void **depth, void **tri_id)
     return FRR_OK;
 }
 
-static int mesh_register(frr_ctx *c, const float *dev, bool owned, uint64_t ntris, int vs, int *mesh_out)
+static int mesh_register(frr_ctx *c, const float *dev, bool owned, uint64_t ntris, int vs, int *mesh_out, const uint32_t *idx = nullptr, uint64_t nverts = 0)
 {
-    Mesh m; m.dev = dev; m.owned = owned; m.used = true; m.ntris = ntris; m.vs = vs; m.gen = ++c->mesh_gen;
+    Mesh m; m.dev = dev; m.idx = idx; m.nverts = nverts; m.owned = owned; m.used = true; m.ntris = ntris; m.vs = vs; m.gen = ++c->mesh_gen;
     for (size_t i = 0; i < c->meshes.size(); ++i)
         if (!c->meshes[i].used) { c->meshes[i] = m; *mesh_out = (int)i; return FRR_OK; }
     c->meshes.push_back(m);
@@ -1420,11 +1434,68 @@ int frr_mesh_bind_device(frr_ctx *c, const void *dev, uint64_t ntris, int vs_id,
     c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
     return mesh_register(c, (const float *)dev, false, ntris, vs_id, mesh_out);
 }
+// ---- indexed meshes: the Model the reference expands on the CPU (phong.rs:187-205), drawn as it is --------------------
+static int indexed_args(frr_ctx *c, const void *verts, uint64_t nverts, const void *idx, uint64_t ntris, int vs_id, int *mesh_out)
+{
+    if (!c || !mesh_out || frr_vs_input_floats(vs_id) < 0 || (nverts && !verts) || (ntris && !idx)) return fail(c, FRR_ERR_INVALID, "bad mesh");
+    if (ntris && !nverts) return fail(c, FRR_ERR_INVALID, "indexed mesh: triangles but no vertices");
+    if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
+    if (nverts > 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^32 - 1 vertices per mesh (u32 indices)");
+    return FRR_OK;
+}
+static int bad_index(frr_ctx *c, uint64_t t, uint64_t nverts)
+{
+    return fail(c, FRR_ERR_INVALID, "indexed mesh: triangle " + std::to_string(t) + " has an index >= nverts (" + std::to_string(nverts) + "): model.vert(i, j) would panic");
+}
+int frr_mesh_upload_indexed(frr_ctx *c, const float *vertices, uint64_t nverts, const uint32_t *indices, uint64_t ntris, int vs_id, int *mesh_out)
+{
+    { int rc = indexed_args(c, vertices, nverts, indices, ntris, vs_id, mesh_out); if (rc != FRR_OK) return rc; }
+    if (((uintptr_t)indices & 3u) != 0) return fail(c, FRR_ERR_INVALID, "index pointer must be 4-byte aligned");
+    for (uint64_t t = 0; t < ntris; ++t)
+        if (indices[3 * t] >= nverts || indices[3 * t + 1] >= nverts || indices[3 * t + 2] >= nverts) return bad_index(c, t, nverts);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t vbytes = (size_t)nverts * frr_vs_input_floats(vs_id) * sizeof(float), ibytes = (size_t)ntris * 3 * sizeof(uint32_t);
+    void *dv = nullptr, *di = nullptr;
+    if (hipMalloc(&dv, vbytes ? vbytes : 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc mesh");
+    if (hipMalloc(&di, ibytes ? ibytes : 16) != hipSuccess) { (void)hipFree(dv); return fail(c, FRR_ERR_NOMEM, "hipMalloc mesh indices"); }
+    hipError_t e = hipSuccess;
+    if (vbytes) e = hipMemcpyAsync(dv, vertices, vbytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && ibytes) e = hipMemcpyAsync(di, indices, ibytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(dv); (void)hipFree(di); return fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
+    return mesh_register(c, (const float *)dv, true, ntris, vs_id, mesh_out, (const uint32_t *)di, nverts);
+}
+int frr_mesh_bind_device_indexed(frr_ctx *c, const void *dev_vertices, uint64_t nverts, const void *dev_indices, uint64_t ntris, int vs_id, int *mesh_out)
+{
+    { int rc = indexed_args(c, dev_vertices, nverts, dev_indices, ntris, vs_id, mesh_out); if (rc != FRR_OK) return rc; }
+    if (((uintptr_t)dev_vertices & 15u) != 0) return fail(c, FRR_ERR_INVALID, "mesh pointer must be 16-byte aligned");
+    if (((uintptr_t)dev_indices & 3u) != 0) return fail(c, FRR_ERR_INVALID, "index pointer must be 4-byte aligned");
+    if (ntris) {
+        // every index < nverts?  One reduction over the list on the caller's stream -- behind whatever wrote the list --
+        // and a host wait: binding is a set-up call.
+        HIP_TRY(c, hipSetDevice(c->device));
+        uint32_t *d_bad = nullptr, bad = 0xFFFFFFFFu;
+        if (hipMalloc((void **)&d_bad, 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+        hipError_t e = hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_index_check, dim3((uint32_t)std::min<uint64_t>((ntris + 255) / 256, 1024)), dim3(256), 0, c->stream,
+                               (const uint32_t *)dev_indices, (uint32_t)ntris, (uint32_t)nverts, d_bad);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_bad);
+        if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
+        if (bad != 0xFFFFFFFFu) return bad_index(c, bad, nverts);
+    }
+    c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
+    return mesh_register(c, (const float *)dev_vertices, false, ntris, vs_id, mesh_out, (const uint32_t *)dev_indices, nverts);
+}
 int frr_mesh_free(frr_ctx *c, int mesh)
 {
     if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a draw of it
-    if (c->meshes[mesh].owned) (void)hipFree((void *)c->meshes[mesh].dev);
+    if (c->meshes[mesh].owned) { (void)hipFree((void *)c->meshes[mesh].dev); if (c->meshes[mesh].idx) (void)hipFree((void *)c->meshes[mesh].idx); }
     c->meshes[mesh] = Mesh();
     return FRR_OK;
 }
@@ -1483,7 +1554,10 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     UserShader *us = new UserShader();
     us->nf = vs_input_floats; us->K = num_varyings;
     const std::string U = std::to_string(FRR_SHADER_USER_BASE), Ks = std::to_string(num_varyings);
-    std::vector<std::string> exprs = {"frr::k_geom_single<" + U + ">", "frr::k_geom_clip<" + U + ">"};
+    std::vector<std::string> exprs = {"frr::k_geom_single<" + U + ", false>", "frr::k_geom_clip<" + U + ", false>"};
+    const std::string geom_idx_expr = "frr::k_geom_single<" + U + ", true>", clip_idx_expr = "frr::k_geom_clip<" + U + ", true>";   // indexed meshes
+    (void)hiprtcAddNameExpression(prog, geom_idx_expr.c_str());
+    (void)hiprtcAddNameExpression(prog, clip_idx_expr.c_str());
     const std::string sweep_expr = "frr::k_raster<" + Ks + ", " + U + ">";   // the brute-force tile kernel (option raster_sweep)
     (void)hiprtcAddNameExpression(prog, sweep_expr.c_str());
     const std::string entries_expr = "frr::k_raster_entries<" + Ks + ", " + U + ">";   // windows whose rows share depth entries (x0 < 0)
@@ -1505,7 +1579,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     }
     bool ok = true;
     auto lowered = [&](const std::string &e) { const char *n = nullptr; ok = ok && hiprtcGetLoweredName(prog, e.c_str(), &n) == HIPRTC_SUCCESS && n; return std::string(n ? n : ""); };
-    us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
+    us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->geom_idx = lowered(geom_idx_expr); us->clip_idx = lowered(clip_idx_expr); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
     size_t cs = 0;
@@ -1884,6 +1958,7 @@ int frr_debug_mvp(frr_ctx *c, int mesh, int use_mfma, float *clip_out, float *ms
     if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used || !clip_out) return fail(c, FRR_ERR_INVALID, "bad arguments");
     const Mesh &m = c->meshes[mesh];
     if (m.vs != FRR_VS_PHONG && m.vs != FRR_VS_GOURAUD) return fail(c, FRR_ERR_INVALID, "needs a pos3/uv2/normal3 mesh");
+    if (m.idx) return fail(c, FRR_ERR_UNSUPPORTED, "frr_debug_mvp reads an expanded mesh, not an indexed one");
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t nverts = (uint32_t)(m.ntris * 3);
     float4 *d = nullptr;

@@ -161,8 +161,10 @@ struct DevUniforms {
 };
 
 struct GeomArgs {
-    const float *in;        // [ntris][3][NF]
+    const float *in;        // [ntris][3][NF]; indexed mesh: [nverts][NF]
+    const uint32_t *idx;    // indexed mesh: [ntris][3] vertex numbers (corner j of triangle t = in + idx[3t + j] * NF); else null
     uint32_t ntris;
+    uint32_t nverts;        // indexed mesh: vertex records behind `in` (> 0: the kernels clamp every index to nverts - 1)
     uint32_t width, height; // viewport of renderer.rs:107-108
     uint32_t fan_cap;       // capacity of the fan space (triangles): FAN_REGIONS regions of fan_cap / FAN_REGIONS (a multiple of FAN_REGIONS)
     uint32_t seq, epoch;    // sequence number of this geometry pass / failures before `epoch` are stale (Counters::first_bad)

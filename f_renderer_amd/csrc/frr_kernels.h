@@ -322,17 +322,38 @@ constexpr int CLIP_MAXV = 21;
 constexpr int CLIP_QUEUE_AT = 16;   // clipped inputs in one block from which on the block reports itself (the host then switches the clip queue on)
 constexpr int CLIP_INBLOCK = GEOM_BLOCK / 64;   // clipped inputs a geometry block expands itself when the clip queue is in use
 
+// The three vertex records of input triangle t (inputs[j] of phong.rs:190-197).  An expanded mesh holds them one after the
+// other; an indexed mesh (frr_mesh_upload_indexed) holds each vertex once and names a triangle's corners by number: three
+// u32 loads (12 contiguous bytes per thread), then the same 16-byte vector loads of run_vs at in + idx * NF.  The clamp is
+// not the error path -- registration refuses a mesh with an index >= nverts -- it keeps the loads inside the vertex array
+// whatever an index buffer that was rewritten in place without a re-bind holds.
+template <int NF, bool IDX>
+__device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const float *vp[3])
+{
+    if constexpr (IDX) {
+        const uint32_t *ix = g.idx + (size_t)t * 3;
+        const uint32_t last = g.nverts - 1u;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) vp[v] = g.in + (size_t)min(ix[v], last) * NF;
+    } else {
+        const float *in = g.in + (size_t)t * (3 * NF);
+#pragma unroll
+        for (int v = 0; v < 3; ++v) vp[v] = in + v * NF;
+    }
+}
+
 // Returns the lane's binning record (all zero for lanes that emit no fan triangle).  eoff: the input's emission offset
 // within its geometry block (tinfo[t] >> FAN_BITS).
-template <int VS>
+template <int VS, bool IDX>
 __device__ __forceinline__ uint4 clip_triangle_wave(const GeomArgs &g, const DevUniforms &u, uint32_t t, uint32_t fbase, uint32_t eoff, int lane,
                                                    float (*s_xy)[2], int32_t *s_key, float (*s_v)[7 + (VSInfo<VS>::K > 0 ? VSInfo<VS>::K : 1)])
 {
     constexpr int NF = VSInfo<VS>::NF, K = VSInfo<VS>::K, KS = K > 0 ? K : 1;
     float pos[3][4], ctx[3][KS];
-    const float *in = g.in + (size_t)t * (3 * NF);
+    const float *in[3];
+    tri_inputs<NF, IDX>(g, t, in);
 #pragma unroll
-    for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in + v * NF, pos[v], ctx[v]);
+    for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in[v], pos[v], ctx[v]);
     // this lane's vertex
     float p[4], c[KS];
     bool keep;
@@ -532,7 +553,7 @@ __device__ __forceinline__ void geom_bookkeeping(const GeomArgs &g)
     me.tinfo = g.tinfo; me.fanbase = g.fanbase; me.fan_okey = g.fan_okey; me.block_prefix = g.block_prefix;
 }
 
-template <int VS>
+template <int VS, bool IDX>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUniforms u)
 {
     __shared__ uint32_t s_w[4];
@@ -556,9 +577,10 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
     uint32_t n = 0;   // triangles this input emits (the reference's count)
     bool clipped = false;
     if (t < g.ntris) {
-        const float *in = g.in + (size_t)t * (3 * NF);
+        const float *in[3];
+        tri_inputs<NF, IDX>(g, t, in);
 #pragma unroll
-        for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in + v * NF, pos[v], ctx[v]);
+        for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in[v], pos[v], ctx[v]);
         n = classify(pos, clipped);
     }
     if (seq_is_cancelled(first_bad, g.seq, g.epoch, false)) return;   // an earlier command failed: the host replays from there (nothing written yet)
@@ -707,13 +729,13 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         for (uint32_t e = (uint32_t)w; e < nin; e += GEOM_BLOCK / 64) {
             const uint32_t en = s_cl[e];
-            (void)clip_triangle_wave<VS>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
+            (void)clip_triangle_wave<VS, IDX>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
         }
     }
 }
 
 // the clipped inputs the geometry blocks queued (GeomArgs::use_clipq), one wavefront per triangle over the whole chip
-template <int VS>
+template <int VS, bool IDX>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniforms u)
 {
     __shared__ float s_cxy[GEOM_BLOCK / 64][CLIP_MAXV][2];
@@ -725,7 +747,7 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniform
     const uint32_t stride = gridDim.x * (GEOM_BLOCK / 64);
     for (uint32_t e = blockIdx.x * (GEOM_BLOCK / 64) + (uint32_t)w; e < n; e += stride) {
         const uint2 q = g.clipq[e];
-        (void)clip_triangle_wave<VS>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
+        (void)clip_triangle_wave<VS, IDX>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
     }
 }
 
@@ -734,6 +756,20 @@ __global__ void k_geom_empty(GeomArgs g)
 {
     if (seq_cancelled(g.cnt, g.seq, g.epoch, false)) return;
     if (threadIdx.x == 0 && blockIdx.x == 0) geom_bookkeeping(g);
+}
+
+// frr_mesh_bind_device_indexed: the reference's out-of-bounds panic (model.vert(i, j)) for an index list that lives on the
+// device.  *first_bad (0xFFFFFFFF on entry) becomes the smallest triangle number with an index >= nverts.
+__global__ __launch_bounds__(256) void k_index_check(const uint32_t *__restrict__ idx, uint32_t ntris, uint32_t nverts, uint32_t *first_bad)
+{
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x; t < ntris; t += (uint64_t)gridDim.x * 256u) {
+        const uint32_t *ix = idx + (size_t)t * 3;
+        if (ix[0] >= nverts || ix[1] >= nverts || ix[2] >= nverts) bad = min(bad, (uint32_t)t);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint32_t)__shfl_xor(bad, o));
+    if ((threadIdx.x & 63) == 0 && bad != 0xFFFFFFFFu) atomicMin(first_bad, bad);
 }
 
 // Exclusive scan of the draw's block sums (in place: they become Counters::block_prefix), by one workgroup of 1024

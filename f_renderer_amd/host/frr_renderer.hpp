@@ -19,6 +19,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -169,6 +170,11 @@ public:
     }
     // init_vertex_input (phong.rs:187-201): Vec<[VSInput;3]>
     std::vector<std::array<struct VSInput, 3>> vertex_inputs() const;
+    // The same mesh without the expansion, for Renderer::upload_mesh_indexed: one VSInput per distinct (v, vt, vn) triple of
+    // the faces, in first-use order, and per face the three vertex numbers.  vertices[faces[i][j]] == vertex_inputs()[i][j],
+    // bit for bit.
+    struct Indexed { std::vector<struct VSInput> vertices; std::vector<std::array<uint32_t, 3>> faces; };
+    Indexed indexed_inputs() const;
 
 private:
     Model() = default;
@@ -252,6 +258,23 @@ inline std::vector<std::array<VSInput, 3>> Model::vertex_inputs() const
     return out;
 }
 
+inline Model::Indexed Model::indexed_inputs() const
+{
+    Indexed out;
+    out.faces.resize(faces_len());
+    std::map<std::array<uint32_t, 3>, uint32_t> seen;
+    for (size_t i = 0; i < faces_len(); ++i)
+        for (size_t j = 0; j < 3; ++j) {
+            const auto it = seen.find(faces_[i][j]);
+            if (it != seen.end()) { out.faces[i][j] = it->second; continue; }
+            const Vec3 p = vert(i, j), n = normal(i, j);
+            const std::array<float, 2> t = uv(i, j);
+            out.faces[i][j] = seen[faces_[i][j]] = (uint32_t)out.vertices.size();
+            out.vertices.push_back(VSInput{{p.x, p.y, p.z}, {t[0], t[1]}, {n.x, n.y, n.z}});
+        }
+    return out;
+}
+
 struct Mesh { int id = -1; uint64_t ntris = 0; int vs = 0; };
 
 // Device-resident FrameBuffer + f32 depth buffer + u32 triangle-id buffer and the two halves of the
@@ -286,6 +309,27 @@ public:
     {
         Mesh m; m.ntris = ntris; m.vs = vs_id;
         check(frr_mesh_upload(ctx_, vs_inputs, ntris, vs_id, &m.id));
+        return m;
+    }
+    // The Model itself (vertex array + index list) instead of its expansion: corner j of triangle t is
+    // vertices[faces[t][j]].  An index >= the vertex count is the reference's out-of-bounds panic -> frr::Error.
+    Mesh upload_mesh_indexed(const Model::Indexed &m, int vs_id = FRR_VS_PHONG)
+    {
+        return upload_mesh_indexed_raw(reinterpret_cast<const float *>(m.vertices.data()), m.vertices.size(),
+                                       reinterpret_cast<const uint32_t *>(m.faces.data()), m.faces.size(), vs_id);
+    }
+    Mesh upload_mesh_indexed_raw(const float *vertices, uint64_t nverts, const uint32_t *indices, uint64_t ntris, int vs_id)
+    {
+        Mesh m; m.ntris = ntris; m.vs = vs_id;
+        check(frr_mesh_upload_indexed(ctx_, vertices, nverts, indices, ntris, vs_id, &m.id));
+        return m;
+    }
+    // the same for device memory the caller owns (16-byte aligned vertices); validated on the device inside the call.  After
+    // an in-place rewrite of either buffer: frame_fence, rewrite, bind again (include/frr.h: frr_create)
+    Mesh bind_mesh_device_indexed(const void *dev_vertices, uint64_t nverts, const void *dev_indices, uint64_t ntris, int vs_id)
+    {
+        Mesh m; m.ntris = ntris; m.vs = vs_id;
+        check(frr_mesh_bind_device_indexed(ctx_, dev_vertices, nverts, dev_indices, ntris, vs_id, &m.id));
         return m;
     }
     void free_mesh(Mesh &m) { if (m.id >= 0) { check(frr_mesh_free(ctx_, m.id)); m.id = -1; } }

@@ -207,6 +207,30 @@ class Renderer:
         self._check(self._lib.frr_mesh_bind_device(self._ctx, C.c_void_p(dev_ptr), ntris, vs_id, C.byref(mid)))
         return Mesh(self, mid.value, ntris, vs_id, keepalive)
 
+    def upload_mesh_indexed(self, vertices, indices, vs_id):
+        """The Model itself instead of its expansion (phong.rs:187-205): vertices float32 [V,NF], indices uint32 [F,3];
+        corner j of triangle t is vertices[indices[t, j]].  Draws exactly as upload_mesh(vertices[indices]) does.
+        An index >= V (the reference's out-of-bounds panic) raises FrrError(FRR_ERR_INVALID)."""
+        nf = self._lib.frr_vs_input_floats(vs_id)
+        if nf < 0:
+            raise FrrError(N.FRR_ERR_INVALID, "unknown vertex shader id")
+        v = np.ascontiguousarray(vertices, np.float32)
+        i = np.ascontiguousarray(indices, np.uint32)
+        if v.size % nf or i.size % 3:
+            raise FrrError(N.FRR_ERR_INVALID, "vertices / indices size is not a multiple of floats_per_vertex / 3")
+        ntris = i.size // 3
+        mid = C.c_int()
+        self._check(self._lib.frr_mesh_upload_indexed(self._ctx, v.ctypes.data, v.size // nf, i.ctypes.data, ntris, vs_id, C.byref(mid)))
+        return Mesh(self, mid.value, ntris, vs_id)
+
+    def bind_mesh_device_indexed(self, vert_ptr, nverts, idx_ptr, ntris, vs_id, keepalive=None):
+        """Same, for a vertex array (float32 [nverts,NF]) and an index list (uint32 [ntris,3]) already in HBM, e.g. two
+        torch tensors' data_ptr().  The indices are validated on the device inside this call (a host wait).  After an
+        in-place rewrite of either buffer: frame_fence, rewrite, bind again (which validates again)."""
+        mid = C.c_int()
+        self._check(self._lib.frr_mesh_bind_device_indexed(self._ctx, C.c_void_p(vert_ptr), nverts, C.c_void_p(idx_ptr), ntris, vs_id, C.byref(mid)))
+        return Mesh(self, mid.value, ntris, vs_id, keepalive)
+
     def set_texture(self, slot, image):
         """PSUniform.sample_2d_* (phong.rs:43-45): FrameBuffer or uint8 [h,w,4]."""
         buf = image.buffer if isinstance(image, FrameBuffer) else np.ascontiguousarray(image, np.uint8)

@@ -218,6 +218,24 @@ int frr_target_ptrs(frr_ctx *ctx, void **color_rgba8, void **depth_f32, void **t
 int frr_mesh_upload(frr_ctx *ctx, const float *vs_inputs, uint64_t ntris, int vs_id, int *mesh_out);
 /* Same, data already in device memory (borrowed until frr_mesh_free). */
 int frr_mesh_bind_device(frr_ctx *ctx, const void *dev_vs_inputs, uint64_t ntris, int vs_id, int *mesh_out);
+/* The same mesh as a Model keeps it (obj_loader.rs; what init_vertex_input expands on the CPU, phong.rs:187-205): each
+ * vertex once and three vertex numbers per triangle.
+ * vertices: nverts x frr_vs_input_floats(vs_id) f32; indices: ntris x 3 u32, corner j of triangle t = vertices[indices[3t+j]]
+ * == inputs[j] of phong.rs:190-197 with model.vert/uv/normal folded into one vertex record.
+ * The mesh id is an ordinary one (frr_geometry, frr_draw, frr_readback_setup, frr_mesh_free ...), and everything a draw of
+ * it produces -- images, triangle ids, emission order, statistics -- is that of the expanded mesh, bit for bit.
+ * An index >= nverts is the reference's out-of-bounds panic (model.vert(i, j)): FRR_ERR_INVALID, no mesh id, and
+ * frr_last_error names the first such triangle.  frr_mesh_upload_indexed checks on the host; frr_mesh_bind_device_indexed
+ * with one small kernel over the index list on the ctx's stream and a host wait inside the call.  ntris == 0 is valid;
+ * nverts == 0 with ntris > 0 is FRR_ERR_INVALID; ntris < 2^27 as above; device vertices 16-byte aligned, indices 4-byte.
+ * Rewriting the vertices OR the indices of a device-bound mesh in place follows the rule of frr_create: frr_frame_fence,
+ * rewrite, bind again -- and the new bind validates again.  (Should an index list be rewritten WITHOUT a re-bind, the
+ * kernels still read only inside the vertex array: they clamp every index to nverts - 1.  That is a guard for the
+ * machine, not a defined result.)  frr_debug_mvp does not take an indexed mesh (FRR_ERR_UNSUPPORTED). */
+int frr_mesh_upload_indexed(frr_ctx *ctx, const float *vertices, uint64_t nverts,
+                            const uint32_t *indices, uint64_t ntris, int vs_id, int *mesh_out);
+int frr_mesh_bind_device_indexed(frr_ctx *ctx, const void *dev_vertices, uint64_t nverts,
+                                 const void *dev_indices, uint64_t ntris, int vs_id, int *mesh_out);
 int frr_mesh_free(frr_ctx *ctx, int mesh);
 /* FrameBuffer used as texture (PSUniform.sample_2d_*, phong.rs:43-45): RGBA8 row-major.
  * height >= width is required: sample_2d clamps y with width (renderer.rs:523,525), so a

@@ -70,6 +70,8 @@ pub mod ffi {
         pub fn frr_bind_targets(ctx: *mut frr_ctx, color: *mut c_void, depth: *mut c_void, tri_id: *mut c_void) -> c_int;
         pub fn frr_target_ptrs(ctx: *mut frr_ctx, color: *mut *mut c_void, depth: *mut *mut c_void, tri_id: *mut *mut c_void) -> c_int;
         pub fn frr_mesh_upload(ctx: *mut frr_ctx, vs_inputs: *const f32, ntris: u64, vs_id: c_int, mesh_out: *mut c_int) -> c_int;
+        pub fn frr_mesh_upload_indexed(ctx: *mut frr_ctx, vertices: *const f32, nverts: u64, indices: *const u32, ntris: u64, vs_id: c_int, mesh_out: *mut c_int) -> c_int;
+        pub fn frr_mesh_bind_device_indexed(ctx: *mut frr_ctx, dev_vertices: *const c_void, nverts: u64, dev_indices: *const c_void, ntris: u64, vs_id: c_int, mesh_out: *mut c_int) -> c_int;
         pub fn frr_mesh_free(ctx: *mut frr_ctx, mesh: c_int) -> c_int;
         pub fn frr_texture_upload(ctx: *mut frr_ctx, slot: c_int, rgba: *const u8, width: u32, height: u32) -> c_int;
         pub fn frr_set_uniforms(ctx: *mut frr_ctx, u: *const frr_uniforms) -> c_int;
