@@ -8,6 +8,8 @@
 //       the reference's own asset formats: Model::new (obj_loader.rs:15-97), uploaded as an indexed mesh (the expansion of
 //       init_vertex_input, phong.rs:187-201, is the GPU's gather)
 //       and FrameBuffer::load_file (renderer.rs:427-471, BGRA storage)
+//   a --wireframe anywhere among the arguments of the two forms above overlays the mesh's edges (FrameBuffer::draw_line,
+//       renderer.rs:540-588, over the setup triangles) in white after the shaded draw, on the device
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
 //       loaders only (no GPU): what the two loaders produce, for the CPU-side check against the Python mirror
 #include <cmath>
@@ -27,6 +29,13 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
+    bool wireframe = false;
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "--wireframe") {
+            wireframe = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            --argc; --i;
+        }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -43,7 +52,8 @@ int main(int argc, char **argv)
     const bool assets = mode == "--assets";
     if ((assets && argc < 7) || (!assets && argc < 8)) {
         std::cerr << "usage: phong_headless mesh.f32 ntris tex.rgba tex_size W H out.rgba [out.ppm]\n"
-                     "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n";
+                     "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
+                     "       (--wireframe: overlay the mesh's edges)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -88,6 +98,7 @@ int main(int argc, char **argv)
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317
         renderer.geometry_processing(mesh);                                                     // loop A
         renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_PHONG);                 // loop B
+        if (wireframe) renderer.draw_wireframe({255, 255, 255, 255});                           // the edges over the shaded frame
         renderer.read_frame_buffer(frame_buffer);                                               // phong.rs:386
 
         const frr_stats st = renderer.stats();

@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("FRR_LIB") or os.path.join(_HERE, "libfrr_hip.so")  # FRR_LIB: developer override
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_lines.h")]
 _HDR = os.path.join(_ROOT, "include", "frr.h")
 
 HIPCC_FLAGS = [
@@ -121,6 +121,12 @@ SIGNATURES = {
     "frr_mesh_upload_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_bind_device_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_lines_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_lines_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_lines_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_draw_lines": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_draw_wireframe": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "frr_host_line_pixels": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
     "frr_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "frr_set_uniforms": (C.c_int, [C.c_void_p, _P(Uniforms)]),
     "frr_shader_register": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _P(C.c_int)]),

@@ -2,6 +2,7 @@
 // frr_kernels.h.  gfx950 only; no CPU fallback (every compute entry point needs the device).
 #include "frr_kernels.h"
 #include "frr_tile_order.h"
+#include "frr_lines.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -35,10 +36,10 @@ using namespace frr;
 namespace {
 
 enum KernelId { KID_CLEAR, KID_GEOM, KID_GEOM_SCAN, KID_BIN_COUNT,
-                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_COUNT };
+                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_LINES_MARK, KID_LINES_PAINT, KID_COUNT };
 const char *const kKernelNames[KID_COUNT] = {"k_clear", "k_geom", "k_geom_scan",
                                              "k_bin_count", "k_tile_scan", "k_bin_fill",
-                                             "k_raster", "k_bin_seg"};
+                                             "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint"};
 
 struct Mesh {
     const float *dev = nullptr;    // [ntris][3][NF], or with idx: the vertex array [nverts][NF]
@@ -52,6 +53,13 @@ struct Mesh {
 struct Texture {
     uint8_t *dev = nullptr;
     uint32_t w = 0, h = 0;
+};
+// a list of draw_line calls (frr_lines_upload / frr_lines_bind_device): every segment's walk stays inside the buffer
+struct Lines {
+    const uint4 *xyxy = nullptr;     // [n] {x1, y1, x2, y2}
+    const uint32_t *rgba = nullptr;  // [n]
+    uint64_t n = 0;
+    bool owned = false, used = false;
 };
 struct ProfRec { int kid; hipEvent_t a, b; };
 
@@ -175,7 +183,7 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER } kind;
+    enum Kind { GEOM, RASTER, LINES } kind;
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -183,7 +191,9 @@ struct Cmd {
     int mesh = -1; bool filter = false; int32_t fy0 = 0, fy1 = 0;
     // RASTER
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
-    int par = 0;               // the parity it ran with (finish(): which table a failed command left behind)
+    // LINES: a list, or (lines < 0) the wireframe of the latest geometry pass in one colour
+    int lines = -1; uint32_t wire_rgba = 0;
+    int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
 };
@@ -286,6 +296,15 @@ struct frr_ctx {
     uint32_t max_tiles = 0;
     bool lds_attr_set = false;
     std::vector<Mesh> meshes;
+    std::vector<Lines> lines;
+    // draw_line order is resolved per pixel on a u32 plane of W * H (frr_lines.h), all-zero between commands: one per stream
+    // that can carry target writes -- [0] `stream`, [1] / [2] the frame streams tstream[0] / tstream[1] -- because the line
+    // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
+    uint32_t *line_owner[3] = {};
+    uint32_t lines_chunk = 0;       // option lines_chunk (0: LINES_CHUNK)
+    // per lane of device tables: the latest wireframe reads its geometry pass's fan cursors, which the next pass IN THAT LANE
+    // zeroes (geom_bookkeeping), whatever workspace set it writes; the other lane's frame shares nothing with it
+    ReaderFence wire_reader[2];
     std::map<int, UserModule> user_modules;   // user shader id -> its code object loaded on this ctx's device
     Texture tex[FRR_MAX_TEXTURES];
     frr_uniforms uni;
@@ -364,6 +383,7 @@ int drain(frr_ctx *c)
     for (FrameStream &t : c->tstream) t.dirty = t.xdirty = false;
     c->g_used = false;
     for (int i = 0; i < 2; ++i) c->gset[i].reader.pending = c->bset[i].reader.pending = false;
+    for (ReaderFence &r : c->wire_reader) r.pending = false;
     return FRR_OK;
 }
 // a caller's stream waits for the ctx's frame streams: what is enqueued on it next sees every frame issued so far
@@ -769,6 +789,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     // kernel that last read this workspace
     if ((rc = gstream_join(c)) != FRR_OK) return rc;
     if ((rc = gstream_wait_readers(c, S.reader)) != FRR_OK) return rc;
+    if ((rc = gstream_wait_readers(c, c->wire_reader[f.lane])) != FRR_OK) return rc;
     GeomArgs g;
     g.in = m.dev; g.idx = m.idx; g.nverts = (uint32_t)m.nverts; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
     g.fan_cap = (uint32_t)fan_cap;
@@ -1019,6 +1040,68 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// FrameBuffer::draw_line (renderer.rs:540-588) for every segment of a list, in list order, or for the edges of the latest
+// geometry pass's triangles: colour only, on the targets' stream, ordered like a tile kernel.  It cannot fail on the
+// device and has nothing in the device tables to reset, so a replay simply runs it again in its place.
+int exec_lines(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    const bool wire = cmd.lines < 0;
+    int rc;
+    if (wire && (rc = scan_now(c)) != FRR_OK) return rc;   // a fan space that was too small is flagged before the edges are read (they are then cancelled, and replayed)
+    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    LinesArgs a;
+    memset(&a, 0, sizeof a);
+    uint32_t batches;
+    if (wire) {
+        const GeomSet &S = c->gset[f.gset];
+        a.recs = S.recs; a.tinfo = S.tinfo; a.fan_cap = f.geom_fan_cap; a.wire_rgba = cmd.wire_rgba;
+        a.gpar = f.gpar(); a.lane = f.lane;
+        batches = (uint32_t)((3ull * (f.geom_ntris + f.geom_fan_cap) + 63) / 64);
+        if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
+    } else {
+        const Lines &L = c->lines[cmd.lines];
+        a.xyxy = L.xyxy; a.rgba = L.rgba; a.nlines = (uint32_t)L.n;
+        batches = (uint32_t)((L.n + 63) / 64);
+    }
+    hipStream_t ts;
+    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
+    // (a device-bound list needs no join of `ts` with the caller's stream: frr_lines_bind_device has waited on the host for
+    // that stream, behind whatever wrote the list)
+    uint32_t *&owner = c->line_owner[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
+    if (!owner) {
+        const size_t bytes = (size_t)c->W * c->H * sizeof(uint32_t);
+        if (hipMalloc((void **)&owner, bytes) != hipSuccess) { owner = nullptr; return fail(c, FRR_ERR_NOMEM, "hipMalloc owner plane"); }
+        const hipError_t e = hipMemsetAsync(owner, 0, bytes, ts);
+        if (e != hipSuccess) { (void)hipFree(owner); owner = nullptr; return fail(c, FRR_ERR_HIP, std::string("hipMemsetAsync owner plane: ") + hipGetErrorString(e)); }
+    }
+    a.W = c->W; a.H = c->H;
+    a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
+    if (a.own.blocked) blocked_rows((int)((c->H + TILE - 1) / TILE), f.rank, f.world, &a.own.brow0, &a.own.brow1);
+    a.chunk = c->lines_chunk ? c->lines_chunk : LINES_CHUNK;
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    a.owner = owner; a.color = (uint32_t *)f.color;
+    const dim3 grid(std::max<uint32_t>(std::min<uint32_t>(batches, 16384u), 1u)), block(64);
+    {
+        ProfScope p(c, KID_LINES_MARK, ts);
+        if (wire) hipLaunchKernelGGL(k_lines_mark<true>, grid, block, 0, ts, a);
+        else hipLaunchKernelGGL(k_lines_mark<false>, grid, block, 0, ts, a);
+    }
+    {
+        ProfScope p(c, KID_LINES_PAINT, ts);
+        if (wire) hipLaunchKernelGGL(k_lines_paint<true>, grid, block, 0, ts, a);
+        else hipLaunchKernelGGL(k_lines_paint<false>, grid, block, 0, ts, a);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (wire) {
+        ReaderFence &wr = c->wire_reader[f.lane];
+        wr.pending = true; wr.stream = ts; wr.recorded = false;
+        cmd.par = f.gpar(); cmd.set = f.gset;
+    }
+    cmd.lane = f.lane;
+    return FRR_OK;
+}
+
 int finish(frr_ctx *c);
 
 // run a command and remember it (finish() replays the commands from a failed one onwards)
@@ -1027,7 +1110,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : exec_raster(c, cmd);
+    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : exec_lines(c, cmd);
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1095,8 +1178,11 @@ int finish(frr_ctx *c)
         // the device tables as they were before the failed command: it has used its own parity's cursors (and, when its
         // block sums were scanned inside the next raster pass's binning launch, that pass has reserved bin space)
         h.first_bad = SEQ_NONE; h.overflow = 0u;
-        for (size_t k = i; k < std::min(i + 2, c->log.size()); ++k) {
+        // (line commands in between own no table: the "next" command is the next geometry or raster pass)
+        for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
+            if (m.kind == Cmd::LINES) continue;
+            ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
                 for (int r = 0; r < FAN_REGIONS; ++r) gt.fan_cursor[r].v = 0u;
@@ -1194,6 +1280,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     for (int i = 1; i >= 0; --i) ok = ok && hipEventCreateWithFlags(&c->tstream[i].ev, hipEventDisableTiming) == hipSuccess;
     for (auto &e : c->ev_bin) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
+    for (ReaderFence &r : c->wire_reader) ok = ok && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_verify, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_export, hipEventDisableTiming) == hipSuccess;
     if (!ok) { frr_destroy(c); return FRR_ERR_NOMEM; }
     c->fs.color = c->own_color[0]; c->fs.depth = c->own_depth[0]; c->fs.tri_id = c->own_tri_id[0];
@@ -1232,6 +1319,9 @@ void frr_destroy(frr_ctx *c)
     for (hipStream_t st : {c->gstream, c->tstream[1].st, c->tstream[0].st, c->stream}) if (st) (void)hipStreamSynchronize(st);
     prof_collect(c);
     for (auto &m : c->meshes) if (m.used && m.owned) { (void)hipFree((void *)m.dev); if (m.idx) (void)hipFree((void *)m.idx); }
+    for (auto &l : c->lines) if (l.used && l.owned) { (void)hipFree((void *)l.xyxy); (void)hipFree((void *)l.rgba); }
+    for (uint32_t *p : c->line_owner) if (p) (void)hipFree(p);
+    for (ReaderFence &r : c->wire_reader) if (r.ev) (void)hipEventDestroy(r.ev);
     for (auto &t : c->tex) if (t.dev) (void)hipFree(t.dev);
     if (c->host_bad) (void)hipHostFree(c->host_bad);
     for (auto &um : c->user_modules) if (um.second.mod) (void)hipModuleUnload(um.second.mod);
@@ -1279,6 +1369,7 @@ int frr_set_option(frr_ctx *c, const char *name, int64_t v)
     else if (n == "overlap") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "overlap: 0, 1 or 2"); c->overlap = (int)v; }
     else if (n == "bound_targets_in_flight") c->bound_in_flight = v != 0;
     else if (n == "tile_order") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "tile_order: 0, 1 or 2"); c->tile_order = (int)v; }
+    else if (n == "lines_chunk") { if (v < 0 || v > (int64_t)LINES_CHUNK) return fail(c, FRR_ERR_INVALID, "lines_chunk: 0 .. 2^24"); c->lines_chunk = (uint32_t)v; }
     else if (n == "frames_in_flight") { if (v != 1 && v != 2) return fail(c, FRR_ERR_INVALID, "frames_in_flight: 1 or 2"); c->frames_in_flight = (int)v; }
     else return fail(c, FRR_ERR_INVALID, "unknown option");
     return FRR_OK;
@@ -1498,6 +1589,115 @@ int frr_mesh_free(frr_ctx *c, int mesh)
     if (c->meshes[mesh].owned) { (void)hipFree((void *)c->meshes[mesh].dev); if (c->meshes[mesh].idx) (void)hipFree((void *)c->meshes[mesh].idx); }
     c->meshes[mesh] = Mesh();
     return FRR_OK;
+}
+
+// ---- draw_line (renderer.rs:540-588): lists of segments and the wireframe of the latest setup list ------------------
+static int bad_segment(frr_ctx *c, uint64_t k)
+{
+    return fail(c, FRR_ERR_INVALID, "lines: segment " + std::to_string(k) + " would write past the " + std::to_string(c->W) + " x " + std::to_string(c->H) +
+                                    " buffer: set_pixel would panic (renderer.rs:497-503)");
+}
+static int lines_args(frr_ctx *c, const void *xyxy, const void *rgba, uint64_t nlines, int *lines_out)
+{
+    if (!c || !lines_out || (nlines && (!xyxy || !rgba))) return fail(c, FRR_ERR_INVALID, "bad line list");
+    if (nlines >= (1ull << 31)) return fail(c, FRR_ERR_UNSUPPORTED, "2^31 or more segments per list (owner numbers are u32)");
+    return FRR_OK;
+}
+static int lines_register(frr_ctx *c, const void *xyxy, const void *rgba, uint64_t n, bool owned, int *lines_out)
+{
+    Lines l; l.xyxy = (const uint4 *)xyxy; l.rgba = (const uint32_t *)rgba; l.n = n; l.owned = owned; l.used = true;
+    for (size_t i = 0; i < c->lines.size(); ++i)
+        if (!c->lines[i].used) { c->lines[i] = l; *lines_out = (int)i; return FRR_OK; }
+    c->lines.push_back(l);
+    *lines_out = (int)c->lines.size() - 1;
+    return FRR_OK;
+}
+int frr_lines_upload(frr_ctx *c, const uint32_t *xyxy, const uint8_t *rgba, uint64_t nlines, int *lines_out)
+{
+    { int rc = lines_args(c, xyxy, rgba, nlines, lines_out); if (rc != FRR_OK) return rc; }
+    const uint64_t npix = (uint64_t)c->W * c->H;
+    for (uint64_t k = 0; k < nlines; ++k)
+        if (line_max_index(line_setup(xyxy[4 * k], xyxy[4 * k + 1], xyxy[4 * k + 2], xyxy[4 * k + 3]), c->W) >= npix) return bad_segment(c, k);
+    HIP_TRY(c, hipSetDevice(c->device));
+    void *dx = nullptr, *dc = nullptr;
+    if (hipMalloc(&dx, nlines ? nlines * 16 : 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc lines");
+    if (hipMalloc(&dc, nlines ? nlines * 4 : 16) != hipSuccess) { (void)hipFree(dx); return fail(c, FRR_ERR_NOMEM, "hipMalloc line colours"); }
+    hipError_t e = hipSuccess;
+    if (nlines) e = hipMemcpyAsync(dx, xyxy, nlines * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nlines) e = hipMemcpyAsync(dc, rgba, nlines * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(dx); (void)hipFree(dc); return fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
+    return lines_register(c, dx, dc, nlines, true, lines_out);
+}
+int frr_lines_bind_device(frr_ctx *c, const void *dev_xyxy, const void *dev_rgba, uint64_t nlines, int *lines_out)
+{
+    { int rc = lines_args(c, dev_xyxy, dev_rgba, nlines, lines_out); if (rc != FRR_OK) return rc; }
+    if (((uintptr_t)dev_xyxy & 15u) != 0) return fail(c, FRR_ERR_INVALID, "segment pointer must be 16-byte aligned");
+    if (((uintptr_t)dev_rgba & 3u) != 0) return fail(c, FRR_ERR_INVALID, "colour pointer must be 4-byte aligned");
+    if (nlines) {
+        // does every walk stay inside the buffer?  One reduction over the list on the caller's stream -- behind whatever wrote
+        // the list -- and a host wait, as for the indices of frr_mesh_bind_device_indexed.
+        HIP_TRY(c, hipSetDevice(c->device));
+        uint32_t *d_bad = nullptr, bad = 0xFFFFFFFFu;
+        if (hipMalloc((void **)&d_bad, 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+        hipError_t e = hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_lines_check, dim3((uint32_t)std::min<uint64_t>((nlines + 255) / 256, 1024)), dim3(256), 0, c->stream,
+                               (const uint4 *)dev_xyxy, (uint32_t)nlines, c->W, (uint64_t)c->W * c->H, d_bad);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_bad);
+        if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
+        if (bad != 0xFFFFFFFFu) return bad_segment(c, bad);
+    }
+    return lines_register(c, dev_xyxy, dev_rgba, nlines, false, lines_out);   // (the host wait above stands for a join of the ctx's private streams)
+}
+int frr_lines_free(frr_ctx *c, int lines)
+{
+    if (!c || lines < 0 || lines >= (int)c->lines.size() || !c->lines[lines].used) return fail(c, FRR_ERR_INVALID, "bad line list id");
+    { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a draw of it
+    if (c->lines[lines].owned) { (void)hipFree((void *)c->lines[lines].xyxy); (void)hipFree((void *)c->lines[lines].rgba); }
+    c->lines[lines] = Lines();
+    return FRR_OK;
+}
+int frr_draw_lines(frr_ctx *c, int lines)
+{
+    if (!c || lines < 0 || lines >= (int)c->lines.size() || !c->lines[lines].used) return fail(c, FRR_ERR_INVALID, "bad line list id");
+    if (c->lines[lines].n == 0) return FRR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Cmd cmd;
+    cmd.kind = Cmd::LINES; cmd.lines = lines; cmd.duni = c->duni;
+    return exec_cmd(c, cmd);
+}
+int frr_draw_wireframe(frr_ctx *c, const uint8_t rgba[4])
+{
+    if (!c || !rgba) return fail(c, FRR_ERR_INVALID, "bad arguments");
+    const FrameState &f = c->fs;
+    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_draw_wireframe before frr_geometry");
+    if (f.geom_filter.active)
+        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry (unfiltered) before frr_draw_wireframe");
+    if (f.geom_ntris == 0) return FRR_OK;
+    // (segment numbers + 1 are u32, and a wave's last batch of 64 must not wrap either)
+    if (3ull * (f.geom_ntris + f.geom_fan_cap) + 64ull >= 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "wireframe: more than 2^32 / 3 setup slots (owner numbers are u32)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Cmd cmd;
+    cmd.kind = Cmd::LINES; cmd.lines = -1; cmd.duni = c->duni;
+    memcpy(&cmd.wire_rgba, rgba, 4);
+    return exec_cmd(c, cmd);
+}
+int64_t frr_host_line_pixels(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2, uint32_t width, uint64_t *out, uint64_t cap)
+{
+    const LineSeg s = line_setup(x1, y1, x2, y2);
+    const uint64_t n = line_iters(s);
+    uint64_t count = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t p[2];
+        const int np = line_iter(s, (uint32_t)i, width, p);
+        for (int w = 0; w < np; ++w, ++count) if (out && count < cap) out[count] = p[w];
+    }
+    return (int64_t)count;
 }
 
 int frr_texture_upload(frr_ctx *c, int slot, const uint8_t *rgba, uint32_t w, uint32_t h)

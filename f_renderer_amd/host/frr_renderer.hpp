@@ -3,7 +3,7 @@
 // is the compiled-language host layer: same names, argument meaning and error behaviour as
 //   Renderer::geometry_processing  /root/reference/f_renderer/src/renderer.rs:96-112
 //   Renderer::rasterization        /root/reference/f_renderer/src/renderer.rs:269-284
-//   FrameBuffer::{new,fill,clear,get_size,get_data,set_pixel,get_pixel}  renderer.rs:418-514
+//   FrameBuffer::{new,fill,clear,get_size,get_data,set_pixel,get_pixel,draw_line}  renderer.rs:418-514, 540-588
 //   set_identity / set_look_at / set_perspective   matrix_util.rs:3-35,   Camera  camera.rs:4-26
 //   Model::{new,faces_len,vert,uv,normal}  obj_loader.rs:7-97 (+ init_vertex_input, phong.rs:187-201)
 //   FrameBuffer::load_file  renderer.rs:427-471 (BGRA storage; TGA decoded here, the reference uses the image crate)
@@ -134,6 +134,33 @@ public:
         std::array<uint8_t, 4> c;
         std::memcpy(c.data(), &buffer_.at((size_t)(y * width_ + x) * 4), 4);
         return c;
+    }
+    // renderer.rs:540-588, statement by statement: endpoints sorted per axis, independently (a falling line is drawn as the
+    // rising one); vertical / horizontal lines exclude their upper end; set_pixel addresses linearly with no test of x, so
+    // x >= width lands in a later row, and past the buffer the reference panics (std::out_of_range here)
+    void draw_line(uint32_t xa, uint32_t ya, uint32_t xb, uint32_t yb, const std::array<uint8_t, 4> &c)
+    {
+        const uint32_t x1 = xa < xb ? xa : xb, x2 = xa < xb ? xb : xa, y1 = ya < yb ? ya : yb, y2 = ya < yb ? yb : ya;
+        auto put = [&](uint64_t x, uint64_t y) {
+            const uint64_t p = y * width_ + x;
+            if (p >= (uint64_t)width_ * height_) throw std::out_of_range("draw_line: pixel past the buffer");
+            std::memcpy(&buffer_[(size_t)p * 4], c.data(), 4);
+        };
+        if (x1 == x2 && y1 == y2) put(x1, y1);
+        else if (x1 == x2) for (uint64_t y = y1; y < y2; ++y) put(x1, y);
+        else if (y1 == y2) for (uint64_t x = x1; x < x2; ++x) put(x, y1);
+        else {
+            const uint64_t dx = x2 - x1, dy = y2 - y1;
+            uint64_t rem = 0;
+            if (dx > dy) {
+                uint64_t y = y1;
+                for (uint64_t x = x1; x < x2; ++x) { put(x, y); rem += dy; if (rem >= dx) { y += 1; rem -= dx; put(x, y); } }
+            } else {
+                uint64_t x = x1;
+                for (uint64_t y = y1; y < y2; ++y) { put(x, y); rem += dx; if (rem >= dy) { x += 1; rem -= dy; put(x, y); } }
+            }
+            put(x2, y2);
+        }
     }
 private:
     uint32_t width_, height_;
@@ -276,6 +303,9 @@ inline Model::Indexed Model::indexed_inputs() const
 }
 
 struct Mesh { int id = -1; uint64_t ntris = 0; int vs = 0; };
+struct Lines { int id = -1; uint64_t nlines = 0; };   // a list of draw_line calls on the device
+struct LineSegment { uint32_t x1, y1, x2, y2; };
+static_assert(sizeof(LineSegment) == 16, "LineSegment must be 4 packed u32");
 
 // Device-resident FrameBuffer + f32 depth buffer + u32 triangle-id buffer and the two halves of the
 // reference's draw loop as batched calls (`Renderer {}` itself is stateless in the reference, :41).
@@ -332,6 +362,28 @@ public:
         check(frr_mesh_bind_device_indexed(ctx_, dev_vertices, nverts, dev_indices, ntris, vs_id, &m.id));
         return m;
     }
+    // A list of FrameBuffer::draw_line calls (renderer.rs:540-588), in call order.  A segment whose walk would leave the
+    // buffer (the reference's panic) -> frr::Error naming it, and no list.
+    Lines upload_lines(const std::vector<LineSegment> &segments, const std::vector<std::array<uint8_t, 4>> &colors)
+    {
+        if (segments.size() != colors.size()) throw Error(FRR_ERR_INVALID, "one colour per segment");
+        Lines l; l.nlines = segments.size();
+        check(frr_lines_upload(ctx_, reinterpret_cast<const uint32_t *>(segments.data()), reinterpret_cast<const uint8_t *>(colors.data()), l.nlines, &l.id));
+        return l;
+    }
+    // the same for device memory the caller owns (segments 16-byte aligned); validated on the device inside the call
+    Lines bind_lines_device(const void *dev_xyxy, const void *dev_rgba, uint64_t nlines)
+    {
+        Lines l; l.nlines = nlines;
+        check(frr_lines_bind_device(ctx_, dev_xyxy, dev_rgba, nlines, &l.id));
+        return l;
+    }
+    void free_lines(Lines &l) { if (l.id >= 0) { check(frr_lines_free(ctx_, l.id)); l.id = -1; } }
+    // frame_buffer.draw_line(...) for every segment of the list, in order: colour only, ordered with the draws around it
+    void draw_lines(const Lines &l) { check(frr_draw_lines(ctx_, l.id)); }
+    // the edges of every triangle of the last geometry_processing / draw in one colour (an edge with an endpoint off the
+    // screen is skipped whole); no read-back
+    void draw_wireframe(const std::array<uint8_t, 4> &color) { check(frr_draw_wireframe(ctx_, color.data())); }
     void free_mesh(Mesh &m) { if (m.id >= 0) { check(frr_mesh_free(ctx_, m.id)); m.id = -1; } }
     void set_texture(int slot, const FrameBuffer &fb) { check(frr_texture_upload(ctx_, slot, fb.get_data().data(), fb.width(), fb.height())); }
     void set_uniforms() { check(frr_set_uniforms(ctx_, &uniforms)); }

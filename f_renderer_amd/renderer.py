@@ -5,6 +5,7 @@ Reference surface (Rust, /root/reference/f_renderer/src/renderer.rs):
   Renderer::rasterization(width_range, height_range, triangle, pixel_shader, ps_uniform,
                           frame_buffer, depth_buffer)                                  :269-284
   FrameBuffer::{new, fill, clear, get_size, get_data, set_pixel, get_pixel}            :418-514
+  FrameBuffer::draw_line                                                               :540-588
 and the matrix/camera helpers matrix_util.rs:3-35, camera.rs:4-26.
 
 The per-triangle, closure-taking calls become batched calls with table-selected shaders: same
@@ -99,6 +100,51 @@ class FrameBuffer:
     def get_pixel(self, x, y):
         return self.buffer[y, x].copy()
 
+    def _set_linear(self, x, y, color):
+        # set_pixel as draw_line reaches it (renderer.rs:497-503): offset (y*width + x)*4 with no test of x, so x >= width
+        # lands in a later row; past the buffer the reference panics
+        p = y * self.width + x
+        if p >= self.width * self.height:
+            raise IndexError(f"draw_line: pixel ({x}, {y}) is past the {self.width} x {self.height} buffer")
+        self.buffer.reshape(-1, 4)[p] = color
+
+    def draw_line(self, x1, y1, x2, y2, color):
+        """renderer.rs:540-588, statement by statement.  The endpoints are sorted per axis, independently (a falling line
+        is drawn as the rising one); vertical and horizontal lines exclude their upper end."""
+        color = np.asarray(color, np.uint8)
+        x1, y1, x2, y2 = int(x1), int(y1), int(x2), int(y2)
+        x1, x2 = (x1, x2) if x1 < x2 else (x2, x1)
+        y1, y2 = (y1, y2) if y1 < y2 else (y2, y1)
+        if x1 == x2 and y1 == y2:
+            self._set_linear(x1, y1, color)
+        elif x1 == x2:
+            for y in range(y1, y2):
+                self._set_linear(x1, y, color)
+        elif y1 == y2:
+            for x in range(x1, x2):
+                self._set_linear(x, y1, color)
+        else:
+            dx, dy, rem = x2 - x1, y2 - y1, 0
+            if dx > dy:
+                y = y1
+                for x in range(x1, x2):
+                    self._set_linear(x, y, color)
+                    rem += dy
+                    if rem >= dx:
+                        y += 1
+                        rem -= dx
+                        self._set_linear(x, y, color)
+            else:
+                x = x1
+                for y in range(y1, y2):
+                    self._set_linear(x, y, color)
+                    rem += dx
+                    if rem >= dy:
+                        x += 1
+                        rem -= dy
+                        self._set_linear(x, y, color)
+            self._set_linear(x2, y2, color)
+
 
 class Mesh:
     def __init__(self, renderer, mesh_id, ntris, vs_id, keepalive=None):
@@ -107,6 +153,18 @@ class Mesh:
     def free(self):
         if self.id is not None:
             self.renderer._check(N.lib().frr_mesh_free(self.renderer._ctx, self.id))
+            self.id = None
+
+
+class Lines:
+    """A list of draw_line calls on the device (Renderer.upload_lines / bind_lines_device)."""
+
+    def __init__(self, renderer, lines_id, nlines, keepalive=None):
+        self.renderer, self.id, self.nlines, self._keep = renderer, lines_id, nlines, keepalive
+
+    def free(self):
+        if self.id is not None:
+            self.renderer._check(N.lib().frr_lines_free(self.renderer._ctx, self.id))
             self.id = None
 
 
@@ -231,6 +289,23 @@ class Renderer:
         self._check(self._lib.frr_mesh_bind_device_indexed(self._ctx, C.c_void_p(vert_ptr), nverts, C.c_void_p(idx_ptr), ntris, vs_id, C.byref(mid)))
         return Mesh(self, mid.value, ntris, vs_id, keepalive)
 
+    def upload_lines(self, xyxy, rgba):
+        """A list of FrameBuffer::draw_line calls (renderer.rs:540-588) -> device.  xyxy: uint32 [n,4] = x1, y1, x2, y2;
+        rgba: uint8 [n,4], or one colour for all.  A segment that would panic in the reference (its walk leaves the
+        buffer) raises FrrError(FRR_ERR_INVALID) naming it, and nothing is uploaded."""
+        a = np.ascontiguousarray(xyxy, np.uint32).reshape(-1, 4)
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(rgba, np.uint8).reshape(-1, 4), (a.shape[0], 4)))
+        lid = C.c_int()
+        self._check(self._lib.frr_lines_upload(self._ctx, a.ctypes.data, c.ctypes.data, a.shape[0], C.byref(lid)))
+        return Lines(self, lid.value, a.shape[0])
+
+    def bind_lines_device(self, xyxy_ptr, rgba_ptr, nlines, keepalive=None):
+        """Same, for a list already in HBM (uint32 [n,4] and uint8 [n,4], e.g. two torch tensors' data_ptr()); validated on
+        the device inside this call (a host wait).  After an in-place rewrite: frame_fence, rewrite, bind again."""
+        lid = C.c_int()
+        self._check(self._lib.frr_lines_bind_device(self._ctx, C.c_void_p(xyxy_ptr), C.c_void_p(rgba_ptr), nlines, C.byref(lid)))
+        return Lines(self, lid.value, nlines, keepalive)
+
     def set_texture(self, slot, image):
         """PSUniform.sample_2d_* (phong.rs:43-45): FrameBuffer or uint8 [h,w,4]."""
         buf = image.buffer if isinstance(image, FrameBuffer) else np.ascontiguousarray(image, np.uint8)
@@ -319,6 +394,17 @@ class Renderer:
         hr = height_range or (0, self.height)
         self._check(self._lib.frr_draw(self._ctx, mesh.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
 
+    def draw_lines(self, lines):
+        """for each segment of the list, in order: frame_buffer.draw_line(x1, y1, x2, y2, color) on the colour target (depth
+        and triangle ids untouched), ordered with the draws around it like any of them."""
+        self._check(self._lib.frr_draw_lines(self._ctx, lines.id))
+
+    def draw_wireframe(self, color):
+        """The three edges of every triangle of the last geometry_processing (between their spi), one colour; an edge with
+        an endpoint off the screen is skipped whole.  No read-back, no host wait."""
+        c = np.ascontiguousarray(color, np.uint8).reshape(4)
+        self._check(self._lib.frr_draw_wireframe(self._ctx, c.ctypes.data))
+
     def frame_fence(self, stream=None):
         """`stream` (a hipStream_t handle, e.g. torch's stream.cuda_stream; None = the ctx's stream) waits for every frame
         issued so far -- no host wait (frr_frame_fence; option bound_targets_in_flight)."""
@@ -371,7 +457,7 @@ class Renderer:
         return float(ms.value)
 
     KERNELS = ("k_clear", "k_geom", "k_geom_scan", "k_bin_count",
-               "k_tile_scan", "k_bin_fill", "k_raster", "k_bin_seg")
+               "k_tile_scan", "k_bin_fill", "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint")
 
     def profile_enable(self, on=True, kernels=None, period=1):
         """Bracket launches with HIP events: all kernels (on=True), none (False) or the named ones; only every

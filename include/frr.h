@@ -5,8 +5,8 @@
  * The reference API is per-triangle and closure-based (Rust generics):
  *   Renderer::geometry_processing   /root/reference/f_renderer/src/renderer.rs:96-112
  *   Renderer::rasterization         /root/reference/f_renderer/src/renderer.rs:269-284
- *   FrameBuffer::{new,fill,clear,get_data,get_size,set_pixel,get_pixel,sample_2d}
- *                                   /root/reference/f_renderer/src/renderer.rs:418-538
+ *   FrameBuffer::{new,fill,clear,get_data,get_size,set_pixel,get_pixel,sample_2d,draw_line}
+ *                                   /root/reference/f_renderer/src/renderer.rs:418-588
  * driven by the two-pass draw loop   /root/reference/examples/src/bin/phong.rs:314-387.
  * Closures and generic varyings cannot cross an FFI to a GPU, so this ABI is batched at the
  * granularity of that draw loop and shaders are table-selected; varyings are a flat float[K]
@@ -277,6 +277,42 @@ int frr_raster(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int3
  * frr_readback_setup. */
 int frr_draw(frr_ctx *ctx, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
 
+/* ---- lines ------------------------------------------------------------------------------- */
+
+/* FrameBuffer::draw_line(x1, y1, x2, y2, color) (renderer.rs:540-588), the reference's only drawing primitive besides the
+ * triangle, for a whole list of calls at once.  Everything the reference does is reproduced: the endpoints are sorted per
+ * axis, independently (:541-542: a falling line is drawn as the rising one), a vertical or horizontal line excludes its upper
+ * end (:548, :553), every other line paints a second pixel in the column (row) where its minor coordinate steps and ends
+ * with (x2, y2) (:563-572, :575-584), and set_pixel addresses linearly with no test of x (:497-503): x >= width lands in a
+ * later row.
+ * A list is nlines x {x1, y1, x2, y2} u32 and nlines x RGBA8, in call order.  A segment for which the reference would panic
+ * -- the largest linear pixel index of its walk, computed in 64 bits, is >= width * height of the ctx -- makes the whole list
+ * FRR_ERR_INVALID: no list id, and frr_last_error names the first such segment.  frr_lines_upload checks on the host;
+ * frr_lines_bind_device (borrowed device memory, xyxy 16-byte and rgba 4-byte aligned) with one small kernel on the ctx's
+ * stream and a host wait inside the call.  nlines == 0 is valid; nlines < 2^31.  Rewriting a device-bound list in place
+ * follows the rule of frr_create for device-bound meshes: frr_frame_fence, rewrite, bind again -- and the new bind validates
+ * again.  (Should a list be rewritten WITHOUT a re-bind, the kernels still write only inside the colour target: a segment
+ * or a pixel that would leave it is dropped.  That is a guard for the machine, not a defined result.) */
+int frr_lines_upload(frr_ctx *ctx, const uint32_t *xyxy, const uint8_t *rgba, uint64_t nlines, int *lines_out);
+int frr_lines_bind_device(frr_ctx *ctx, const void *dev_xyxy, const void *dev_rgba, uint64_t nlines, int *lines_out);
+int frr_lines_free(frr_ctx *ctx, int lines);
+/* for k in 0..nlines: frame_buffer.draw_line(x1[k], y1[k], x2[k], y2[k], rgba[k]) on the ctx's colour target (row stride =
+ * the ctx's width).  Colour only: depth and triangle ids are untouched, and so is every field of frr_stats.  The call is
+ * ordered like any command that writes the targets -- behind the draws issued before it and before those issued after it: a
+ * later triangle draw overwrites a line pixel wherever its fragment passes the depth test, and nowhere else -- and where
+ * segments of the list meet, the later one's colour stays.  A pending frr_clear is settled first, as by a sub-window
+ * raster.  On a partitioned ctx a pixel is written only if this rank owns the tile row of its linear index
+ * ((index / width) / 32), so that the ranks' images stitch to the reference's like those of any draw. */
+int frr_draw_lines(frr_ctx *ctx, int lines);
+/* The edges (v0,v1), (v1,v2), (v2,v0) of every triangle of the last frr_geometry in one colour: segment 3t + e is edge e of
+ * setup triangle t, between the spi of its emission-order vertices (what frr_readback_setup returns).  The reference has no
+ * caller of draw_line to copy, so this rule is the library's own: an edge with an endpoint outside 0 <= x < width,
+ * 0 <= y < height is skipped whole.  The result is by definition that of frr_draw_lines on the list a host would build that
+ * way from frr_readback_setup -- without the read-back: the triangle count is taken from the device tables, and the call
+ * waits for nothing on the host.  It fails where frr_readback_setup fails (FRR_ERR_INVALID after a frr_draw that filtered
+ * the setup list on a partitioned ctx). */
+int frr_draw_wireframe(frr_ctx *ctx, const uint8_t rgba[4]);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to
@@ -342,6 +378,10 @@ int frr_event_elapsed_ms(frr_ctx *ctx, int a, int b, float *ms);
  *                             -1 (default): when the counters last read back (frr_sync, frr_readback, frr_get_stats)
  *                             showed a block with more than 16 clipped inputs
  *   "clear_eager"             1: frr_clear runs its own kernel at once instead of riding on the next full-window draw
+ *   "lines_chunk"             a test hook like bin_capacity: iterations one segment contributes to a round of its wavefront in the
+ *                             line kernels (0 = default 2^24, the bound that keeps a wavefront's prefix sums in 32 bits).  Only a
+ *                             segment nearly as long as a 2^24-pixel buffer takes a second round at the default; a small value
+ *                             lets the tests walk that path on a 96 x 70 frame
  *   "tile_order"              which workgroup of the tile kernel takes which tile (segmented binning): 0 (default) the fixed order
  *                             by position; 1 heaviest first -- each XCD's run of neighbouring tiles by descending records in the
  *                             latest pass over the same grid on the same workspace (the fixed order on a first pass, after a new
@@ -351,7 +391,7 @@ int frr_set_option(frr_ctx *ctx, const char *name, int64_t value);
 /* per-kernel accumulated device time (ms) and launch count since frr_profile_reset.  `mask`:
  * 0 = off, -1 = every kernel, else OR of (1 << index) with index in the order k_clear,
  * k_geom, k_geom_scan, k_bin_count, k_tile_scan, k_bin_fill, k_raster,
- * k_bin_seg (k_geom covers the clip kernel too when the clip queue is in use).  A profiled launch is bracketed by two
+ * k_bin_seg, k_lines_mark, k_lines_paint (k_geom covers the clip kernel too when the clip queue is in use).  A profiled launch is bracketed by two
  * HIP events on the ctx stream. */
 int frr_profile_enable(frr_ctx *ctx, int mask);
 /* bracket only every `period`-th launch of each selected kernel (default 1): an event pair costs the
@@ -373,6 +413,9 @@ void frr_set_perspective(float fovy, float aspect, float zn, float zf, float m[1
 int frr_debug_atan2f(frr_ctx *ctx, const float *y, const float *x, float *out, uint64_t n);
 /* the same source compiled for the host, to pin the port against glibc without a GPU */
 float frr_host_atan2f(float y, float x);
+/* the line kernels' per-iteration arithmetic compiled for the host (cf. frr_host_atan2f): the linear pixel indices
+ * y * width + x that draw_line(x1, y1, x2, y2) paints, in write order; returns their number (written up to cap) */
+int64_t frr_host_line_pixels(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2, uint32_t width, uint64_t *out, uint64_t cap);
 /* MVP x vertex contraction of a pos3/uv2/normal3 mesh with the current uniforms: clip xyzw per vertex
  * (ntris*3*4 floats) by the exact VALU form (use_mfma = 0, glam's association) or by
  * v_mfma_f32_16x16x4_f32 (use_mfma = 1, an fmaf chain: NOT bit-identical); *ms = kernel time. */
