@@ -3,6 +3,7 @@
 #include "frr_kernels.h"
 #include "frr_tile_order.h"
 #include "frr_lines.h"
+#include "frr_varyings.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -135,6 +136,12 @@ struct GeomSet {
     uint4 *pbox = nullptr; size_t pbox_cap = 0;
     uint32_t *bcount = nullptr; size_t bcount_cap = 0;          // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
     uint2 *clipq = nullptr; size_t clipq_cap = 0;               // [input triangles] the clip kernel's queue (GeomArgs::clipq)
+    // frr_resolve_varyings: emission index within the draw -> slot, one table per parity of the geometry pass (allocated by
+    // the first resolve of a pass on this set, at the set's setup capacity); vslot_stream: the stream of its latest user
+    uint32_t *vslot[2] = {nullptr, nullptr}; size_t vslot_cap[2] = {0, 0}; hipStream_t vslot_stream[2] = {nullptr, nullptr};
+    // the geometry pass (its sequence number, in which epoch) whose table the latest resolve built: a later resolve of the same
+    // pass skips k_vary_slots.  A replay starts a new epoch, so a table a cancelled launch never built is built by the replay.
+    uint32_t vslot_seq[2] = {0, 0}, vslot_epoch[2] = {0, 0};
     ReaderFence reader;
 };
 struct BinSet {
@@ -183,7 +190,7 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER, LINES } kind;
+    enum Kind { GEOM, RASTER, LINES, VARY } kind;
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -193,6 +200,8 @@ struct Cmd {
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
     // LINES: a list, or (lines < 0) the wireframe of the latest geometry pass in one colour
     int lines = -1; uint32_t wire_rgba = 0;
+    // VARY (frr_resolve_varyings): the window in x0 .. y1 and the caller's buffer
+    float *vary_out = nullptr;
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
@@ -1102,6 +1111,67 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_resolve_varyings: the interpolated varyings (renderer.rs:368-378) of every pixel of the window that a triangle of the
+// latest geometry pass owns, into the caller's buffer (frr_varyings.h).  On the targets' stream, ordered like a tile kernel
+// behind the pass's geometry; it reads the pass's tables on the device (no host wait), cannot fail there and owns no
+// device table, so a replay runs it again in its place -- behind a failed command it writes nothing (seq_cancelled).
+int exec_vary(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    int rc;
+    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass (a fan space that was too small is flagged here)
+    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    GeomSet &S = c->gset[f.gset];
+    const int par = f.gpar();
+    {
+        const uint32_t *const before = S.vslot[par];
+        if ((rc = ensure(c, S.vslot[par], S.vslot_cap[par], S.setup_cap)) != FRR_OK) return rc;
+        if (S.vslot[par] != before) S.vslot_seq[par] = 0;   // new memory: no table
+    }
+    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
+    hipStream_t ts = tstream_of(c);
+    // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
+    if (ts != c->stream) c->tstream[f.tset].dirty = c->tstream[f.tset].xdirty = true;
+    if (S.vslot_stream[par] && S.vslot_stream[par] != ts) {   // the table's previous resolve ran on another stream: after it
+        HIP_TRY(c, hipEventRecord(c->ev_join, S.vslot_stream[par]));
+        HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_join, 0));
+    }
+    S.vslot_stream[par] = ts;
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    VaryArgs a;
+    memset(&a, 0, sizeof a);
+    a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
+    a.K = frr_vs_num_varyings(f.geom_vs);
+    a.recs = S.recs; a.vary = S.vary; a.tinfo = S.tinfo; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix;
+    a.table = S.vslot[par];
+    a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.setup_cap, S.vslot_cap[par]), 0xFFFFFFFFu); a.fan_cap = f.geom_fan_cap;
+    a.ntris = (uint32_t)f.geom_ntris;
+    a.gpar = par; a.lane = f.lane;
+    a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
+    if (a.own.blocked) blocked_rows((int)((wh + TILE - 1) / TILE), f.rank, f.world, &a.own.brow0, &a.own.brow1);
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    a.tri_id = f.tri_id; a.out = cmd.vary_out;
+    if (S.vslot_seq[par] != f.geom_seq || S.vslot_epoch[par] != c->epoch) {   // (else: an earlier resolve of this pass built the table)
+        const uint32_t sgrid = (uint32_t)std::min<uint64_t>((f.geom_ntris + f.geom_fan_cap + VARY_WG - 1) / VARY_WG, 4096);
+        hipLaunchKernelGGL(k_vary_slots, dim3(std::max<uint32_t>(sgrid, 1u)), dim3(VARY_WG), 0, ts, a);
+        S.vslot_seq[par] = f.geom_seq; S.vslot_epoch[par] = c->epoch;
+    }
+    const dim3 grid((unsigned)((ww + VARY_WG - 1) / VARY_WG), (unsigned)wh), block(VARY_WG);
+    // 16-byte stores where every entry's address allows them: K a multiple of 4 and an aligned buffer
+    const bool vec = (a.K & 3) == 0 && (((uintptr_t)a.out | (uintptr_t)a.vary) & 15u) == 0u;
+    if (a.K == 3) hipLaunchKernelGGL((k_vary_resolve<3, false>), grid, block, 0, ts, a);
+    else if (a.K == 8 && vec) hipLaunchKernelGGL((k_vary_resolve<8, true>), grid, block, 0, ts, a);
+    else if (a.K == 8) hipLaunchKernelGGL((k_vary_resolve<8, false>), grid, block, 0, ts, a);
+    else if (vec) hipLaunchKernelGGL((k_vary_resolve<0, true>), grid, block, 0, ts, a);   // user shaders: K at run time
+    else hipLaunchKernelGGL((k_vary_resolve<0, false>), grid, block, 0, ts, a);
+    HIP_TRY(c, hipGetLastError());
+    // like a wireframe it reads the pass's fan cursors, which the next pass in this lane zeroes, and its workspace
+    ReaderFence &wr = c->wire_reader[f.lane];
+    wr.pending = true; wr.stream = ts; wr.recorded = false;
+    cmd.par = par; cmd.set = f.gset; cmd.lane = f.lane;
+    return FRR_OK;
+}
+
 int finish(frr_ctx *c);
 
 // run a command and remember it (finish() replays the commands from a failed one onwards)
@@ -1110,7 +1180,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : exec_lines(c, cmd);
+    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : exec_vary(c, cmd);
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1178,10 +1248,10 @@ int finish(frr_ctx *c)
         // the device tables as they were before the failed command: it has used its own parity's cursors (and, when its
         // block sums were scanned inside the next raster pass's binning launch, that pass has reserved bin space)
         h.first_bad = SEQ_NONE; h.overflow = 0u;
-        // (line commands in between own no table: the "next" command is the next geometry or raster pass)
+        // (line and varyings commands in between own no table: the "next" command is the next geometry or raster pass)
         for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
-            if (m.kind == Cmd::LINES) continue;
+            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY) continue;
             ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
@@ -1328,7 +1398,7 @@ void frr_destroy(frr_ctx *c)
     std::vector<void *> ptrs = {c->own_color[0], c->own_depth[0], c->own_tri_id[0], c->own_color[1], c->own_depth[1], c->own_tri_id[1],
                                 c->cnt, c->tile_counts, c->tile_offsets, c->tile_cursor};
     for (GeomSet &S : c->gset) for (void *p : {(void *)S.block_sums, (void *)S.block_prefix, (void *)S.tinfo, (void *)S.fanbase, (void *)S.fan_okey, (void *)S.recs,
-                                               (void *)S.vary, (void *)S.pbox, (void *)S.bcount, (void *)S.clipq}) ptrs.push_back(p);
+                                               (void *)S.vary, (void *)S.pbox, (void *)S.bcount, (void *)S.clipq, (void *)S.vslot[0], (void *)S.vslot[1]}) ptrs.push_back(p);
     for (BinSet &B : c->bset) for (void *p : {(void *)B.bins, (void *)B.bins2, (void *)B.bin_matrix, (void *)B.tile_cost, (void *)B.tile_perm}) ptrs.push_back(p);
     for (void *p : ptrs) if (p) (void)hipFree(p);
 #ifdef FRR_DEBUG_COUNTERS
@@ -2024,6 +2094,73 @@ int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uin
             }
         }
     }
+    return FRR_OK;
+}
+
+// argument checks of frr_resolve_varyings / frr_readback_varyings; *K: varyings per vertex, *nothing: valid, writes nothing
+static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries, int *K, bool *nothing)
+{
+    if (!c) return FRR_ERR_INVALID;
+    const FrameState &f = c->fs;
+    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
+    if (x1 <= x0 || y1 <= y0) return fail(c, FRR_ERR_INVALID, "empty or inverted window");
+    if (x0 < 0) return fail(c, FRR_ERR_UNSUPPORTED, "x0 < 0: pixels of neighbouring rows share depth entries, an entry has no single pixel");
+    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
+    if (ww > (int64_t)c->W || wh > (int64_t)c->H) return fail(c, FRR_ERR_INVALID, "window larger than the FrameBuffer");
+    if (y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_INVALID, "window coordinates outside the i16 range");
+    if ((wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H)
+        return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
+    if (f.geom_filter.active)
+        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry (unfiltered) and frr_raster before frr_resolve_varyings");
+    if (!buf || ((uintptr_t)buf & 3u)) return fail(c, FRR_ERR_INVALID, "output buffer is NULL or not 4-byte aligned");
+    if (out_entries < (uint64_t)wh * (uint64_t)x1) return fail(c, FRR_ERR_INVALID, "out_entries < (y1 - y0) * x1");
+    *K = frr_vs_num_varyings(f.geom_vs);
+    *nothing = *K <= 0 || f.geom_ntris == 0;   // (geom_ntris == 0: an empty mesh, or frr_clear since -- the setup list is gone)
+    return FRR_OK;
+}
+
+int frr_geometry_num_varyings(const frr_ctx *c)
+{
+    if (!c || c->fs.geom_vs < 0) return FRR_ERR_INVALID;
+    return frr_vs_num_varyings(c->fs.geom_vs);
+}
+
+int frr_resolve_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_f32, uint64_t out_entries)
+{
+    int K = 0; bool nothing = false;
+    const int rc = vary_check(c, x0, x1, y0, y1, dev_out_f32, out_entries, &K, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Cmd cmd;
+    cmd.kind = Cmd::VARY; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.vary_out = (float *)dev_out_f32; cmd.duni = c->duni;
+    return exec_cmd(c, cmd);
+}
+
+int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, float *host_inout, uint64_t out_entries)
+{
+    int K = 0; bool nothing = false;
+    int rc = vary_check(c, x0, x1, y0, y1, host_inout, out_entries, &K, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a temporary device buffer that starts as the caller's: what the command leaves untouched comes back as it went in
+    const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
+    const size_t bytes = (size_t)entries * (size_t)K * sizeof(float);
+    float *tmp = nullptr;
+    if (hipMalloc((void **)&tmp, bytes) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc varyings buffer");
+    hipError_t e = hipMemcpy(tmp, host_inout, bytes, hipMemcpyHostToDevice);   // (returns when the copy is done: in front of the command on any stream)
+    if (e == hipSuccess) {
+        Cmd cmd;
+        cmd.kind = Cmd::VARY; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.vary_out = tmp; cmd.duni = c->duni;
+        rc = exec_cmd(c, cmd);
+        const int rf = finish(c);   // synchronisation point (and, if a list was too small, the replay -- the command included); the log is empty afterwards
+        if (rc == FRR_OK) rc = rf;
+        if (rc == FRR_OK) e = hipMemcpy(host_inout, tmp, bytes, hipMemcpyDeviceToHost);
+        // (a finish() that failed may have left the command in the log: nothing may replay it into the freed buffer)
+        for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == Cmd::VARY && c->log[k].vary_out == tmp) c->log.erase(c->log.begin() + (ptrdiff_t)k);
+    }
+    (void)hipFree(tmp);
+    if (rc != FRR_OK) return rc;
+    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy varyings: ") + hipGetErrorString(e));
     return FRR_OK;
 }
 

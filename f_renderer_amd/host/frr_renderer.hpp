@@ -430,6 +430,29 @@ public:
     }
     void read_depth(std::vector<float> &depth) { depth.resize((size_t)width_ * height_); check(frr_readback(ctx_, nullptr, depth.data(), nullptr)); }
     void read_triangle_ids(std::vector<uint32_t> &ids) { ids.resize((size_t)width_ * height_); check(frr_readback(ctx_, nullptr, nullptr, ids.data())); }
+    // The pixel shader's input (renderer.rs:368-378) of every pixel of the window that a triangle of the last
+    // geometry_processing / draw owns, f32 [entries][K] with entry (cy - y0) * x1 + (cx - x0); every other entry is left
+    // untouched (include/frr.h: frr_resolve_varyings).  Device memory, no host wait: order the reads with frame_fence on a
+    // created stream (nullptr / the legacy default stream means the renderer's own) or with sync.
+    void resolve_varyings(void *dev_out_f32, uint64_t entries, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        check(frr_resolve_varyings(ctx_, width_range.first, width_range.second, height_range.first, height_range.second, dev_out_f32, entries));
+    }
+    void resolve_varyings(void *dev_out_f32, uint64_t entries) { resolve_varyings(dev_out_f32, entries, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // the same on the host: `out` is resized to (y1 - y0) * x1 * K floats (new elements = fill, existing ones are kept: they are
+    // what entries nobody owns hold afterwards); returns K, the varyings of the last geometry_processing / draw
+    int readback_varyings(std::vector<float> &out, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range, float fill = 0.0f)
+    {
+        const int num_varyings = frr_geometry_num_varyings(ctx_);   // the library's own K: the copy-back never passes `out`
+        if (num_varyings < 0) throw Error(FRR_ERR_INVALID, "readback_varyings before geometry_processing");
+        const int64_t rows = (int64_t)height_range.second - height_range.first;
+        const uint64_t entries = rows > 0 && width_range.second > 0 ? (uint64_t)rows * (uint64_t)width_range.second : 0;
+        out.resize((size_t)entries * (size_t)(num_varyings > 0 ? num_varyings : 0), fill);
+        float none = fill;
+        check(frr_readback_varyings(ctx_, width_range.first, width_range.second, height_range.first, height_range.second, out.empty() ? &none : out.data(), entries));
+        return num_varyings > 0 ? num_varyings : 0;
+    }
+    int readback_varyings(std::vector<float> &out, float fill = 0.0f) { return readback_varyings(out, {0, (int32_t)width_}, {0, (int32_t)height_}, fill); }
     frr_stats stats() { frr_stats s; check(frr_get_stats(ctx_, &s)); return s; }
     frr_ctx *raw() { return ctx_; }
 

@@ -405,6 +405,31 @@ class Renderer:
         c = np.ascontiguousarray(color, np.uint8).reshape(4)
         self._check(self._lib.frr_draw_wireframe(self._ctx, c.ctypes.data))
 
+    def resolve_varyings(self, out_ptr, entries, width_range=None, height_range=None):
+        """The pixel shader's input (renderer.rs:368-378) of every pixel of the window that a triangle of the last
+        geometry_processing owns, into device memory: float32 [entries][K] at `out_ptr` (e.g. a torch tensor's data_ptr()),
+        entry (cy - y0) * x1 + (cx - x0); every other entry is left untouched.  No host wait: order the reads with
+        frame_fence(stream) or sync() (frr_resolve_varyings).  `stream` has to be a created stream (torch.cuda.Stream()):
+        handle 0 -- torch's default stream -- means the renderer's own stream to frame_fence and fences nothing for the caller."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        self._check(self._lib.frr_resolve_varyings(self._ctx, int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), C.c_void_p(out_ptr or 0), int(entries)))
+
+    def readback_varyings(self, width_range=None, height_range=None, fill=np.nan):
+        """The same on the host: float32 [(y1 - y0) * x1, K], `fill` (a scalar, or an array of that shape) where no triangle
+        of the last geometry_processing owns the entry (frr_readback_varyings)."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        k = self._lib.frr_geometry_num_varyings(self._ctx)   # the library's own K: the copy-back can never pass the array
+        if k < 0:
+            raise FrrError(N.FRR_ERR_INVALID, "readback_varyings before geometry_processing")
+        entries = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
+        out = np.empty((entries, k), np.float32)
+        out[...] = fill
+        buf = out if out.size else np.zeros(1, np.float32)   # (nothing to write: the call still checks its arguments)
+        self._check(self._lib.frr_readback_varyings(self._ctx, int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), buf.ctypes.data, entries))
+        return out
+
     def frame_fence(self, stream=None):
         """`stream` (a hipStream_t handle, e.g. torch's stream.cuda_stream; None = the ctx's stream) waits for every frame
         issued so far -- no host wait (frr_frame_fence; option bound_targets_in_flight)."""

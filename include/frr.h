@@ -313,6 +313,48 @@ int frr_draw_lines(frr_ctx *ctx, int lines);
  * the setup list on a partitioned ctx). */
 int frr_draw_wireframe(frr_ctx *ctx, const uint8_t rgba[4]);
 
+/* ---- the pixel shader's input as a buffer (deferred shading) -------------------------------- */
+/* The ShaderContext the reference hands to the pixel shader -- `input` of renderer.rs:368-378, the perspective-correct
+ * interpolation of the winning triangle's varyings -- for every pixel of a window, pixel-major f32 [entries][K].
+ *   K       the varyings of the latest frr_geometry / frr_draw, frr_vs_num_varyings of its vs_id (user shaders included, up
+ *           to FRR_MAX_VARYINGS).
+ *   window  (x0, x1) x (y0, y1): the one the raster passes of that geometry used.  Pixel (cx, cy) has the depth index
+ *           i = (cy - y0) * x1 + (cx - x0) (renderer.rs:362).
+ * Where the triangle-id target at i names a triangle of the latest geometry pass (tri_base <= id < tri_base + its triangle
+ * count), out[i * K + k], k < K, becomes i0 * c0 + i1 * c1 + i2 * c2 of renderer.rs:374-378 for that triangle at that
+ * pixel, from the barycentrics of :343-360 and w, c0, c1, c2 of :368-372 -- the arithmetic and association of the tile
+ * kernel's resolve (1 / (rhw != 0 ? rhw : 1), r * a * w, no contraction), so the value is the very one the built-in and user
+ * pixel shaders receive.  EVERY OTHER ENTRY OF out IS LEFT UNTOUCHED: a frame of several draws composes -- called after each
+ * draw, the buffer ends with every pixel holding the varyings of its final owner (K may differ between the draws only if
+ * the caller keeps a buffer per K).  Which pixel shader the raster pass ran does not matter: after a FRR_PS_DEPTH draw the
+ * result is the same.
+ * frr_resolve_varyings: dev_out_f32 is device memory, 4-byte aligned, of out_entries * K floats; rows whose addresses allow
+ * it leave as 16-byte stores.  It is a command like a wireframe: it runs on the current frame's stream behind the draws
+ * issued so far and before those issued after it, settles a pending frr_clear first (as a sub-window raster does), reads the
+ * current frame's target set (own or caller-bound) and the geometry pass's tables on the device, and waits for nothing on
+ * the host.  The caller orders its reads of dev_out_f32 with frr_frame_fence or frr_sync, as for bound targets -- with
+ * frr_frame_fence on a stream of its own: a NULL stream there means the ctx's stream, so the legacy default stream (handle
+ * 0, what torch uses unless told otherwise) cannot be fenced; read on a created stream, or after frr_sync.  Behind a
+ * command that found a work list too small it writes nothing and is replayed with that command -- so dev_out_f32 stays
+ * allocated until the next synchronisation point or frr_clear, like a bound target.  frr_clear forgets the commands
+ * logged so far: a resolve that was cancelled by a failure the host has not seen by then is not replayed (the frame's
+ * targets are overwritten by the clear, the caller's buffer keeps what it held).  A draw verifies itself before it returns
+ * (frr_frame_fence), so a resolve issued after the frr_raster / frr_draw of its geometry pass is never cancelled; one issued
+ * between frr_geometry and frr_raster is guaranteed only once a synchronisation point has passed before the next
+ * frr_clear.  On a partitioned ctx only the pixels
+ * of the window's tile rows this rank owns are written.
+ * frr_readback_varyings: the same into host memory -- a temporary device buffer starts as a copy of host_inout, the
+ * command runs, and after a synchronisation point the buffer is copied back: "untouched" holds on the host too.
+ * Errors.  FRR_ERR_INVALID: out_entries < (y1 - y0) * x1; x1 <= x0, y1 <= y0 or a window beyond what frr_raster accepts;
+ * a NULL or misaligned buffer; a call before any frr_geometry; a setup list filtered by frr_draw on a partitioned ctx (where
+ * frr_draw_wireframe and frr_readback_setup fail: use frr_geometry + frr_raster).  FRR_ERR_UNSUPPORTED: x0 < 0 -- pixels of
+ * neighbouring rows share depth entries there, so an entry has no single pixel.  K == 0, an empty mesh, or a frr_clear since
+ * the geometry pass: FRR_OK, nothing written. */
+/* K of the latest frr_geometry / frr_draw (what sizes the buffers above); FRR_ERR_INVALID before any geometry pass */
+int frr_geometry_num_varyings(const frr_ctx *ctx);
+int frr_resolve_varyings(frr_ctx *ctx, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_f32, uint64_t out_entries);
+int frr_readback_varyings(frr_ctx *ctx, int32_t x0, int32_t x1, int32_t y0, int32_t y1, float *host_inout, uint64_t out_entries);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to
