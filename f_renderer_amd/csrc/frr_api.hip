@@ -4,6 +4,7 @@
 #include "frr_tile_order.h"
 #include "frr_lines.h"
 #include "frr_varyings.h"
+#include "frr_own.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -15,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // The text of the device headers, for frr_shader_register (hiprtc compiles user shaders into the library's own kernels):
@@ -43,26 +45,36 @@ const char *const kKernelNames[KID_COUNT] = {"k_clear", "k_geom", "k_geom_scan",
                                              "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint"};
 
 struct Mesh {
+    DevBuf<float> own_dev; DevBuf<uint32_t> own_idx;   // a host upload: the library's copies (dev / idx point at them); else empty, and dev AND idx are the caller's
     const float *dev = nullptr;    // [ntris][3][NF], or with idx: the vertex array [nverts][NF]
     const uint32_t *idx = nullptr; // indexed mesh (frr_mesh_upload_indexed): [ntris][3] vertex numbers, all < nverts when registered
-    uint64_t nverts = 0;
-    bool owned = false, used = false;   // owned: dev AND idx are the library's allocations (a host upload); else both are the caller's
-    uint64_t ntris = 0;
+    uint64_t nverts = 0, ntris = 0;
+    bool used = false;
     int vs = 0;
     uint64_t gen = 0;   // which registration of the ctx this is (DrawSig: a later mesh may live at a freed one's address)
 };
 struct Texture {
-    uint8_t *dev = nullptr;
+    DevBuf<uint8_t> dev;
     uint32_t w = 0, h = 0;
 };
 // a list of draw_line calls (frr_lines_upload / frr_lines_bind_device): every segment's walk stays inside the buffer
 struct Lines {
+    DevBuf<uint4> own_xyxy; DevBuf<uint32_t> own_rgba;   // a host upload: the library's copies; else empty
     const uint4 *xyxy = nullptr;     // [n] {x1, y1, x2, y2}
     const uint32_t *rgba = nullptr;  // [n]
     uint64_t n = 0;
-    bool owned = false, used = false;
+    bool used = false;
 };
-struct ProfRec { int kid; hipEvent_t a, b; };
+// slot tables (frr_ctx::meshes, lines): a record goes into the first unused slot, or behind the last; its index is its id
+template <typename R> int slot_put(std::vector<R> &v, R &&r)
+{
+    size_t i = 0;
+    while (i < v.size() && v[i].used) ++i;
+    if (i < v.size()) v[i] = std::move(r); else v.push_back(std::move(r));
+    return (int)i;
+}
+template <typename R> bool slot_ok(const std::vector<R> &v, int id) { return id >= 0 && id < (int)v.size() && v[(size_t)id].used; }
+struct ProfRec { int kid; Event a, b; };
 
 // ---- user shaders (frr_shader_register): a per-process registry of code objects, loaded per ctx on first use ---------
 constexpr int kSpanShapes[6][2] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIGHT_NW, 6}};   // the shapes launch_raster knows
@@ -110,14 +122,14 @@ struct UserModule {
 // One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
 struct FrameStream {
     hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;   // joins it into a caller's stream (fence_stream)
+    Event ev;                  // joins it into a caller's stream (fence_stream)
     bool dirty = false;        // it holds work `stream` has not waited for
     bool xdirty = false;       // ... that the stream of the latest frr_frame_fence (frr_ctx::xfence) has not waited for
     uint32_t joined = 0;       // the join_epoch in which it last waited for `stream` (gstream_join)
 };
 // The tile kernel that last read a workspace set: the second stream waits for it before it overwrites the set.
 struct ReaderFence {
-    hipEvent_t ev = nullptr; bool pending = false; // fires when the latest tile kernel that reads this set is done
+    Event ev; bool pending = false;                // fires when the latest tile kernel that reads this set is done
     hipStream_t stream = nullptr;                  // ... on this stream
     bool recorded = false;                         // the event was recorded right behind that kernel
 };
@@ -126,30 +138,30 @@ struct ReaderFence {
 // that the geometry + binning kernels of pass n + 1 can run on the ctx's second stream while the tile kernel of pass n
 // still reads what pass n left (frr_device.h: GeomTab / BinTab are the device-side halves of the same scheme).
 struct GeomSet {
-    uint32_t *block_sums = nullptr; size_t block_sums_cap = 0; // per 256-triangle block: triangles emitted
-    uint32_t *block_prefix = nullptr; size_t block_prefix_cap = 0; // ... and their exclusive scan
-    uint32_t *tinfo = nullptr; size_t tinfo_cap = 0;           // per input: fan size | emission offset in its block
-    uint32_t *fanbase = nullptr; size_t fanbase_cap = 0;       // per clipped input: first fan slot
-    uint32_t *fan_okey = nullptr; size_t fan_okey_cap = 0;     // per fan slot: order key within the draw
-    RasterRec *recs = nullptr; size_t setup_cap = 0;            // [input triangles + fan capacity]
-    float *vary = nullptr; size_t vary_cap = 0;                 // floats
-    uint4 *pbox = nullptr; size_t pbox_cap = 0;
-    uint32_t *bcount = nullptr; size_t bcount_cap = 0;          // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
-    uint2 *clipq = nullptr; size_t clipq_cap = 0;               // [input triangles] the clip kernel's queue (GeomArgs::clipq)
+    DevBuf<uint32_t> block_sums;     // per 256-triangle block: triangles emitted
+    DevBuf<uint32_t> block_prefix;   // ... and their exclusive scan
+    DevBuf<uint32_t> tinfo;          // per input: fan size | emission offset in its block
+    DevBuf<uint32_t> fanbase;        // per clipped input: first fan slot
+    DevBuf<uint32_t> fan_okey;       // per fan slot: order key within the draw
+    DevBuf<RasterRec> recs;          // [input triangles + fan capacity]: the setup capacity, recs.cap()
+    DevBuf<float> vary;              // floats
+    DevBuf<uint4> pbox;              // [recs.cap()]
+    DevBuf<uint32_t> bcount;         // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
+    DevBuf<uint2> clipq;             // [input triangles] the clip kernel's queue (GeomArgs::clipq)
     // frr_resolve_varyings: emission index within the draw -> slot, one table per parity of the geometry pass (allocated by
     // the first resolve of a pass on this set, at the set's setup capacity); vslot_stream: the stream of its latest user
-    uint32_t *vslot[2] = {nullptr, nullptr}; size_t vslot_cap[2] = {0, 0}; hipStream_t vslot_stream[2] = {nullptr, nullptr};
+    DevBuf<uint32_t> vslot[2]; hipStream_t vslot_stream[2] = {nullptr, nullptr};
     // the geometry pass (its sequence number, in which epoch) whose table the latest resolve built: a later resolve of the same
     // pass skips k_vary_slots.  A replay starts a new epoch, so a table a cancelled launch never built is built by the replay.
     uint32_t vslot_seq[2] = {0, 0}, vslot_epoch[2] = {0, 0};
     ReaderFence reader;
 };
 struct BinSet {
-    uint4 *bins = nullptr; size_t bin_cap = 0;   // 16-byte cull records, one per (triangle, tile) pair
-    uint4 *bins2 = nullptr; size_t bin2_cap = 0; // the same in near-first order per tile (tile kernel pre-pass)
-    uint32_t *bin_matrix = nullptr; size_t bin_matrix_cap = 0; // [G][ntiles] per-chunk tile histograms
-    uint32_t *tile_cost = nullptr; size_t tile_cost_cap = 0;   // [ntiles] records per tile of the latest tile kernel on this set
-    uint32_t *tile_perm = nullptr; size_t tile_perm_cap = 0;   // [ntiles] block -> tile order of the current pass (option tile_order)
+    DevBuf<uint4> bins;            // 16-byte cull records, one per (triangle, tile) pair
+    DevBuf<uint4> bins2;           // the same in near-first order per tile (tile kernel pre-pass)
+    DevBuf<uint32_t> bin_matrix;   // [G][ntiles] per-chunk tile histograms
+    DevBuf<uint32_t> tile_cost;    // [ntiles] records per tile of the latest tile kernel on this set
+    DevBuf<uint32_t> tile_perm;    // [ntiles] block -> tile order of the current pass (option tile_order)
     bool cost_known = false; TileOrderKey cost_key = {};       // tile_cost was written by a pass with this key (frr_tile_order.h)
     ReaderFence reader;
 };
@@ -217,6 +229,7 @@ struct DrawSig {
     const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
     int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset;
 };
+static_assert(std::is_trivially_copyable<FrameState>::value && std::is_trivially_copyable<Cmd>::value, "the replay copies them: views only, no owner");
 inline bool same_sig(const DrawSig &a, const DrawSig &b) { return memcmp(&a, &b, sizeof a) == 0; }
 inline uint64_t fnv1a(const void *p, size_t n, uint64_t h = 1469598103934665603ull)
 {
@@ -239,7 +252,7 @@ struct frr_ctx {
     // of frame n's (2,040 tiles on 1,536 workgroup slots end with a third of the chip idle).  Nobody can look at own targets
     // except through this library (frr_readback, frr_target_ptrs, which join the streams first), so the only visible
     // change is that frr_target_ptrs' pointers are those of the CURRENT frame.  Caller-bound targets: one set, one stream.
-    uint8_t *own_color[2] = {}; float *own_depth[2] = {}; uint32_t *own_tri_id[2] = {};
+    DevBuf<uint8_t> own_color[2]; DevBuf<float> own_depth[2]; DevBuf<uint32_t> own_tri_id[2];
     // The private frame streams, by target set index (tstream_of).  [1]: everything of the frames that use own target set 1
     // (or, option bound_targets_in_flight, of every other frame); [0], option bound_targets_in_flight: the frames in between
     // (the caller's stream then carries no frame work at all).  [1] is acquired first (frr_clear), and calls that go over
@@ -249,13 +262,13 @@ struct frr_ctx {
     bool bound_in_flight = false;    // option bound_targets_in_flight: frames on caller-bound targets alternate between the two private streams too;
                                      // the caller binds another target set for each of two consecutive frames and fences its reads (frr_frame_fence)
     int frames_in_flight = 2;        // option frames_in_flight (1: one target set, everything on the caller's stream)
-    Counters *cnt = nullptr;
+    DevBuf<Counters> cnt;
     FrameState fs;
     GeomSet gset[2];
     BinSet bset[2];
     // cross-stream ordering: every workspace set has an event that fires when the latest tile kernel reading it is done (the second
     // stream waits for it before it overwrites a workspace that kernel reads), ev_bin[k & 3] when binning k is done
-    hipEvent_t ev_bin[4] = {}, ev_join = nullptr;
+    Event ev_bin[4], ev_join;
     uint64_t bin_serial = 0;
     // inputs the caller wrote on `stream` (a device-bound mesh) must be visible to the ctx's private streams: every bind
     // starts a new epoch, and a private stream waits for `stream` once per epoch before its next geometry pass
@@ -266,7 +279,7 @@ struct frr_ctx {
     uint32_t replays = 0;           // replays since frr_clear (frr_stats.replays)
     bool in_replay = false;
     Counters hc;                    // host copy of the device counters as of the latest finish()
-    uint32_t *host_bad = nullptr;   // host-visible word the device writes a failed command's number to (Counters::host_bad)
+    uint32_t *host_bad = nullptr;   // host-visible word the device writes a failed command's number to (Counters::host_bad); hipHostMalloc, freed by frr_destroy
     uint32_t seen_bad = SEQ_NONE;   // its value when the host last looked
     // A draw cannot fail, whoever consumes its targets and however (stream order, frr_frame_fence, frr_sync): a raster pass whose
     // need of the work lists is not known to fit -- no pass with the same DrawSig has completed on the current lists -- is
@@ -276,20 +289,20 @@ struct frr_ctx {
     uint64_t mesh_gen = 0;          // meshes registered so far (Mesh::gen)
     uint64_t tex_epoch = 0;         // frr_texture_upload calls so far (DrawSig: a user VS may sample a texture)
     uint64_t sync_epoch = 0;        // frr_sync calls so far (DrawSig of a device-bound mesh: rewritten in place behind one?)
-    hipEvent_t ev_verify = nullptr;
+    Event ev_verify;
     bool verify_pending = false;
     DrawSig verify_sig;
     // own targets handed out (frr_target_ptrs / frr_frame_fence): the frame that next renders into that set waits for what
     // the stream they were handed to holds by then (the caller's reads), see frr_clear
     bool exported[2] = {false, false};
     hipStream_t export_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_export = nullptr;
+    Event ev_export;
     // frr_frame_wait: one event per stream handed in (recorded on it), pending until a target write issued after the latest
     // frr_frame_wait consumes them; every target write until then -- a deferred clear of an earlier frame or binding too --
     // waits for all of them.  Events are reused (wait_pool).
-    struct FrameWait { hipStream_t stream; hipEvent_t ev; };
+    struct FrameWait { hipStream_t stream; Event ev; };
     std::vector<FrameWait> waits;
-    std::vector<hipEvent_t> wait_pool;
+    std::vector<Event> wait_pool;
     uint32_t wait_serial = 0;       // frr_frame_wait calls so far
     size_t fan_hint = 0;       // fan capacity asked for by a draw that overflowed
     int bin_g = 0;             // option bin_chunks: override the number of binning chunks (dev)
@@ -301,7 +314,7 @@ struct frr_ctx {
     int clip_queue = -1;        // option clip_queue: 1 use the queue + k_geom_clip, 0 never, -1 when the latest counters read back
     bool clip_queue_auto = false; //   showed a block with more than CLIP_QUEUE_AT clipped inputs (results are the same either way)
     // binning workspace of the CSR fallback (one set: that path does not overlap)
-    uint32_t *tile_counts = nullptr, *tile_offsets = nullptr, *tile_cursor = nullptr;
+    DevBuf<uint32_t> tile_counts, tile_offsets, tile_cursor;
     uint32_t max_tiles = 0;
     bool lds_attr_set = false;
     std::vector<Mesh> meshes;
@@ -309,7 +322,7 @@ struct frr_ctx {
     // draw_line order is resolved per pixel on a u32 plane of W * H (frr_lines.h), all-zero between commands: one per stream
     // that can carry target writes -- [0] `stream`, [1] / [2] the frame streams tstream[0] / tstream[1] -- because the line
     // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
-    uint32_t *line_owner[3] = {};
+    DevBuf<uint32_t> line_owner[3];
     uint32_t lines_chunk = 0;       // option lines_chunk (0: LINES_CHUNK)
     // per lane of device tables: the latest wireframe reads its geometry pass's fan cursors, which the next pass IN THAT LANE
     // zeroes (geom_bookkeeping), whatever workspace set it writes; the other lane's frame shares nothing with it
@@ -325,13 +338,13 @@ struct frr_ctx {
     int tile_order = TILE_ORDER_FIXED;   // option tile_order: which block of the tile kernel takes which tile (frr_tile_order.h)
     uint64_t ordered_passes = 0;   // raster passes whose tile kernel took a built order (frr_tile_order_passes)
 #ifdef FRR_DEBUG_COUNTERS
-    unsigned long long *dbg_tiles = nullptr; // FRR_DEBUG_TILES: per-tile timeline of the latest tile kernel
+    DevBuf<unsigned long long> dbg_tiles;    // FRR_DEBUG_TILES: per-tile timeline of the latest tile kernel
 #endif
-    hipEvent_t ev[16] = {};
+    Event ev[16];             // frr_event_record (timing events)
     bool ev_set[16] = {};
     uint32_t prof_mask = 0;   // bit per KernelId
     std::vector<ProfRec> prof_pending;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;      // timing events of the profile, between uses
     uint32_t prof_period = 1;         // bracket only every prof_period-th launch of a kernel (frr_profile_set_period)
     uint32_t prof_seen[KID_COUNT] = {};
     double prof_ms[KID_COUNT] = {};
@@ -352,7 +365,8 @@ int fail(frr_ctx *c, int code, const std::string &msg)
         if (e_ != hipSuccess)                                                                               \
             return fail(c, FRR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
     } while (0)
-
+int hip_rc(frr_ctx *c, hipError_t e) { return e == hipSuccess ? FRR_OK : fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
+int nomem(frr_ctx *c, const char *what) { return fail(c, FRR_ERR_NOMEM, std::string("out of device memory: ") + what + ": " + hipGetErrorString(hipPeekAtLastError())); }
 
 bool own_targets(const frr_ctx *c)
 {
@@ -376,13 +390,11 @@ bool multi_stream(const frr_ctx *c) { return c->g_used || c->tstream[0].st || c-
 // the ctx's own target set t (the second one is allocated on first use)
 int ensure_own_set(frr_ctx *c, int t)
 {
-    if (c->own_color[t] && c->own_depth[t] && c->own_tri_id[t]) return FRR_OK;
     const size_t npx = (size_t)c->W * c->H;
-    const bool ok = (c->own_color[t] || hipMalloc((void **)&c->own_color[t], npx * 4) == hipSuccess) &&
-                    (c->own_depth[t] || hipMalloc((void **)&c->own_depth[t], npx * 4) == hipSuccess) &&
-                    (c->own_tri_id[t] || hipMalloc((void **)&c->own_tri_id[t], npx * 4) == hipSuccess);
-    if (!ok) return fail(c, FRR_ERR_NOMEM, "second target set");
-    return FRR_OK;
+    const bool ok = (c->own_color[t] || c->own_color[t].reset(npx * 4) == hipSuccess) &&
+                    (c->own_depth[t] || c->own_depth[t].reset(npx) == hipSuccess) &&
+                    (c->own_tri_id[t] || c->own_tri_id[t].reset(npx) == hipSuccess);
+    return ok ? FRR_OK : nomem(c, "frame targets");
 }
 
 // all streams idle
@@ -417,16 +429,37 @@ int fence_stream(frr_ctx *c, hipStream_t st)
 }
 int join_tile_streams(frr_ctx *c) { return fence_stream(c, c->stream); }
 
-template <typename T> int ensure(frr_ctx *c, T *&p, size_t &cap, size_t need)
+// a workspace buffer of at least `need` elements; *fresh: it is new memory, what the old one held is gone
+template <typename T> int ensure(frr_ctx *c, DevBuf<T> &b, size_t need, bool *fresh = nullptr)
 {
-    if (need <= cap && p) return FRR_OK;
-    if (p) { int rc = drain(c); if (rc != FRR_OK) return rc; HIP_TRY(c, hipFree(p)); p = nullptr; cap = 0; }
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, need * sizeof(T));
-    if (e != hipSuccess) return fail(c, FRR_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    p = (T *)q;
-    cap = need;
-    return FRR_OK;
+    const bool grow = need > b.cap() || !b;
+    if (fresh) *fresh = grow;
+    if (!grow) return FRR_OK;
+    if (b) { int rc = drain(c); if (rc != FRR_OK) return rc; HIP_TRY(c, b.release()); }   // (the device may still be reading it)
+    return b.reset(need) == hipSuccess ? FRR_OK : nomem(c, "workspace");
+}
+// a fresh buffer that holds `bytes` of host memory, copied on c->stream; wait: the host waits for it (false: the call's next upload will)
+template <typename T> int upload(frr_ctx *c, DevBuf<T> &out, const void *host, size_t bytes, const char *what, bool wait = true)
+{
+    DevBuf<T> b;
+    if (b.reset((bytes + sizeof(T) - 1) / sizeof(T)) != hipSuccess) return nomem(c, what);
+    hipError_t e = bytes ? hipMemcpyAsync(b.get(), host, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    if (e == hipSuccess && wait) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) out = std::move(b);   // (only now: a failed upload leaves what `out` held)
+    return hip_rc(c, e);
+}
+// The first bad element of a list in the caller's device memory, 0xFFFFFFFF if none: launch(cell) starts one reduction over the
+// list on the caller's stream -- behind whatever wrote the list -- and the host waits for it (binding is a set-up call).
+template <typename Launch> int first_bad_on_device(frr_ctx *c, uint32_t *bad, Launch launch)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint32_t> cell;
+    if (cell.reset(4) != hipSuccess) return nomem(c, "check cell");
+    *bad = 0xFFFFFFFFu;
+    hipError_t e = hipMemcpyAsync(cell.get(), bad, sizeof *bad, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch(cell.get()); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, cell.get(), sizeof *bad, hipMemcpyDeviceToHost, c->stream);
+    return hip_rc(c, e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
 }
 
 // ---- cross-stream ordering (no-ops when everything runs on one stream) ----------------------------------------------
@@ -479,30 +512,31 @@ int tile_launched(frr_ctx *c, hipStream_t ts, GeomSet &gs, BinSet &bs)
     return FRR_OK;
 }
 
-hipEvent_t get_event(frr_ctx *c)
+// e: an event out of a pool of spare ones, or a new one (empty, and the error, if it cannot be created)
+hipError_t pooled_event(std::vector<Event> &pool, bool timing, Event &e)
 {
-    if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;   // (the caller drops the sample)
-    return e;
+    if (pool.empty()) return e.create(timing);
+    e = std::move(pool.back()); pool.pop_back();
+    return hipSuccess;
 }
 struct ProfScope {
-    frr_ctx *c; int kid; hipStream_t st; hipEvent_t a = nullptr;
+    frr_ctx *c; int kid; hipStream_t st; Event a;
     ProfScope(frr_ctx *c_, int kid_, hipStream_t st_) : c(c_), kid(kid_), st(st_)
     {
         if ((c->prof_mask & (1u << kid)) && (c->prof_seen[kid]++ % c->prof_period) == 0) {
-            a = get_event(c);
-            if (a && hipEventRecord(a, st) != hipSuccess) { c->ev_pool.push_back(a); a = nullptr; }
+            (void)pooled_event(c->ev_pool, true, a);   // (empty: the sample is dropped)
+            if (a && hipEventRecord(a, st) != hipSuccess) c->ev_pool.push_back(std::move(a));
         }
     }
     ~ProfScope()
     {
         // a sample whose events could not be created or recorded is dropped (frr_profile_get then reports fewer launches)
         if (!a) return;
-        hipEvent_t b = get_event(c);
-        if (b && hipEventRecord(b, st) == hipSuccess) { c->prof_pending.push_back({kid, a, b}); return; }
-        c->ev_pool.push_back(a);
-        if (b) c->ev_pool.push_back(b);
+        Event b;
+        (void)pooled_event(c->ev_pool, true, b);
+        if (b && hipEventRecord(b, st) == hipSuccess) { c->prof_pending.push_back({kid, std::move(a), std::move(b)}); return; }
+        c->ev_pool.push_back(std::move(a));
+        if (b) c->ev_pool.push_back(std::move(b));
     }
 };
 void prof_collect(frr_ctx *c)
@@ -512,7 +546,7 @@ void prof_collect(frr_ctx *c)
     for (auto &r : c->prof_pending) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) { c->prof_ms[r.kid] += ms; c->prof_n[r.kid]++; }
-        c->ev_pool.push_back(r.a); c->ev_pool.push_back(r.b);
+        c->ev_pool.push_back(std::move(r.a)); c->ev_pool.push_back(std::move(r.b));
     }
     c->prof_pending.clear();
 }
@@ -634,10 +668,9 @@ int scan_now(frr_ctx *c)
 struct SpanShape { int nw, occ; };
 SpanShape span_shape(const frr_ctx *c, uint32_t grid, uint64_t ntris, int ps_id)
 {
-    static const SpanShape all[] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIGHT_NW, 6}};
     if (c->raster_nw || c->raster_occ)                   // options raster_nw / raster_occ (tests, tools)
-        for (const SpanShape &k : all)
-            if ((!c->raster_nw || k.nw == c->raster_nw) && (!c->raster_occ || k.occ == c->raster_occ)) return k;
+        for (const auto &k : kSpanShapes)
+            if ((!c->raster_nw || k[0] == c->raster_nw) && (!c->raster_occ || k[1] == c->raster_occ)) return {k[0], k[1]};
     if (grid <= 256u) return {16, 4};
     if (grid <= 768u) return {8, 6};
     if (ps_id == FRR_PS_DEPTH && grid > 1536u && ntris * 2u <= 192ull * grid) return {LIGHT_NW, 6};
@@ -679,7 +712,7 @@ int target_write(frr_ctx *c, bool consume, hipStream_t *ts)
     if (*ts != c->stream) c->tstream[c->fs.tset].dirty = c->tstream[c->fs.tset].xdirty = true;
     for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(*ts, w.ev, 0));
     if (consume) {
-        for (const frr_ctx::FrameWait &w : c->waits) c->wait_pool.push_back(w.ev);
+        for (frr_ctx::FrameWait &w : c->waits) c->wait_pool.push_back(std::move(w.ev));
         c->waits.clear();
     }
     return FRR_OK;
@@ -769,17 +802,17 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     uint64_t fan_cap = region * FAN_REGIONS;
     if (nt + fan_cap > 0xFFFFFFF0ull) fan_cap = (0xFFFFFFF0ull - nt) / FAN_REGIONS * FAN_REGIONS;
     const size_t slots = (size_t)(nt + fan_cap);
-    if ((rc = ensure(c, S.block_sums, S.block_sums_cap, (size_t)nblocks + 1)) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.block_prefix, S.block_prefix_cap, (size_t)nblocks + 1)) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.tinfo, S.tinfo_cap, (size_t)std::max<uint64_t>(nt, 1))) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.fanbase, S.fanbase_cap, (size_t)std::max<uint64_t>(nt, 1))) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.fan_okey, S.fan_okey_cap, (size_t)std::max<uint64_t>(fan_cap, 1))) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.recs, S.setup_cap, std::max<size_t>(slots, 1024))) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.pbox, S.pbox_cap, S.setup_cap)) != FRR_OK) return rc;
-    if ((rc = ensure(c, S.bcount, S.bcount_cap, (size_t)nblocks + 1)) != FRR_OK) return rc;
-    if (K > 0 && (rc = ensure(c, S.vary, S.vary_cap, (size_t)S.setup_cap * 3 * std::max(K, 8) /* (K <= 8 in the shader table) */)) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.block_sums, (size_t)nblocks + 1)) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.block_prefix, (size_t)nblocks + 1)) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.tinfo, (size_t)std::max<uint64_t>(nt, 1))) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.fanbase, (size_t)std::max<uint64_t>(nt, 1))) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.fan_okey, (size_t)std::max<uint64_t>(fan_cap, 1))) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.recs, std::max<size_t>(slots, 1024))) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.pbox, S.recs.cap())) != FRR_OK) return rc;
+    if ((rc = ensure(c, S.bcount, (size_t)nblocks + 1)) != FRR_OK) return rc;
+    if (K > 0 && (rc = ensure(c, S.vary, S.recs.cap() * 3 * std::max(K, 8) /* (K <= 8 in the shader table) */)) != FRR_OK) return rc;
     const bool use_clipq = nt > 0 && (c->clip_queue > 0 || (c->clip_queue < 0 && c->clip_queue_auto));
-    if (use_clipq && (rc = ensure(c, S.clipq, S.clipq_cap, (size_t)nt)) != FRR_OK) return rc;
+    if (use_clipq && (rc = ensure(c, S.clipq, (size_t)nt)) != FRR_OK) return rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // the previous pass's n_emit feeds this pass's tri_base
     if (on_g && !c->gstream) {
         // created on first use: a process maps its HIP streams onto a handful of hardware queues, and two streams that
@@ -832,7 +865,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
         f.geom_duni_hash = h;
     }
     f.geom_tex_epoch = c->tex_epoch;
-    f.geom_sync_epoch = m.owned ? 0 : c->sync_epoch;   // (a host-uploaded mesh cannot change under the library)
+    f.geom_sync_epoch = m.own_dev ? 0 : c->sync_epoch;   // (a host-uploaded mesh cannot change under the library)
     f.tris_in += nt; f.draws += 1;
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
@@ -876,9 +909,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     const uint32_t ntiles = (uint32_t)a.tiles_x * a.tiles_y;
     a.color = f.color; a.depth = f.depth; a.tri_id = f.tri_id; a.cnt = c->cnt;
 #ifdef FRR_DEBUG_COUNTERS
-    if (!c->dbg_tiles && getenv("FRR_DEBUG_TILES")) {
-        if (hipMalloc((void **)&c->dbg_tiles, (size_t)c->max_tiles * 64) != hipSuccess) c->dbg_tiles = nullptr;
-    }
+    if (!c->dbg_tiles && getenv("FRR_DEBUG_TILES")) (void)c->dbg_tiles.reset((size_t)c->max_tiles * 8);   // (empty if that fails)
     if (c->dbg_tiles) (void)hipMemsetAsync(c->dbg_tiles, 0, (size_t)c->max_tiles * 64, tstream_of(c));
     a.dbg_tiles = c->dbg_tiles;
 #endif
@@ -896,12 +927,12 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     if (!B.bins) {
         size_t want = std::max<size_t>((size_t)f.geom_ntris * 8 + 4 * (size_t)c->max_tiles, (size_t)1 << 22);
         if (c->bin_cap_init) want = c->bin_cap_init;      // option bin_capacity (tests of the replay)
-        want = std::max(want, c->bset[bi ^ 1].bin_cap);   // (what the other workspace has grown to)
-        if ((rc = ensure(c, B.bins, B.bin_cap, want)) != FRR_OK) return rc;
-        if ((rc = ensure(c, B.bins2, B.bin2_cap, want)) != FRR_OK) return rc;
+        want = std::max(want, c->bset[bi ^ 1].bins.cap());   // (what the other workspace has grown to)
+        if ((rc = ensure(c, B.bins, want)) != FRR_OK) return rc;
+        if ((rc = ensure(c, B.bins2, want)) != FRR_OK) return rc;
     }
     a.bins2 = B.bins2;
-    a.bins = B.bins; a.bin_cap = (uint32_t)std::min<size_t>(B.bin_cap, 0xFFFFFFFFu);
+    a.bins = B.bins; a.bin_cap = (uint32_t)std::min<size_t>(B.bins.cap(), 0xFFFFFFFFu);
     hipStream_t gs = gstream_of(c);
     if (segmented) {
         const uint32_t ltiles = std::max<uint32_t>(grid, 1u);   // the binning numbers the rank's OWN tiles only (local_tile_row)
@@ -913,10 +944,10 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         // Option tile_order 1: the tile kernel records each tile's records in tile_cost; a later pass over the same grid on
         // this set orders its blocks heaviest first by them (build_tile_perm).  Measured no faster than the fixed order
         // (DESIGN.md section 5), so off by default: then nothing is recorded and nothing built.
-        const size_t cost_cap0 = B.tile_cost_cap;
-        if ((rc = ensure(c, B.tile_cost, B.tile_cost_cap, ltiles)) != FRR_OK) return rc;
-        if ((rc = ensure(c, B.tile_perm, B.tile_perm_cap, ltiles)) != FRR_OK) return rc;
-        if (B.tile_cost_cap != cost_cap0) {   // new memory: no costs recorded yet (and defined ones until a tile kernel writes them)
+        bool fresh_cost;
+        if ((rc = ensure(c, B.tile_cost, ltiles, &fresh_cost)) != FRR_OK) return rc;
+        if ((rc = ensure(c, B.tile_perm, ltiles)) != FRR_OK) return rc;
+        if (fresh_cost) {   // new memory: no costs recorded yet (and defined ones until a tile kernel writes them)
             B.cost_known = false;
             HIP_TRY(c, hipMemsetAsync(B.tile_cost, 0, (size_t)ltiles * sizeof(uint32_t), gs));
         }
@@ -932,7 +963,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         const int do_scan = f.scan_pending ? 1 : 0;
         const uint32_t extra = (do_scan || ordered) ? 1u : 0u;
         if (extra && G > 255u) G = 255u;
-        if ((rc = ensure(c, B.bin_matrix, B.bin_matrix_cap, (size_t)BIN_MAX_G * ((size_t)c->max_tiles + 1))) != FRR_OK) return rc;
+        if ((rc = ensure(c, B.bin_matrix, (size_t)BIN_MAX_G * ((size_t)c->max_tiles + 1))) != FRR_OK) return rc;
         // dynamic LDS: tile counters + as many staged 16-B records as fit (a chunk emits ~1.8 records per triangle)
         constexpr size_t kLdsBudget = 160 * 1024 - 1024; // the kernel's static LDS is < 1 KB
         const size_t hist_bytes = (((size_t)ltiles + 3) & ~(size_t)3) * sizeof(uint32_t);
@@ -948,8 +979,8 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         SL = std::min<uint64_t>(SL, ((uint64_t)1 << 30) / ltiles);
         if (c->ent_slot_override) SL = c->ent_slot_override;
         a.ent_slot = (uint32_t)SL;
-        a.bin_cap = (uint32_t)std::min<size_t>(B.bin_cap, 0xBFFFFFFFu);
-        if ((rc = ensure(c, B.bins2, B.bin2_cap, (size_t)ltiles * SL + a.bin_cap)) != FRR_OK) return rc;
+        a.bin_cap = (uint32_t)std::min<size_t>(B.bins.cap(), 0xBFFFFFFFu);
+        if ((rc = ensure(c, B.bins2, (size_t)ltiles * SL + a.bin_cap)) != FRR_OK) return rc;
         a.bins2 = B.bins2;
         if ((rc = gstream_wait_readers(c, B.reader)) != FRR_OK) return rc;   // the tile kernel that last read this workspace
         {
@@ -1077,12 +1108,12 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
     if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
     // (a device-bound list needs no join of `ts` with the caller's stream: frr_lines_bind_device has waited on the host for
     // that stream, behind whatever wrote the list)
-    uint32_t *&owner = c->line_owner[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
+    DevBuf<uint32_t> &owner = c->line_owner[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
     if (!owner) {
-        const size_t bytes = (size_t)c->W * c->H * sizeof(uint32_t);
-        if (hipMalloc((void **)&owner, bytes) != hipSuccess) { owner = nullptr; return fail(c, FRR_ERR_NOMEM, "hipMalloc owner plane"); }
-        const hipError_t e = hipMemsetAsync(owner, 0, bytes, ts);
-        if (e != hipSuccess) { (void)hipFree(owner); owner = nullptr; return fail(c, FRR_ERR_HIP, std::string("hipMemsetAsync owner plane: ") + hipGetErrorString(e)); }
+        const size_t npx = (size_t)c->W * c->H;
+        if (owner.reset(npx) != hipSuccess) return nomem(c, "owner plane");
+        const hipError_t e = hipMemsetAsync(owner, 0, npx * sizeof(uint32_t), ts);
+        if (e != hipSuccess) { (void)owner.release(); return fail(c, FRR_ERR_HIP, std::string("hipMemsetAsync owner plane: ") + hipGetErrorString(e)); }
     }
     a.W = c->W; a.H = c->H;
     a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
@@ -1123,11 +1154,9 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
     GeomSet &S = c->gset[f.gset];
     const int par = f.gpar();
-    {
-        const uint32_t *const before = S.vslot[par];
-        if ((rc = ensure(c, S.vslot[par], S.vslot_cap[par], S.setup_cap)) != FRR_OK) return rc;
-        if (S.vslot[par] != before) S.vslot_seq[par] = 0;   // new memory: no table
-    }
+    bool fresh_table;
+    if ((rc = ensure(c, S.vslot[par], S.recs.cap(), &fresh_table)) != FRR_OK) return rc;
+    if (fresh_table) S.vslot_seq[par] = 0;   // new memory: no table
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     hipStream_t ts = tstream_of(c);
     // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
@@ -1144,7 +1173,7 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     a.K = frr_vs_num_varyings(f.geom_vs);
     a.recs = S.recs; a.vary = S.vary; a.tinfo = S.tinfo; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix;
     a.table = S.vslot[par];
-    a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.setup_cap, S.vslot_cap[par]), 0xFFFFFFFFu); a.fan_cap = f.geom_fan_cap;
+    a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.recs.cap(), S.vslot[par].cap()), 0xFFFFFFFFu); a.fan_cap = f.geom_fan_cap;
     a.ntris = (uint32_t)f.geom_ntris;
     a.gpar = par; a.lane = f.lane;
     a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
@@ -1237,8 +1266,8 @@ int finish(frr_ctx *c)
             const size_t need = (size_t)(worst + worst / 4 + 1024);
             for (BinSet &B : c->bset) {
                 if (!B.bins && (gone || &B != &c->bset[c->log[i].set])) continue;   // (a workspace nobody has used yet is sized when it is)
-                if ((rc = ensure(c, B.bins, B.bin_cap, std::max(need, B.bin_cap))) != FRR_OK) return rc;
-                if ((rc = ensure(c, B.bins2, B.bin2_cap, std::max(need, B.bin2_cap))) != FRR_OK) return rc;
+                if ((rc = ensure(c, B.bins, std::max(need, B.bins.cap()))) != FRR_OK) return rc;
+                if ((rc = ensure(c, B.bins2, std::max(need, B.bins2.cap()))) != FRR_OK) return rc;
             }
         }
         if (h.overflow & 1u) {
@@ -1286,7 +1315,7 @@ int finish(frr_ctx *c)
     c->epoch = c->next_seq;
     if (c->next_seq > 0xF0000000u) {   // sequence numbers start over (nothing is in flight)
         const uint32_t none = SEQ_NONE;
-        HIP_TRY(c, hipMemcpy(&c->cnt->first_bad, &none, sizeof none, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(&c->cnt.get()->first_bad, &none, sizeof none, hipMemcpyHostToDevice));
         c->next_seq = c->epoch = 1;
     }
     return FRR_OK;
@@ -1339,37 +1368,28 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     if (stream) c->stream = (hipStream_t)stream;
     else { if (acquire_stream(device, &c->stream) != hipSuccess) { delete c; return FRR_ERR_HIP; } c->own_stream = true; }
     const size_t npx = (size_t)width * height;
-    bool ok = hipMalloc((void **)&c->own_color[0], npx * 4) == hipSuccess && hipMalloc((void **)&c->own_depth[0], npx * 4) == hipSuccess &&
-              hipMalloc((void **)&c->own_tri_id[0], npx * 4) == hipSuccess && hipMalloc((void **)&c->cnt, sizeof(Counters)) == hipSuccess;
     c->max_tiles = ((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
-    ok = ok && hipMalloc((void **)&c->tile_counts, (c->max_tiles + 1) * 4) == hipSuccess &&
-         hipMalloc((void **)&c->tile_offsets, (c->max_tiles + 1) * 4) == hipSuccess &&
-         hipMalloc((void **)&c->tile_cursor, (c->max_tiles + 1) * 4) == hipSuccess;
-    for (GeomSet &S : c->gset) ok = ok && hipEventCreateWithFlags(&S.reader.ev, hipEventDisableTiming) == hipSuccess;
-    for (BinSet &B : c->bset) ok = ok && hipEventCreateWithFlags(&B.reader.ev, hipEventDisableTiming) == hipSuccess;
-    for (int i = 1; i >= 0; --i) ok = ok && hipEventCreateWithFlags(&c->tstream[i].ev, hipEventDisableTiming) == hipSuccess;
-    for (auto &e : c->ev_bin) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
-    for (ReaderFence &r : c->wire_reader) ok = ok && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_verify, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_export, hipEventDisableTiming) == hipSuccess;
+    bool ok = ensure_own_set(c, 0) == FRR_OK && c->cnt.reset(1) == hipSuccess;
+    for (DevBuf<uint32_t> *b : {&c->tile_counts, &c->tile_offsets, &c->tile_cursor}) ok = ok && b->reset((size_t)c->max_tiles + 1) == hipSuccess;
+    for (Event *e : {&c->gset[0].reader.ev, &c->gset[1].reader.ev, &c->bset[0].reader.ev, &c->bset[1].reader.ev, &c->tstream[1].ev, &c->tstream[0].ev,
+                     &c->ev_bin[0], &c->ev_bin[1], &c->ev_bin[2], &c->ev_bin[3], &c->ev_join, &c->wire_reader[0].ev, &c->wire_reader[1].ev,
+                     &c->ev_verify, &c->ev_export}) ok = ok && e->create() == hipSuccess;
     if (!ok) { frr_destroy(c); return FRR_ERR_NOMEM; }
     c->fs.color = c->own_color[0]; c->fs.depth = c->own_depth[0]; c->fs.tri_id = c->own_tri_id[0];
-    {
-        // tables of frame 0 (no frame has that number), no failed command
-        memset(&c->hc, 0, sizeof c->hc);
-        c->hc.first_bad = SEQ_NONE;
-        if (hipHostMalloc((void **)&c->host_bad, 64, hipHostMallocMapped) == hipSuccess) {
-            *c->host_bad = SEQ_NONE;
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, c->host_bad, 0) == hipSuccess) c->hc.host_bad = (uint32_t *)dp;
-        }
-        if (hipMemcpy(c->cnt, &c->hc, sizeof(Counters), hipMemcpyHostToDevice) != hipSuccess) { frr_destroy(c); return FRR_ERR_HIP; }
+    // tables of frame 0 (no frame has that number), no failed command
+    memset(&c->hc, 0, sizeof c->hc);
+    c->hc.first_bad = SEQ_NONE;
+    if (hipHostMalloc((void **)&c->host_bad, 64, hipHostMallocMapped) == hipSuccess) {
+        *c->host_bad = SEQ_NONE;
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, c->host_bad, 0) == hipSuccess) c->hc.host_bad = (uint32_t *)dp;
     }
+    if (hipMemcpy(c->cnt, &c->hc, sizeof(Counters), hipMemcpyHostToDevice) != hipSuccess) { frr_destroy(c); return FRR_ERR_HIP; }
     (void)hipMemsetAsync(c->tile_counts, 0, (c->max_tiles + 1) * 4, c->stream);
     (void)hipMemsetAsync(c->own_color[0], 0, npx * 4, c->stream);      // FrameBuffer::new zero-fills (renderer.rs:423)
     (void)hipMemsetAsync(c->own_depth[0], 0, npx * 4, c->stream);
     (void)hipMemsetAsync(c->own_tri_id[0], 0xFF, npx * 4, c->stream);
-    for (auto &e : c->ev) (void)hipEventCreate(&e);
+    for (Event &e : c->ev) (void)e.create(true);
     memset(&c->uni, 0, sizeof c->uni);
     frr_set_identity(c->uni.model); frr_set_identity(c->uni.view); frr_set_identity(c->uni.proj);
     c->uni.light_pos[0] = 1.2f; c->uni.light_pos[1] = 1.0f; c->uni.light_pos[2] = 2.0f;   // phong.rs:129
@@ -1388,35 +1408,13 @@ void frr_destroy(frr_ctx *c)
     (void)hipSetDevice(c->device);
     for (hipStream_t st : {c->gstream, c->tstream[1].st, c->tstream[0].st, c->stream}) if (st) (void)hipStreamSynchronize(st);
     prof_collect(c);
-    for (auto &m : c->meshes) if (m.used && m.owned) { (void)hipFree((void *)m.dev); if (m.idx) (void)hipFree((void *)m.idx); }
-    for (auto &l : c->lines) if (l.used && l.owned) { (void)hipFree((void *)l.xyxy); (void)hipFree((void *)l.rgba); }
-    for (uint32_t *p : c->line_owner) if (p) (void)hipFree(p);
-    for (ReaderFence &r : c->wire_reader) if (r.ev) (void)hipEventDestroy(r.ev);
-    for (auto &t : c->tex) if (t.dev) (void)hipFree(t.dev);
-    if (c->host_bad) (void)hipHostFree(c->host_bad);
     for (auto &um : c->user_modules) if (um.second.mod) (void)hipModuleUnload(um.second.mod);
-    std::vector<void *> ptrs = {c->own_color[0], c->own_depth[0], c->own_tri_id[0], c->own_color[1], c->own_depth[1], c->own_tri_id[1],
-                                c->cnt, c->tile_counts, c->tile_offsets, c->tile_cursor};
-    for (GeomSet &S : c->gset) for (void *p : {(void *)S.block_sums, (void *)S.block_prefix, (void *)S.tinfo, (void *)S.fanbase, (void *)S.fan_okey, (void *)S.recs,
-                                               (void *)S.vary, (void *)S.pbox, (void *)S.bcount, (void *)S.clipq, (void *)S.vslot[0], (void *)S.vslot[1]}) ptrs.push_back(p);
-    for (BinSet &B : c->bset) for (void *p : {(void *)B.bins, (void *)B.bins2, (void *)B.bin_matrix, (void *)B.tile_cost, (void *)B.tile_perm}) ptrs.push_back(p);
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-#ifdef FRR_DEBUG_COUNTERS
-    if (c->dbg_tiles) (void)hipFree(c->dbg_tiles);
-#endif
-    for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (GeomSet &S : c->gset) if (S.reader.ev) (void)hipEventDestroy(S.reader.ev);
-    for (BinSet &B : c->bset) if (B.reader.ev) (void)hipEventDestroy(B.reader.ev);
-    for (int i = 1; i >= 0; --i) if (c->tstream[i].ev) (void)hipEventDestroy(c->tstream[i].ev);
-    for (auto &e : c->ev_bin) if (e) (void)hipEventDestroy(e);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (hipEvent_t e : {c->ev_verify, c->ev_export}) if (e) (void)hipEventDestroy(e);
-    for (const frr_ctx::FrameWait &w : c->waits) (void)hipEventDestroy(w.ev);
-    for (hipEvent_t e : c->wait_pool) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
+    if (c->host_bad) (void)hipHostFree(c->host_bad);
     // (back to the pool in the reverse order of their typical acquisition, so that the next ctx gets them in the same roles)
     for (hipStream_t st : {c->gstream, c->tstream[0].st, c->tstream[1].st}) release_stream(c->device, st);
     if (c->own_stream) release_stream(c->device, c->stream);
+    // Every buffer and event is a member and goes with the ctx, after the synchronisation above: all work that uses one was
+    // issued on those four streams, and nothing has been issued since (prof_collect only reads events that have fired).
     delete c;
 }
 
@@ -1563,13 +1561,11 @@ int frr_target_ptrs(frr_ctx *c, void **color, void **depth, void **tri_id)
     return FRR_OK;
 }
 
-static int mesh_register(frr_ctx *c, const float *dev, bool owned, uint64_t ntris, int vs, int *mesh_out, const uint32_t *idx = nullptr, uint64_t nverts = 0)
+static int mesh_register(frr_ctx *c, Mesh &&m, uint64_t ntris, int vs, int *mesh_out, uint64_t nverts = 0)
 {
-    Mesh m; m.dev = dev; m.idx = idx; m.nverts = nverts; m.owned = owned; m.used = true; m.ntris = ntris; m.vs = vs; m.gen = ++c->mesh_gen;
-    for (size_t i = 0; i < c->meshes.size(); ++i)
-        if (!c->meshes[i].used) { c->meshes[i] = m; *mesh_out = (int)i; return FRR_OK; }
-    c->meshes.push_back(m);
-    *mesh_out = (int)c->meshes.size() - 1;
+    if (m.own_dev) { m.dev = m.own_dev; m.idx = m.own_idx; }
+    m.nverts = nverts; m.used = true; m.ntris = ntris; m.vs = vs; m.gen = ++c->mesh_gen;
+    *mesh_out = slot_put(c->meshes, std::move(m));
     return FRR_OK;
 }
 int frr_mesh_upload(frr_ctx *c, const float *vs_inputs, uint64_t ntris, int vs_id, int *mesh_out)
@@ -1577,15 +1573,9 @@ int frr_mesh_upload(frr_ctx *c, const float *vs_inputs, uint64_t ntris, int vs_i
     if (!c || !mesh_out || frr_vs_input_floats(vs_id) < 0 || (ntris && !vs_inputs)) return fail(c, FRR_ERR_INVALID, "bad mesh");
     if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
     HIP_TRY(c, hipSetDevice(c->device));
-    size_t bytes = (size_t)ntris * 3 * frr_vs_input_floats(vs_id) * sizeof(float);
-    void *d = nullptr;
-    if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc mesh");
-    if (bytes) {
-        hipError_t e = hipMemcpyAsync(d, vs_inputs, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
-    }
-    return mesh_register(c, (const float *)d, true, ntris, vs_id, mesh_out);
+    Mesh m;
+    const int rc = upload(c, m.own_dev, vs_inputs, (size_t)ntris * 3 * frr_vs_input_floats(vs_id) * sizeof(float), "mesh");
+    return rc != FRR_OK ? rc : mesh_register(c, std::move(m), ntris, vs_id, mesh_out);
 }
 int frr_mesh_bind_device(frr_ctx *c, const void *dev, uint64_t ntris, int vs_id, int *mesh_out)
 {
@@ -1593,7 +1583,8 @@ int frr_mesh_bind_device(frr_ctx *c, const void *dev, uint64_t ntris, int vs_id,
     if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
     if (((uintptr_t)dev & 15u) != 0) return fail(c, FRR_ERR_INVALID, "mesh pointer must be 16-byte aligned");
     c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
-    return mesh_register(c, (const float *)dev, false, ntris, vs_id, mesh_out);
+    Mesh m; m.dev = (const float *)dev;
+    return mesh_register(c, std::move(m), ntris, vs_id, mesh_out);
 }
 // ---- indexed meshes: the Model the reference expands on the CPU (phong.rs:187-205), drawn as it is --------------------
 static int indexed_args(frr_ctx *c, const void *verts, uint64_t nverts, const void *idx, uint64_t ntris, int vs_id, int *mesh_out)
@@ -1615,49 +1606,34 @@ int frr_mesh_upload_indexed(frr_ctx *c, const float *vertices, uint64_t nverts, 
     for (uint64_t t = 0; t < ntris; ++t)
         if (indices[3 * t] >= nverts || indices[3 * t + 1] >= nverts || indices[3 * t + 2] >= nverts) return bad_index(c, t, nverts);
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t vbytes = (size_t)nverts * frr_vs_input_floats(vs_id) * sizeof(float), ibytes = (size_t)ntris * 3 * sizeof(uint32_t);
-    void *dv = nullptr, *di = nullptr;
-    if (hipMalloc(&dv, vbytes ? vbytes : 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc mesh");
-    if (hipMalloc(&di, ibytes ? ibytes : 16) != hipSuccess) { (void)hipFree(dv); return fail(c, FRR_ERR_NOMEM, "hipMalloc mesh indices"); }
-    hipError_t e = hipSuccess;
-    if (vbytes) e = hipMemcpyAsync(dv, vertices, vbytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && ibytes) e = hipMemcpyAsync(di, indices, ibytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(dv); (void)hipFree(di); return fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
-    return mesh_register(c, (const float *)dv, true, ntris, vs_id, mesh_out, (const uint32_t *)di, nverts);
+    Mesh m; int rc = upload(c, m.own_dev, vertices, (size_t)nverts * frr_vs_input_floats(vs_id) * sizeof(float), "mesh", false);
+    // (should the second one fail, the first copy may still be reading `vertices`: the free in m's destructor waits for the device)
+    if (rc == FRR_OK) rc = upload(c, m.own_idx, indices, (size_t)ntris * 3 * sizeof(uint32_t), "mesh indices");
+    return rc != FRR_OK ? rc : mesh_register(c, std::move(m), ntris, vs_id, mesh_out, nverts);
 }
 int frr_mesh_bind_device_indexed(frr_ctx *c, const void *dev_vertices, uint64_t nverts, const void *dev_indices, uint64_t ntris, int vs_id, int *mesh_out)
 {
     { int rc = indexed_args(c, dev_vertices, nverts, dev_indices, ntris, vs_id, mesh_out); if (rc != FRR_OK) return rc; }
     if (((uintptr_t)dev_vertices & 15u) != 0) return fail(c, FRR_ERR_INVALID, "mesh pointer must be 16-byte aligned");
     if (((uintptr_t)dev_indices & 3u) != 0) return fail(c, FRR_ERR_INVALID, "index pointer must be 4-byte aligned");
-    if (ntris) {
-        // every index < nverts?  One reduction over the list on the caller's stream -- behind whatever wrote the list --
-        // and a host wait: binding is a set-up call.
-        HIP_TRY(c, hipSetDevice(c->device));
-        uint32_t *d_bad = nullptr, bad = 0xFFFFFFFFu;
-        if (hipMalloc((void **)&d_bad, 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
-        hipError_t e = hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
+    if (ntris) {   // every index < nverts?
+        uint32_t bad;
+        const int rc = first_bad_on_device(c, &bad, [&](uint32_t *cell) {
             hipLaunchKernelGGL(k_index_check, dim3((uint32_t)std::min<uint64_t>((ntris + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                               (const uint32_t *)dev_indices, (uint32_t)ntris, (uint32_t)nverts, d_bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_bad);
-        if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
+                               (const uint32_t *)dev_indices, (uint32_t)ntris, (uint32_t)nverts, cell);
+        });
+        if (rc != FRR_OK) return rc;
         if (bad != 0xFFFFFFFFu) return bad_index(c, bad, nverts);
     }
     c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
-    return mesh_register(c, (const float *)dev_vertices, false, ntris, vs_id, mesh_out, (const uint32_t *)dev_indices, nverts);
+    Mesh m; m.dev = (const float *)dev_vertices; m.idx = (const uint32_t *)dev_indices;
+    return mesh_register(c, std::move(m), ntris, vs_id, mesh_out, nverts);
 }
 int frr_mesh_free(frr_ctx *c, int mesh)
 {
-    if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used) return fail(c, FRR_ERR_INVALID, "bad mesh id");
+    if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a draw of it
-    if (c->meshes[mesh].owned) { (void)hipFree((void *)c->meshes[mesh].dev); if (c->meshes[mesh].idx) (void)hipFree((void *)c->meshes[mesh].idx); }
-    c->meshes[mesh] = Mesh();
+    c->meshes[mesh] = Mesh();   // (frees the library's copies)
     return FRR_OK;
 }
 
@@ -1673,13 +1649,11 @@ static int lines_args(frr_ctx *c, const void *xyxy, const void *rgba, uint64_t n
     if (nlines >= (1ull << 31)) return fail(c, FRR_ERR_UNSUPPORTED, "2^31 or more segments per list (owner numbers are u32)");
     return FRR_OK;
 }
-static int lines_register(frr_ctx *c, const void *xyxy, const void *rgba, uint64_t n, bool owned, int *lines_out)
+static int lines_register(frr_ctx *c, Lines &&l, uint64_t n, int *lines_out)
 {
-    Lines l; l.xyxy = (const uint4 *)xyxy; l.rgba = (const uint32_t *)rgba; l.n = n; l.owned = owned; l.used = true;
-    for (size_t i = 0; i < c->lines.size(); ++i)
-        if (!c->lines[i].used) { c->lines[i] = l; *lines_out = (int)i; return FRR_OK; }
-    c->lines.push_back(l);
-    *lines_out = (int)c->lines.size() - 1;
+    if (l.own_xyxy) { l.xyxy = l.own_xyxy; l.rgba = l.own_rgba; }
+    l.n = n; l.used = true;
+    *lines_out = slot_put(c->lines, std::move(l));
     return FRR_OK;
 }
 int frr_lines_upload(frr_ctx *c, const uint32_t *xyxy, const uint8_t *rgba, uint64_t nlines, int *lines_out)
@@ -1689,52 +1663,37 @@ int frr_lines_upload(frr_ctx *c, const uint32_t *xyxy, const uint8_t *rgba, uint
     for (uint64_t k = 0; k < nlines; ++k)
         if (line_max_index(line_setup(xyxy[4 * k], xyxy[4 * k + 1], xyxy[4 * k + 2], xyxy[4 * k + 3]), c->W) >= npix) return bad_segment(c, k);
     HIP_TRY(c, hipSetDevice(c->device));
-    void *dx = nullptr, *dc = nullptr;
-    if (hipMalloc(&dx, nlines ? nlines * 16 : 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc lines");
-    if (hipMalloc(&dc, nlines ? nlines * 4 : 16) != hipSuccess) { (void)hipFree(dx); return fail(c, FRR_ERR_NOMEM, "hipMalloc line colours"); }
-    hipError_t e = hipSuccess;
-    if (nlines) e = hipMemcpyAsync(dx, xyxy, nlines * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nlines) e = hipMemcpyAsync(dc, rgba, nlines * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(dx); (void)hipFree(dc); return fail(c, FRR_ERR_HIP, hipGetErrorString(e)); }
-    return lines_register(c, dx, dc, nlines, true, lines_out);
+    Lines l; int rc = upload(c, l.own_xyxy, xyxy, (size_t)nlines * 16, "lines", false);
+    if (rc == FRR_OK) rc = upload(c, l.own_rgba, rgba, (size_t)nlines * 4, "line colours");   // (on failure l's destructor waits, as for an indexed mesh)
+    return rc != FRR_OK ? rc : lines_register(c, std::move(l), nlines, lines_out);
 }
 int frr_lines_bind_device(frr_ctx *c, const void *dev_xyxy, const void *dev_rgba, uint64_t nlines, int *lines_out)
 {
     { int rc = lines_args(c, dev_xyxy, dev_rgba, nlines, lines_out); if (rc != FRR_OK) return rc; }
     if (((uintptr_t)dev_xyxy & 15u) != 0) return fail(c, FRR_ERR_INVALID, "segment pointer must be 16-byte aligned");
     if (((uintptr_t)dev_rgba & 3u) != 0) return fail(c, FRR_ERR_INVALID, "colour pointer must be 4-byte aligned");
-    if (nlines) {
-        // does every walk stay inside the buffer?  One reduction over the list on the caller's stream -- behind whatever wrote
-        // the list -- and a host wait, as for the indices of frr_mesh_bind_device_indexed.
-        HIP_TRY(c, hipSetDevice(c->device));
-        uint32_t *d_bad = nullptr, bad = 0xFFFFFFFFu;
-        if (hipMalloc((void **)&d_bad, 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
-        hipError_t e = hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
+    if (nlines) {   // does every walk stay inside the buffer?
+        uint32_t bad;
+        const int rc = first_bad_on_device(c, &bad, [&](uint32_t *cell) {
             hipLaunchKernelGGL(k_lines_check, dim3((uint32_t)std::min<uint64_t>((nlines + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                               (const uint4 *)dev_xyxy, (uint32_t)nlines, c->W, (uint64_t)c->W * c->H, d_bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_bad);
-        if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
+                               (const uint4 *)dev_xyxy, (uint32_t)nlines, c->W, (uint64_t)c->W * c->H, cell);
+        });
+        if (rc != FRR_OK) return rc;
         if (bad != 0xFFFFFFFFu) return bad_segment(c, bad);
     }
-    return lines_register(c, dev_xyxy, dev_rgba, nlines, false, lines_out);   // (the host wait above stands for a join of the ctx's private streams)
+    Lines l; l.xyxy = (const uint4 *)dev_xyxy; l.rgba = (const uint32_t *)dev_rgba;
+    return lines_register(c, std::move(l), nlines, lines_out);   // (the host wait above stands for a join of the ctx's private streams)
 }
 int frr_lines_free(frr_ctx *c, int lines)
 {
-    if (!c || lines < 0 || lines >= (int)c->lines.size() || !c->lines[lines].used) return fail(c, FRR_ERR_INVALID, "bad line list id");
+    if (!c || !slot_ok(c->lines, lines)) return fail(c, FRR_ERR_INVALID, "bad line list id");
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a draw of it
-    if (c->lines[lines].owned) { (void)hipFree((void *)c->lines[lines].xyxy); (void)hipFree((void *)c->lines[lines].rgba); }
-    c->lines[lines] = Lines();
+    c->lines[lines] = Lines();   // (frees the library's copies)
     return FRR_OK;
 }
 int frr_draw_lines(frr_ctx *c, int lines)
 {
-    if (!c || lines < 0 || lines >= (int)c->lines.size() || !c->lines[lines].used) return fail(c, FRR_ERR_INVALID, "bad line list id");
+    if (!c || !slot_ok(c->lines, lines)) return fail(c, FRR_ERR_INVALID, "bad line list id");
     if (c->lines[lines].n == 0) return FRR_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     Cmd cmd;
@@ -1777,12 +1736,8 @@ int frr_texture_upload(frr_ctx *c, int slot, const uint8_t *rgba, uint32_t w, ui
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // the draws issued so far sample the old texture
     c->tex_epoch += 1;                                     // ... and a user VS may sample it: no pass is proven for the new one
-    Texture &t = c->tex[slot];
-    if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
-    size_t bytes = (size_t)w * h * 4;
-    if (hipMalloc((void **)&t.dev, bytes) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc texture");
-    HIP_TRY(c, hipMemcpyAsync(t.dev, rgba, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    Texture &t = c->tex[slot];   // (changed -- pointer, width and height together -- only once the new texels are on the device)
+    { int rc = upload(c, t.dev, rgba, (size_t)w * h * 4, "texture"); if (rc != FRR_OK) return rc; }
     t.w = w; t.h = h;
     refresh_dev_uniforms(c);
     return FRR_OK;
@@ -1923,7 +1878,7 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
 
 int frr_geometry(frr_ctx *c, int mesh, uint64_t *ntris_setup)
 {
-    if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used) return fail(c, FRR_ERR_INVALID, "bad mesh id");
+    if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     HIP_TRY(c, hipSetDevice(c->device));
     Cmd cmd;
     cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni;
@@ -1984,7 +1939,7 @@ int frr_raster(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_
 
 int frr_draw(frr_ctx *c, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
-    if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used) return fail(c, FRR_ERR_INVALID, "bad mesh id");
+    if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     HIP_TRY(c, hipSetDevice(c->device));
     // frr_draw knows the raster window, so a partitioned ctx can skip the setup records of triangles
     // that touch none of its tile rows (frr_geometry alone cannot: the window comes later)
@@ -2014,10 +1969,9 @@ int frr_frame_wait(frr_ctx *c, void *stream)
     frr_ctx::FrameWait *w = nullptr;
     for (frr_ctx::FrameWait &p : c->waits) if (p.stream == st) w = &p;   // (the same stream again: the later record covers both)
     if (!w) {
-        hipEvent_t e = nullptr;
-        if (!c->wait_pool.empty()) { e = c->wait_pool.back(); c->wait_pool.pop_back(); }
-        else HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->waits.push_back({st, e});
+        Event e;
+        HIP_TRY(c, pooled_event(c->wait_pool, false, e));
+        c->waits.push_back({st, std::move(e)});
         w = &c->waits.back();
     }
     HIP_TRY(c, hipEventRecord(w->ev, st));
@@ -2145,8 +2099,8 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     // a temporary device buffer that starts as the caller's: what the command leaves untouched comes back as it went in
     const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
     const size_t bytes = (size_t)entries * (size_t)K * sizeof(float);
-    float *tmp = nullptr;
-    if (hipMalloc((void **)&tmp, bytes) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc varyings buffer");
+    DevBuf<float> tmp;
+    if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
     hipError_t e = hipMemcpy(tmp, host_inout, bytes, hipMemcpyHostToDevice);   // (returns when the copy is done: in front of the command on any stream)
     if (e == hipSuccess) {
         Cmd cmd;
@@ -2158,7 +2112,6 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
         // (a finish() that failed may have left the command in the log: nothing may replay it into the freed buffer)
         for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == Cmd::VARY && c->log[k].vary_out == tmp) c->log.erase(c->log.begin() + (ptrdiff_t)k);
     }
-    (void)hipFree(tmp);
     if (rc != FRR_OK) return rc;
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy varyings: ") + hipGetErrorString(e));
     return FRR_OK;
@@ -2292,17 +2245,16 @@ float frr_host_atan2f(float y, float x) { return fd_atan2f(y, x); }
 
 int frr_debug_mvp(frr_ctx *c, int mesh, int use_mfma, float *clip_out, float *ms_out)
 {
-    if (!c || mesh < 0 || mesh >= (int)c->meshes.size() || !c->meshes[mesh].used || !clip_out) return fail(c, FRR_ERR_INVALID, "bad arguments");
+    if (!c || !slot_ok(c->meshes, mesh) || !clip_out) return fail(c, FRR_ERR_INVALID, "bad arguments");
     const Mesh &m = c->meshes[mesh];
     if (m.vs != FRR_VS_PHONG && m.vs != FRR_VS_GOURAUD) return fail(c, FRR_ERR_INVALID, "needs a pos3/uv2/normal3 mesh");
     if (m.idx) return fail(c, FRR_ERR_UNSUPPORTED, "frr_debug_mvp reads an expanded mesh, not an indexed one");
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t nverts = (uint32_t)(m.ntris * 3);
-    float4 *d = nullptr;
-    if (hipMalloc((void **)&d, (size_t)nverts * 16 + 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+    DevBuf<float4> d;
+    if (d.reset((size_t)nverts + 1) != hipSuccess) return nomem(c, "debug buffer");
     const dim3 grid((nverts + 63) / 64), block(64);
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    Event e0, e1; (void)e0.create(true); (void)e1.create(true);
     for (int it = 0; it < 3; ++it) { // last iteration is the timed one
         (void)hipEventRecord(e0, c->stream);
         if (use_mfma) hipLaunchKernelGGL(k_debug_mvp_mfma, grid, block, 0, c->stream, m.dev, nverts, 8, c->duni, d);
@@ -2314,10 +2266,7 @@ int frr_debug_mvp(frr_ctx *c, int mesh, int use_mfma, float *clip_out, float *ms
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     if (ms_out) *ms_out = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
-    return FRR_OK;
+    return hip_rc(c, e);
 }
 
 int frr_debug_gather_calib(frr_ctx *c, uint32_t log2_records)
@@ -2325,33 +2274,30 @@ int frr_debug_gather_calib(frr_ctx *c, uint32_t log2_records)
     if (!c || log2_records < 10 || log2_records > 24) return FRR_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)1 << log2_records;
-    void *d = nullptr;
-    if (hipMalloc(&d, n * 64 + 64) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+    DevBuf<uint4> d;   // n records of 64 bytes and the cell the kernel writes
+    if (d.reset(n * 4 + 4) != hipSuccess) return nomem(c, "debug buffer");
     hipError_t e = hipMemsetAsync(d, 1, n * 64 + 64, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_gather, dim3((uint32_t)(n / 256)), dim3(256), 0, c->stream, (const uint4 *)d, (uint32_t)(n - 1), (uint32_t *)((char *)d + n * 64));
+        hipLaunchKernelGGL(k_debug_gather, dim3((uint32_t)(n / 256)), dim3(256), 0, c->stream, (const uint4 *)d.get(), (uint32_t)(n - 1), (uint32_t *)(d.get() + n * 4));
         e = hipStreamSynchronize(c->stream);
     }
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
-    return FRR_OK;
+    return hip_rc(c, e);
 }
 
 int frr_debug_rcp_check(frr_ctx *c, uint32_t lo_bits, uint32_t hi_bits, uint64_t *mismatches, uint32_t *first_bad)
 {
     if (!c || !mismatches || !first_bad) return FRR_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    unsigned long long *d = nullptr;
-    if (hipMalloc((void **)&d, 16) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+    DevBuf<unsigned long long> d;
+    if (d.reset(2) != hipSuccess) return nomem(c, "debug buffer");
     const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};
     hipError_t e = hipMemcpyAsync(d, init, 16, hipMemcpyHostToDevice, c->stream);
     unsigned long long out[2] = {0, 0};
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_rcp, dim3(4096), dim3(256), 0, c->stream, lo_bits, hi_bits, d, (uint32_t *)(d + 1));
+        hipLaunchKernelGGL(k_debug_rcp, dim3(4096), dim3(256), 0, c->stream, lo_bits, hi_bits, d.get(), (uint32_t *)(d + 1));
         e = hipMemcpyAsync(out, d, 16, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
     *mismatches = out[0];
     *first_bad = (uint32_t)out[1];
@@ -2374,17 +2320,14 @@ int frr_debug_scan64(frr_ctx *c, const uint32_t *in, uint32_t *out)
 {
     if (!c || !in || !out) return FRR_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    uint32_t *d = nullptr;
-    if (hipMalloc((void **)&d, 128 * 4) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+    DevBuf<uint32_t> d;
+    if (d.reset(128) != hipSuccess) return nomem(c, "debug buffer");
     hipError_t e = hipMemcpyAsync(d, in, 64 * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_scan, dim3(1), dim3(64), 0, c->stream, d, d + 64);
+        hipLaunchKernelGGL(k_debug_scan, dim3(1), dim3(64), 0, c->stream, d.get(), d + 64);
         e = hipMemcpyAsync(out, d + 64, 64 * 4, hipMemcpyDeviceToHost, c->stream);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
-    return FRR_OK;
+    return hip_rc(c, e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
 }
 
 int frr_debug_atan2f(frr_ctx *c, const float *y, const float *x, float *out, uint64_t n)
@@ -2392,18 +2335,15 @@ int frr_debug_atan2f(frr_ctx *c, const float *y, const float *x, float *out, uin
     if (!c || !y || !x || !out) return FRR_ERR_INVALID;
     if (n == 0) return FRR_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, n * 12) != hipSuccess) return fail(c, FRR_ERR_NOMEM, "hipMalloc");
+    DevBuf<float> d;
+    if (d.reset(n * 3) != hipSuccess) return nomem(c, "debug buffer");
     hipError_t e = hipMemcpyAsync(d, y, n * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + n, x, n * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_atan2f, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d, d + n, d + 2 * n, n);
+        hipLaunchKernelGGL(k_debug_atan2f, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d.get(), d + n, d + 2 * n, n);
         e = hipMemcpyAsync(out, d + 2 * n, n * 4, hipMemcpyDeviceToHost, c->stream);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, hipGetErrorString(e));
-    return FRR_OK;
+    return hip_rc(c, e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
 }
 
 } // extern "C"
