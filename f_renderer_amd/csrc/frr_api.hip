@@ -589,6 +589,15 @@ void blocked_rows(int tiles_y, int rank, int world, int *t0, int *t1)
     *t1 = *t0 + q + (rank < r ? 1 : 0);
 }
 
+// The ctx's tile-row ownership over `tiles_y` tile rows.  `blocked` is set on a real partition only (world > 1): without one every
+// reader (owns_tile_row -- so k_clear_unowned_rows too --, local_tile_row, tri_rows_owned) answers from `world <= 1` before the layout.
+RowOwner row_owner(const FrameState &f, int tiles_y)
+{
+    RowOwner o = {f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
+    if (o.blocked) blocked_rows(tiles_y, f.rank, f.world, &o.brow0, &o.brow1);
+    return o;
+}
+
 // the code object of user shader `id` on this ctx's device
 int user_module(frr_ctx *c, int id, const UserModule **out)
 {
@@ -677,14 +686,12 @@ SpanShape span_shape(const frr_ctx *c, uint32_t grid, uint64_t ntris, int ps_id)
     return {4, 6};
 }
 
-template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const RasterArgs &a, uint32_t grid, const SpanShape sh, const DevUniforms &du, bool count_frags)
+template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const RasterArgs &a, uint32_t grid, const SpanShape sh, const DevUniforms &du, bool count_frags, int win_safe)
 {
     ProfScope p(c, KID_RASTER, ts);
     if (c->raster_sweep) {
         hipLaunchKernelGGL((k_raster<K, PS>), dim3(grid), dim3(256), 0, ts, a, du);
     } else {
-        // the span algebra needs every coordinate it touches within +-SPAN_SAFE (no i32 wrap)
-        const int win_safe = a.x0 >= -SPAN_SAFE && a.y0 >= -SPAN_SAFE && a.x1 <= SPAN_SAFE && a.y1 <= SPAN_SAFE;
         auto go = [&](auto count_tag, auto nw_tag, auto occ_tag) {
             constexpr bool CNT = decltype(count_tag)::value;
             constexpr int NWV = decltype(nw_tag)::value, OCCV = decltype(occ_tag)::value;
@@ -747,8 +754,7 @@ int settle_targets(frr_ctx *c)
         if (rc != FRR_OK) return rc;
         f.clear_pending = f.unowned_debt = false;
     } else if (f.unowned_debt) {
-        RowOwner own = {f.rank, f.world, f.part_blocked ? 1 : 0, 0, 0};
-        if (own.blocked) blocked_rows(f.debt_tiles_y, f.rank, f.world, &own.brow0, &own.brow1);
+        const RowOwner own = row_owner(f, f.debt_tiles_y);
         // (the rest of a clear issued with an earlier draw: it follows the pending waits, the next frame's writes consume them)
         hipStream_t ts;
         { int rc = target_write(c, false, &ts); if (rc != FRR_OK) return rc; }
@@ -836,13 +842,9 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.in = m.dev; g.idx = m.idx; g.nverts = (uint32_t)m.nverts; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
     g.fan_cap = (uint32_t)fan_cap;
     g.seq = cmd.seq; g.epoch = c->epoch; g.frame_no = f.frame_no;
+    const RowOwner own = row_owner(f, (int)(((int64_t)cmd.fy1 - cmd.fy0 + TILE - 1) / TILE));
     g.part_rank = f.rank; g.part_world = cmd.filter ? f.world : 1; g.part_y0 = cmd.fy0; g.part_y1 = cmd.fy1;
-    g.part_blocked = 0; g.part_brow0 = g.part_brow1 = 0;
-    if (cmd.filter && f.part_blocked) {
-        const int tiles_y = (int)(((int64_t)cmd.fy1 - cmd.fy0 + TILE - 1) / TILE);
-        g.part_blocked = 1;
-        blocked_rows(tiles_y, f.rank, f.world, &g.part_brow0, &g.part_brow1);
-    }
+    g.part_blocked = own.blocked; g.part_brow0 = own.brow0; g.part_brow1 = own.brow1;
     g.gpar = par; g.lane = f.lane;
     g.block_sums = S.block_sums; g.block_prefix = S.block_prefix; g.tinfo = S.tinfo; g.fanbase = S.fanbase; g.fan_okey = S.fan_okey;
     g.recs = S.recs; g.vary = S.vary; g.pbox = S.pbox; g.cnt = c->cnt;
@@ -899,9 +901,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     a.cstride = (int)c->W; a.dstride = x1;
     a.tiles_x = (int)((ww + TILE - 1) / TILE); a.tiles_y = (int)((wh + TILE - 1) / TILE);
     a.tiles_x_magic = 0u; // set below once the grid is known (exact only for block indices and tile counts < 2^16)
-    a.rank = f.rank; a.world = f.world;
-    a.blocked = (f.part_blocked && f.world > 1) ? 1 : 0; a.brow0 = a.brow1 = 0;
-    if (a.blocked) blocked_rows(a.tiles_y, a.rank, a.world, &a.brow0, &a.brow1);
+    a.own = row_owner(f, a.tiles_y);
     a.recs = S.recs; a.vary = S.vary; a.pbox = S.pbox; a.bcount = S.bcount;
     a.tinfo = S.tinfo; a.fanbase = S.fanbase; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix; a.ntris_draw = (uint32_t)f.geom_ntris;
     a.tile_counts = c->tile_counts; a.tile_offsets = c->tile_offsets; a.tile_cursor = c->tile_cursor;
@@ -915,7 +915,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
 #endif
     a.seg = nullptr; a.nseg = 0;
     a.tile_perm = nullptr; a.tile_cost = nullptr;
-    const int owned_rows = a.blocked ? a.brow1 - a.brow0 : (a.tiles_y > a.rank ? (a.tiles_y - a.rank + a.world - 1) / a.world : 0);
+    const int owned_rows = a.own.blocked ? a.own.brow1 - a.own.brow0 : (a.tiles_y > f.rank ? (a.tiles_y - f.rank + f.world - 1) / f.world : 0);
     const uint32_t grid = (uint32_t)a.tiles_x * owned_rows;
     if (a.tiles_x >= 2 && a.tiles_x < 65536 && grid < 65536u) a.tiles_x_magic = (uint32_t)(0x100000000ull / (uint64_t)a.tiles_x + 1ull);
     const SpanShape sh = span_shape(c, grid, f.geom_ntris, ps_id);
@@ -951,7 +951,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
             B.cost_known = false;
             HIP_TRY(c, hipMemsetAsync(B.tile_cost, 0, (size_t)ltiles * sizeof(uint32_t), gs));
         }
-        const TileOrderKey okey = {grid, a.tiles_x, x0, x1, y0, y1, a.rank, a.world, a.blocked, sh.nw};
+        const TileOrderKey okey = {grid, a.tiles_x, x0, x1, y0, y1, f.rank, f.world, a.own.blocked, sh.nw};
         const bool ordered = tile_order_built(c->tile_order, c->in_replay, okey, B.cost_known, B.cost_key);
         const bool record = c->tile_order == TILE_ORDER_HEAVY_FIRST;
         a.tile_cost = record ? B.tile_cost : nullptr;
@@ -1034,6 +1034,8 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     // which only a resolve per ENTRY reproduces (k_raster_entries).  On a partitioned ctx the pixels of an entry belong to
     // different ranks, each with a depth buffer of its own: there the tile kernels run as for any window.
     const bool shared_entries = ww > (int64_t)x1 && f.world <= 1;
+    // the span algebra needs every coordinate it touches within +-SPAN_SAFE (no i32 wrap)
+    const int win_safe = a.x0 >= -SPAN_SAFE && a.y0 >= -SPAN_SAFE && a.x1 <= SPAN_SAFE && a.y1 <= SPAN_SAFE;
     if (grid && shared_entries) {
         ProfScope p(c, KID_RASTER, ts);
         const unsigned eg = (unsigned)((((wh - 1) * (int64_t)x1 + ww) + 255) / 256);
@@ -1054,18 +1056,17 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         ProfScope p(c, KID_RASTER, ts);
         int shi = 4;
         for (int k = 0; k < 6; ++k) if (kSpanShapes[k][0] == sh.nw && kSpanShapes[k][1] == sh.occ) shi = k;
-        const int win_safe = a.x0 >= -SPAN_SAFE && a.y0 >= -SPAN_SAFE && a.x1 <= SPAN_SAFE && a.y1 <= SPAN_SAFE;
         RasterArgs ra = a; DevUniforms d = cmd.duni; int ws = win_safe;
         void *args[] = {&ra, &d, &ws};
         if (c->raster_sweep) (void)hipModuleLaunchKernel(um->sweep, grid, 1, 1, 256, 1, 1, 0, ts, args, nullptr);   // k_raster(RasterArgs, DevUniforms)
         else (void)hipModuleLaunchKernel(um->span[cmd.count_frags ? 1 : 0][shi], grid, 1, 1, (unsigned)kSpanShapes[shi][0] * 64u, 1, 1, 0, ts, args, nullptr);
     } else if (grid) {
         switch (ps_id) {
-        case FRR_PS_DEPTH: launch_raster<0, FRR_PS_DEPTH>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_FLAT: launch_raster<0, FRR_PS_FLAT>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_COLOR: launch_raster<3, FRR_PS_COLOR>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_PHONG: launch_raster<8, FRR_PS_PHONG>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
-        case FRR_PS_BLINN: launch_raster<8, FRR_PS_BLINN>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags); break;
+        case FRR_PS_DEPTH: launch_raster<0, FRR_PS_DEPTH>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags, win_safe); break;
+        case FRR_PS_FLAT: launch_raster<0, FRR_PS_FLAT>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags, win_safe); break;
+        case FRR_PS_COLOR: launch_raster<3, FRR_PS_COLOR>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags, win_safe); break;
+        case FRR_PS_PHONG: launch_raster<8, FRR_PS_PHONG>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags, win_safe); break;
+        case FRR_PS_BLINN: launch_raster<8, FRR_PS_BLINN>(c, ts, a, grid, sh, cmd.duni, cmd.count_frags, win_safe); break;
         }
     }
     HIP_TRY(c, hipGetLastError());
@@ -1116,8 +1117,7 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
         if (e != hipSuccess) { (void)owner.release(); return fail(c, FRR_ERR_HIP, std::string("hipMemsetAsync owner plane: ") + hipGetErrorString(e)); }
     }
     a.W = c->W; a.H = c->H;
-    a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
-    if (a.own.blocked) blocked_rows((int)((c->H + TILE - 1) / TILE), f.rank, f.world, &a.own.brow0, &a.own.brow1);
+    a.own = row_owner(f, (int)((c->H + TILE - 1) / TILE));
     a.chunk = c->lines_chunk ? c->lines_chunk : LINES_CHUNK;
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
     a.owner = owner; a.color = (uint32_t *)f.color;
@@ -1176,8 +1176,7 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.recs.cap(), S.vslot[par].cap()), 0xFFFFFFFFu); a.fan_cap = f.geom_fan_cap;
     a.ntris = (uint32_t)f.geom_ntris;
     a.gpar = par; a.lane = f.lane;
-    a.own = RowOwner{f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
-    if (a.own.blocked) blocked_rows((int)((wh + TILE - 1) / TILE), f.rank, f.world, &a.own.brow0, &a.own.brow1);
+    a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
     a.tri_id = f.tri_id; a.out = cmd.vary_out;
     if (S.vslot_seq[par] != f.geom_seq || S.vslot_epoch[par] != c->epoch) {   // (else: an earlier resolve of this pass built the table)
@@ -2042,7 +2041,7 @@ int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uin
                 frr_setup_vertex &o = out[i * 3 + v];
                 memset(&o, 0, sizeof o);
                 o.spf[0] = r.s[2 * s]; o.spf[1] = r.s[2 * s + 1];
-                o.spi[0] = f32_as_i32(r.s[2 * s] + 0.5f); o.spi[1] = f32_as_i32(r.s[2 * s + 1] + 0.5f);   // renderer.rs:233-234 (the record keeps spf only)
+                o.spi[0] = spi_of(r.s[2 * s]); o.spi[1] = spi_of(r.s[2 * s + 1]);
                 o.rhw = r.rhw[s];
                 for (int k = 0; k < K; ++k) o.ctx[k] = vary[(size_t)slot * 3 * K + (size_t)s * K + k];
             }

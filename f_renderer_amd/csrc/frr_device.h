@@ -191,14 +191,15 @@ struct GeomArgs {
     Counters *cnt;
 };
 
+// tile-row ownership over a range of tile rows: ty % world == rank (interleaved), or, blocked != 0, the rows [brow0, brow1); world <= 1: all
+struct RowOwner { int32_t rank, world, blocked, brow0, brow1; };
 struct RasterArgs {
     int32_t x0, x1, y0, y1;           // width_range / height_range (renderer.rs:270-271)
     int32_t win_w, win_h;             // x1-x0, y1-y0
     int32_t cstride, dstride;         // colour row stride (fb.width), depth row stride (= x1, :362)
     int32_t tiles_x, tiles_y;
     uint32_t tiles_x_magic;           // 2^32 / tiles_x + 1: block index -> tile row by one multiplication (0: plain division)
-    int32_t rank, world;              // tile-row ownership: ty % world == rank (interleaved), or ...
-    int32_t blocked, brow0, brow1;    // ... blocked != 0: the rank owns the contiguous tile rows [brow0, brow1)
+    RowOwner own;                     // tile-row ownership over the window's tiles_y rows
     const RasterRec *recs;
     const float *vary;
     const uint4 *pbox;                // see GeomArgs::pbox
@@ -238,8 +239,7 @@ struct RasterArgs {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// does this rank rasterize tile row ty (window-local)?  interleaved rows, or the block [brow0, brow1)
-struct RowOwner { int rank, world, blocked, brow0, brow1; };
+// does this rank rasterize tile row ty (window-local)?
 __device__ __forceinline__ bool owns_tile_row(int ty, const RowOwner &o)
 {
     return o.world <= 1 || (o.blocked ? (ty >= o.brow0 && ty < o.brow1) : ty % o.world == o.rank);
@@ -464,8 +464,7 @@ __device__ __forceinline__ ScreenVtx to_screen(const float pos[4], float fw, flo
     v.ndcy = pos[1] * v.rhw;
     v.sx = (v.ndcx + 1.0f) * fw * 0.5f;
     v.sy = (1.0f - v.ndcy) * fh * 0.5f;
-    v.ix = f32_as_i32(v.sx + 0.5f);
-    v.iy = f32_as_i32(v.sy + 0.5f);
+    v.ix = spi_of(v.sx); v.iy = spi_of(v.sy);
     return v;
 }
 // Multi-GPU: does a (not clipped) triangle with snapped corner rows iy0..iy2 touch a tile row this rank owns?
@@ -549,6 +548,21 @@ __device__ __forceinline__ Frag frag_eval(float s0x_, float s0y_, float s1x_, fl
     f.a = a * inv; f.b = b * inv; f.c = c * inv;
     f.rhw = r0 * f.a + r1 * f.b + r2 * f.c;                        // :360
     return f;
+}
+// the perspective-correct weights c0, c1, c2 (.x, .y, .z) of the three vertices' varyings at that fragment (renderer.rs:368-372)
+__device__ __forceinline__ float3 frag_weights(const Frag &f, float r0, float r1, float r2)
+{
+    const float w = recip_exact(f.rhw != 0.0f ? f.rhw : 1.0f);                 // :368 (== 1.0f / x, bit for bit)
+    return make_float3(r0 * f.a * w, r1 * f.b * w, r2 * f.c * w);              // :370-372
+}
+// the fragment of the triangle in record *rec at pixel (cx, cy), with its flags word: three 16-byte loads (the edge words are not read)
+struct RecFrag { Frag f; float r0, r1, r2; uint32_t flags; };
+__device__ __forceinline__ RecFrag rec_frag(const RasterRec *rec, int cx, int cy)
+{
+    const uint4 *rp = reinterpret_cast<const uint4 *>(rec);
+    const uint4 q1 = rp[1], q2 = rp[2], q3 = rp[3];
+    const float r0 = u2f(q3.x), r1 = u2f(q3.y), r2 = u2f(q3.z);
+    return {frag_eval(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y), u2f(q2.z), u2f(q2.w), r0, r1, r2, cx, cy), r0, r1, r2, q3.w};
 }
 
 // ---- pixel shader table (contract renderer.rs:283,380) ----------------------------------

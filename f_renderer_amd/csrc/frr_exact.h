@@ -65,6 +65,8 @@ FRR_HD int32_t f32_as_i32(float f)
     return f32_as_i32_ref(f);
 #endif
 }
+// spi of a screen coordinate: `(spf + 0.5) as i32` (renderer.rs:233-234; the setup records keep spf only)
+FRR_HD int32_t spi_of(float s) { return f32_as_i32(s + 0.5f); }
 FRR_HD uint32_t f32_as_u32(float f)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -122,13 +122,12 @@ template <bool SCATTER, class PUT>
 __device__ __forceinline__ void bin_one(const RasterArgs &a, uint32_t *s_hist, const uint4 pb, int lane, const PUT &put)
 {
     const uint32_t i = pb.w;    // the slot the entry stands for
-    const RowOwner own = {a.rank, a.world, a.blocked, a.brow0, a.brow1};
     const TileRange t = tiles_of_pbox(a, pb);
     const int ntx = t.tx1 - t.tx0, nty = t.ty1 - t.ty0;
     const int nt = ntx * nty;
     auto visit = [&](const uint4 &ent, int tx, int ty) {
-        if (!owns_tile_row(ty, own)) return;
-        const int tile = local_tile_row(ty, own) * a.tiles_x + tx;
+        if (!owns_tile_row(ty, a.own)) return;
+        const int tile = local_tile_row(ty, a.own) * a.tiles_x + tx;
         if constexpr (SCATTER) {
             put(atomicAdd(&s_hist[tile], 1u), ent);
         } else {
@@ -142,10 +141,10 @@ __device__ __forceinline__ void bin_one(const RasterArgs &a, uint32_t *s_hist, c
     // predicated positions; 25.9 -> 23.0 us per launch on the 1080p frame without it.)
     const bool small = nt > 0 && ntx <= 2 && nty <= 2;
     if (small) {
-        const bool own0 = owns_tile_row(t.ty0, own);
-        const bool own1 = nty == 2 && owns_tile_row(t.ty0 + 1, own);
-        const int t00 = local_tile_row(t.ty0, own) * a.tiles_x + t.tx0;
-        const int t10 = local_tile_row(t.ty0 + 1, own) * a.tiles_x + t.tx0;
+        const bool own0 = owns_tile_row(t.ty0, a.own);
+        const bool own1 = nty == 2 && owns_tile_row(t.ty0 + 1, a.own);
+        const int t00 = local_tile_row(t.ty0, a.own) * a.tiles_x + t.tx0;
+        const int t10 = local_tile_row(t.ty0 + 1, a.own) * a.tiles_x + t.tx0;
         const bool v0 = own0, v1 = own0 && ntx == 2, v2 = own1, v3 = own1 && ntx == 2;
         if constexpr (SCATTER) {
             uint32_t p0 = ~0u, p1 = ~0u, p2 = ~0u, p3 = ~0u;
@@ -222,7 +221,7 @@ __device__ __forceinline__ void bin_walk_blocks(const RasterArgs &a, uint32_t *s
                                                 const uint32_t *__restrict__ bcount, uint32_t ntris, uint32_t b_lo, uint32_t b_hi,
                                                 int lane, uint32_t wave, const PUT &put)
 {
-    if (a.world <= 1) {
+    if (a.own.world <= 1) {
         // the whole window: nearly every quarter exists, so they are taken as they come, without looking at the counts
         // (entries past a block's count are zero: an empty box)
         const uint32_t nq = (b_hi - b_lo) * (GEOM_BLOCK / 64);
@@ -834,12 +833,11 @@ __global__ __launch_bounds__(256) void k_bin(RasterArgs a, uint32_t fan_cap)
         // entry index: the inputs' entries (dense per block, zero = nothing, GeomArgs::pbox), then the used fan entries
         const uint4 cu = base + lane < n ? a.pbox[fan_map_slot(fm, base + lane)] : make_uint4(0u, 0u, 0u, 0u); // (0,0)-(0,0) is an empty box
         const uint32_t i = cu.w;   // the slot the entry stands for
-        const RowOwner own = {a.rank, a.world, a.blocked, a.brow0, a.brow1};
         const TileRange t = tiles_of_pbox(a, cu);
         const int ntx = t.tx1 - t.tx0, nty = t.ty1 - t.ty0;
         const int nt = ntx * nty;
         auto visit = [&](const uint4 &ent, int tx, int ty) {
-            if (!owns_tile_row(ty, own)) return;
+            if (!owns_tile_row(ty, a.own)) return;
             const int tile = ty * a.tiles_x + tx;
             if constexpr (FILL) {
                 uint32_t pos = a.tile_offsets[tile] + atomicAdd(&a.tile_cursor[tile], 1u);

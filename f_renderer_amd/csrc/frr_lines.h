@@ -143,8 +143,8 @@ template <bool WIRE, bool PAINT> __device__ __forceinline__ void lines_walk(cons
                     // emission-order corners e and e + 1 (the record holds them after the orientation swap of corners 1, 2)
                     const uint32_t ca = e, cb = e == 2u ? 0u : e + 1u;
                     const uint32_t ia = sw && ca ? 3u - ca : ca, ib = sw && cb ? 3u - cb : cb;
-                    const int32_t xa = f32_as_i32(r.s[2 * ia] + 0.5f), ya = f32_as_i32(r.s[2 * ia + 1] + 0.5f);   // spi, renderer.rs:233-234
-                    const int32_t xb = f32_as_i32(r.s[2 * ib] + 0.5f), yb = f32_as_i32(r.s[2 * ib + 1] + 0.5f);
+                    const int32_t xa = spi_of(r.s[2 * ia]), ya = spi_of(r.s[2 * ia + 1]);
+                    const int32_t xb = spi_of(r.s[2 * ib]), yb = spi_of(r.s[2 * ib + 1]);
                     // the library's rule for a wireframe: an edge with an endpoint off the screen is skipped whole
                     if (xa >= 0 && xb >= 0 && ya >= 0 && yb >= 0 && (uint32_t)xa < a.W && (uint32_t)xb < a.W && (uint32_t)ya < a.H && (uint32_t)yb < a.H) {
                         s = line_setup((uint32_t)xa, (uint32_t)ya, (uint32_t)xb, (uint32_t)yb);

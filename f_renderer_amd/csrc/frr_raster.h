@@ -106,7 +106,7 @@ __device__ __forceinline__ TileCtx tile_ctx(const RasterArgs &a)
     // bid / tiles_x by multiplication (scalar unit): exact for bid, tiles_x < 2^16 (tiles_x_magic = 2^32 / tiles_x + 1; 0: divide)
     const int trow = a.tiles_x_magic ? (int)__builtin_amdgcn_readfirstlane((int)__umulhi((uint32_t)bid, a.tiles_x_magic)) : bid / a.tiles_x;
     const int tx = bid - trow * a.tiles_x;
-    const int ty = a.blocked ? a.brow0 + trow : a.rank + trow * a.world;
+    const int ty = a.own.blocked ? a.own.brow0 + trow : a.own.rank + trow * a.own.world;
     c.tile = ty * a.tiles_x + tx;
     c.ltile = bid;                                      // its index among the rank's own tiles (segmented binning)
     c.lx0 = tx * TILE; c.ly0 = ty * TILE;
@@ -156,6 +156,24 @@ __device__ __forceinline__ void tile_fill_clear(const RasterArgs &a, const TileC
     }
 }
 
+// The colour of the fragment f of the triangle at `slot` (renderer.rs:368-381): the perspective weights, the K interpolated
+// varyings, the pixel shader, the RGBA8 word the colour target takes.
+template <int K, int PS>
+__device__ __forceinline__ uint32_t shade_pixel(const RasterArgs &a, const DevUniforms &u, uint32_t slot, const Frag &f,
+                                                float r0, float r1, float r2, const float *u8lut = nullptr)
+{
+    const float3 cw = frag_weights(f, r0, r1, r2);                          // :368-372
+    float in[K > 0 ? K : 1];
+    if constexpr (K > 0) {
+        const float *v = a.vary + (size_t)slot * (3 * K);
+#pragma unroll
+        for (int k = 0; k < K; ++k) in[k] = v[k] * cw.x + v[K + k] * cw.y + v[2 * K + k] * cw.z; // :374-378
+    }
+    float col[4];
+    run_ps<PS>(u, in, col, u8lut);                                          // :380
+    return quantize_u8(col[0]) | (quantize_u8(col[1]) << 8) | (quantize_u8(col[2]) << 16) | (quantize_u8(col[3]) << 24); // :7-14
+}
+
 // resolve: the owner of each pixel is re-evaluated with the same arithmetic and written out
 template <int K, int PS>
 __device__ __forceinline__ void tile_resolve(const RasterArgs &a, const DevUniforms &u, const TileCtx &c,
@@ -184,31 +202,13 @@ __device__ __forceinline__ void tile_resolve(const RasterArgs &a, const DevUnifo
                 continue;
             }
         }
-        const uint4 *rp = reinterpret_cast<const uint4 *>(a.recs + t);
-        const uint4 q1 = rp[1], q2 = rp[2], q3 = rp[3];
-        const int cx = c.ax0 + x, cy = c.ay0 + y;
-        const float r0 = u2f(q3.x), r1 = u2f(q3.y), r2 = u2f(q3.z);
-        Frag f = frag_eval(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y), u2f(q2.z), u2f(q2.w), r0, r1, r2, cx, cy);
+        const RecFrag rf = rec_frag(a.recs + t, c.ax0 + x, c.ay0 + y);
         const size_t di = (size_t)(c.ly0 + y) * a.dstride + (c.lx0 + x);
-        a.depth[di] = f.rhw;                                                    // :366
-        // (the record is here anyway, and its flags carry the triangle's emission offset within its geometry block: one table
-        // lookup instead of id_emission's two dependent ones)
-        a.tri_id[di] = tri_base + a.block_prefix[((id - 1u) >> FAN_BITS) / GEOM_BLOCK] + ((q3.w >> REC_EOFF_SHIFT) & REC_EOFF_MASK);
-        if constexpr (PS != FRR_PS_DEPTH) {
-            const float w = recip_exact(f.rhw != 0.0f ? f.rhw : 1.0f);          // :368 (== 1.0f / x, bit for bit)
-            const float c0 = r0 * f.a * w, c1 = r1 * f.b * w, c2 = r2 * f.c * w; // :370-372
-            float in[K > 0 ? K : 1];
-            if constexpr (K > 0) {
-                const float *v = a.vary + (size_t)t * (3 * K);
-#pragma unroll
-                for (int k = 0; k < K; ++k) in[k] = v[k] * c0 + v[K + k] * c1 + v[2 * K + k] * c2; // :374-378
-            }
-            float col[4];
-            run_ps<PS>(u, in, col, u8lut);                                      // :380
-            const uint32_t q = quantize_u8(col[0]) | (quantize_u8(col[1]) << 8) | (quantize_u8(col[2]) << 16) |
-                               (quantize_u8(col[3]) << 24);                     // :7-14
-            reinterpret_cast<uint32_t *>(a.color)[(size_t)(c.ly0 + y) * a.cstride + (c.lx0 + x)] = q; // :381,:496-503
-        }
+        a.depth[di] = rf.f.rhw;                                                 // :366
+        // (the record's flags word carries the triangle's emission offset within its geometry block: one lookup, not id_emission's two dependent ones)
+        a.tri_id[di] = tri_base + a.block_prefix[((id - 1u) >> FAN_BITS) / GEOM_BLOCK] + ((rf.flags >> REC_EOFF_SHIFT) & REC_EOFF_MASK);
+        if constexpr (PS != FRR_PS_DEPTH)                                       // :381,:496-503
+            reinterpret_cast<uint32_t *>(a.color)[(size_t)(c.ly0 + y) * a.cstride + (c.lx0 + x)] = shade_pixel<K, PS>(a, u, t, rf.f, rf.r0, rf.r1, rf.r2, u8lut);
     }
 }
 
@@ -232,10 +232,7 @@ __device__ __forceinline__ void tile_resolve_depth4(const RasterArgs &a, const T
             won[i] = id[i] != 0u && x + i < c.tw;      // (pixels of a partial tile beyond the window hold all-ones keys)
             float dz = zkey_decode(zk[i]);
             if (won[i] && !(dz != 0.0f && dz == dz)) { // -0.0 merged with +0.0, or NaN: the reference arithmetic decides
-                const uint4 *rp = reinterpret_cast<const uint4 *>(a.recs + slot_of_emission(a, id[i] - 1u));
-                const uint4 q1 = rp[1], q2 = rp[2], q3 = rp[3];
-                dz = frag_eval(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y), u2f(q2.z), u2f(q2.w), u2f(q3.x), u2f(q3.y), u2f(q3.z),
-                               c.ax0 + x + i, c.ay0 + y).rhw;
+                dz = rec_frag(a.recs + slot_of_emission(a, id[i] - 1u), c.ax0 + x + i, c.ay0 + y).f.rhw;
             }
             dv[i] = won[i] ? f2u(dz) : f2u(a.clear_depth);                                         // :366
             iv[i] = won[i] ? tri_base + (id[i] - 1u) : ~0u;
@@ -263,6 +260,29 @@ __device__ __forceinline__ void tile_resolve_depth4(const RasterArgs &a, const T
     }
 }
 
+// The reference's triangle set-up in wrapping i32 (renderer.rs:285-341) from a record: spi of the corners, their bbox clamped to the window
+// and, of edge e = 0, 1, 2 (01, 12, 20), E = A (cx - a.x) + B (cy - a.y) with A = -(b.y - a.y), B = b.x - a.x (:329-331) and the threshold: E < bias
+// rejects  <=>  E > thr accepts (bias 0 for top-left edges, else 1; :333-341).  Edge terms are formed where a kernel asks (behind its bbox test).
+struct SweepSetup {
+    const RasterRec *r;
+    int px[3], py[3], bx0, bx1, by0, by1;
+    __device__ __forceinline__ uint32_t A(int e) const { return 0u - (uint32_t)(py[(e + 1) % 3] - py[e]); }
+    __device__ __forceinline__ uint32_t B(int e) const { return (uint32_t)(px[(e + 1) % 3] - px[e]); }
+    __device__ __forceinline__ uint32_t E(int e, int cx, int cy) const { return A(e) * (uint32_t)(cx - px[e]) + B(e) * (uint32_t)(cy - py[e]); }
+    __device__ __forceinline__ int thr(int e) const { return (r->flags & (2u << e)) ? 0 : -1; }
+};
+__device__ __forceinline__ SweepSetup sweep_setup(const RasterRec *__restrict__ r, const RasterArgs &a)
+{
+    SweepSetup s;
+    s.r = r;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) { s.px[v] = spi_of(r->s[2 * v]); s.py[v] = spi_of(r->s[2 * v + 1]); }
+    // clamped bbox (renderer.rs:285-298; clamp is monotone so it commutes with min/max)
+    s.bx0 = clampi(min(s.px[0], min(s.px[1], s.px[2])), a.x0, a.x1); s.bx1 = clampi(max(s.px[0], max(s.px[1], s.px[2])), a.x0, a.x1);
+    s.by0 = clampi(min(s.py[0], min(s.py[1], s.py[2])), a.y0, a.y1); s.by1 = clampi(max(s.py[0], max(s.py[1], s.py[2])), a.y0, a.y1);
+    return s;
+}
+
 // Brute-force sweep of ONE triangle (wave-uniform index t) by the whole wave: every pixel of
 // bbox-in-tile is tested with the wrapping-i32 edge functions of renderer.rs:329-341.
 // NANPASS = false: the main pass; a NaN fragment takes the key ZKEY_NAN_FRAG and raises *nanflag.
@@ -275,27 +295,16 @@ __device__ __forceinline__ void sweep_triangle(const RasterArgs &a, const TileCt
 {
     const RasterRec *__restrict__ r = a.recs + t;
     const float s0x = r->s[0], s0y = r->s[1], s1x = r->s[2], s1y = r->s[3], s2x = r->s[4], s2y = r->s[5];
-    // spi = (spf + 0.5) as i32 (renderer.rs:233-234; the record keeps spf only)
-    const int p0x = f32_as_i32(s0x + 0.5f), p0y = f32_as_i32(s0y + 0.5f), p1x = f32_as_i32(s1x + 0.5f), p1y = f32_as_i32(s1y + 0.5f);
-    const int p2x = f32_as_i32(s2x + 0.5f), p2y = f32_as_i32(s2y + 0.5f);
-    // clamped bbox (renderer.rs:285-298; clamp is monotone so it commutes with min/max)
-    int bx0 = clampi(min(p0x, min(p1x, p2x)), a.x0, a.x1), bx1 = clampi(max(p0x, max(p1x, p2x)), a.x0, a.x1);
-    int by0 = clampi(min(p0y, min(p1y, p2y)), a.y0, a.y1), by1 = clampi(max(p0y, max(p1y, p2y)), a.y0, a.y1);
-    bx0 = max(bx0, c.ax0); bx1 = min(bx1, c.ax0 + c.tw);        // ... intersected with this tile
-    by0 = max(by0, c.ay0); by1 = min(by1, c.ay0 + c.th);
+    const SweepSetup t3 = sweep_setup(r, a);
+    const int bx0 = max(t3.bx0, c.ax0), bx1 = min(t3.bx1, c.ax0 + c.tw);   // the clamped bbox intersected with this tile
+    const int by0 = max(t3.by0, c.ay0), by1 = min(t3.by1, c.ay0 + c.th);
     const int bw = bx1 - bx0, bh = by1 - by0;
     if (bw <= 0 || bh <= 0) return;
     const int npx = bw * bh;
-    // edge functions E = A*(cx - px) + B*(cy - py) in wrapping i32 (renderer.rs:329-331)
-    const uint32_t A01 = 0u - (uint32_t)(p1y - p0y), B01 = (uint32_t)(p1x - p0x);
-    const uint32_t A12 = 0u - (uint32_t)(p2y - p1y), B12 = (uint32_t)(p2x - p1x);
-    const uint32_t A20 = 0u - (uint32_t)(p0y - p2y), B20 = (uint32_t)(p0x - p2x);
-    const uint32_t E01o = A01 * (uint32_t)(bx0 - p0x) + B01 * (uint32_t)(by0 - p0y);
-    const uint32_t E12o = A12 * (uint32_t)(bx0 - p1x) + B12 * (uint32_t)(by0 - p1y);
-    const uint32_t E20o = A20 * (uint32_t)(bx0 - p2x) + B20 * (uint32_t)(by0 - p2y);
-    const uint32_t fl = r->flags;
-    // reject E < bias  <=>  accept E > bias-1   (bias 0 for top-left edges, else 1; :333-341)
-    const int thr01 = (fl & 2u) ? 0 : -1, thr12 = (fl & 4u) ? 0 : -1, thr20 = (fl & 8u) ? 0 : -1;
+    // the edge functions at the bbox origin; the walk below steps them by A per column and B per row
+    const uint32_t A01 = t3.A(0), B01 = t3.B(0), A12 = t3.A(1), B12 = t3.B(1), A20 = t3.A(2), B20 = t3.B(2);
+    const uint32_t E01o = t3.E(0, bx0, by0), E12o = t3.E(1, bx0, by0), E20o = t3.E(2, bx0, by0);
+    const int thr01 = t3.thr(0), thr12 = t3.thr(1), thr20 = t3.thr(2);
     const float r0 = r->rhw[0], r1 = r->rhw[1], r2 = r->rhw[2];
     // p -> (dx, dy): dy = floor((p + 0.5) / bw) via a 1-ulp reciprocal, exact for p < 1024, bw <= 32
     const float inv_bw = __builtin_amdgcn_rcpf((float)bw);
@@ -411,25 +420,16 @@ __global__ __launch_bounds__(256) void k_raster_entries(RasterArgs a, DevUniform
         const uint32_t t = slot_of_emission(a, i);
         const RasterRec *__restrict__ r = a.recs + t;
         const float s0x = r->s[0], s0y = r->s[1], s1x = r->s[2], s1y = r->s[3], s2x = r->s[4], s2y = r->s[5];
-        const int p0x = f32_as_i32(s0x + 0.5f), p0y = f32_as_i32(s0y + 0.5f), p1x = f32_as_i32(s1x + 0.5f), p1y = f32_as_i32(s1y + 0.5f);
-        const int p2x = f32_as_i32(s2x + 0.5f), p2y = f32_as_i32(s2y + 0.5f);
-        const int bx0 = clampi(min(p0x, min(p1x, p2x)), a.x0, a.x1), bx1 = clampi(max(p0x, max(p1x, p2x)), a.x0, a.x1);
-        const int by0 = clampi(min(p0y, min(p1y, p2y)), a.y0, a.y1), by1 = clampi(max(p0y, max(p1y, p2y)), a.y0, a.y1);
-        if (bx1 <= bx0 || by1 <= by0) continue;
-        const uint32_t A01 = 0u - (uint32_t)(p1y - p0y), B01 = (uint32_t)(p1x - p0x);
-        const uint32_t A12 = 0u - (uint32_t)(p2y - p1y), B12 = (uint32_t)(p2x - p1x);
-        const uint32_t A20 = 0u - (uint32_t)(p0y - p2y), B20 = (uint32_t)(p0x - p2x);
-        const uint32_t fl = r->flags;
-        const int thr01 = (fl & 2u) ? 0 : -1, thr12 = (fl & 4u) ? 0 : -1, thr20 = (fl & 8u) ? 0 : -1;
+        const SweepSetup t3 = sweep_setup(r, a);
+        if (t3.bx1 <= t3.bx0 || t3.by1 <= t3.by0) continue;
+        const int thr01 = t3.thr(0), thr12 = t3.thr(1), thr20 = t3.thr(2);
         const float r0 = r->rhw[0], r1 = r->rhw[1], r2 = r->rhw[2];
         for (int k = kmax; k >= 0; --k) {
             const int lx = ex + k * a.dstride, ly = ey - k;
             if (ly < 0 || ly >= a.win_h) continue;
             const int cx = a.x0 + lx, cy = a.y0 + ly;
-            if (cx < bx0 || cx >= bx1 || cy < by0 || cy >= by1) continue;
-            const int E01 = (int)(A01 * (uint32_t)(cx - p0x) + B01 * (uint32_t)(cy - p0y));
-            const int E12 = (int)(A12 * (uint32_t)(cx - p1x) + B12 * (uint32_t)(cy - p1y));
-            const int E20 = (int)(A20 * (uint32_t)(cx - p2x) + B20 * (uint32_t)(cy - p2y));
+            if (cx < t3.bx0 || cx >= t3.bx1 || cy < t3.by0 || cy >= t3.by1) continue;
+            const int E01 = (int)t3.E(0, cx, cy), E12 = (int)t3.E(1, cx, cy), E20 = (int)t3.E(2, cx, cy);
             if (!((E01 > thr01) & (E12 > thr12) & (E20 > thr20))) continue;
             ++n_cov;
             const Frag f = frag_eval(s0x, s0y, s1x, s1y, s2x, s2y, r0, r1, r2, cx, cy);
@@ -437,20 +437,8 @@ __global__ __launch_bounds__(256) void k_raster_entries(RasterArgs a, DevUniform
             if (f.rhw != f.rhw) ++n_nan;
             if (f.rhw < depth) continue;                                        // :363-365
             depth = f.rhw; id = tri_base + i; wrote = true;                     // :366
-            if constexpr (PS != FRR_PS_DEPTH) {
-                const float w = recip_exact(f.rhw != 0.0f ? f.rhw : 1.0f);      // :368
-                const float c0 = r0 * f.a * w, c1 = r1 * f.b * w, c2 = r2 * f.c * w;
-                float in[K > 0 ? K : 1];
-                if constexpr (K > 0) {
-                    const float *v = a.vary + (size_t)t * (3 * K);
-#pragma unroll
-                    for (int q = 0; q < K; ++q) in[q] = v[q] * c0 + v[K + q] * c1 + v[2 * K + q] * c2;
-                }
-                float col[4];
-                run_ps<PS>(u, in, col, nullptr);
-                reinterpret_cast<uint32_t *>(a.color)[(size_t)ly * a.cstride + lx] =
-                    quantize_u8(col[0]) | (quantize_u8(col[1]) << 8) | (quantize_u8(col[2]) << 16) | (quantize_u8(col[3]) << 24);
-            }
+            if constexpr (PS != FRR_PS_DEPTH)
+                reinterpret_cast<uint32_t *>(a.color)[(size_t)ly * a.cstride + lx] = shade_pixel<K, PS>(a, u, t, f, r0, r1, r2);
         }
     }
     if (wrote) { a.depth[e] = depth; a.tri_id[e] = id; }

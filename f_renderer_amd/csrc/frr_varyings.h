@@ -1,7 +1,7 @@
 // frr_varyings.h -- the ShaderContext the reference hands to the pixel shader (`input`, renderer.rs:368-378) as a device
 // buffer: frr_resolve_varyings writes, for every pixel of a window whose triangle-id entry names a triangle of the latest
-// geometry pass, the perspective-correct interpolation of that triangle's varyings at that pixel -- the value tile_resolve
-// (frr_raster.h) computes in registers and feeds to run_ps, with the same arithmetic in the same association.
+// geometry pass, the perspective-correct interpolation of that triangle's varyings at that pixel -- the value shade_pixel (frr_raster.h)
+// feeds to run_ps: the same fragment and weights (rec_frag, frag_weights: frr_device.h), the sums in the same association (vary_sums).
 //
 // The triangle-id target holds emission indices; the records and varyings live at SLOTS (frr_device.h: slots and order
 // keys).  slot_of_emission finds a slot with two binary searches of dependent loads, which is wrong once per pixel, so
@@ -97,20 +97,16 @@ template <int KT, bool VEC> __global__ __launch_bounds__(VARY_WG) void k_vary_re
     const uint32_t e = a.tri_id[i] - gt->tri_base;
     if (e >= gt->n_emit || e >= a.setup_cap) return;                           // not a triangle of this pass (or nothing drawn: ~0)
     const uint32_t t = min(a.table[e], a.setup_cap - 1u);                      // (a guard for the machine)
-    const uint4 *rp = reinterpret_cast<const uint4 *>(a.recs + t);
-    const uint4 q1 = rp[1], q2 = rp[2], q3 = rp[3];
-    const float r0 = u2f(q3.x), r1 = u2f(q3.y), r2 = u2f(q3.z);
-    const Frag f = frag_eval(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y), u2f(q2.z), u2f(q2.w), r0, r1, r2, cx, cy);   // :343-360
-    const float w = recip_exact(f.rhw != 0.0f ? f.rhw : 1.0f);                 // :368
-    const float c0 = r0 * f.a * w, c1 = r1 * f.b * w, c2 = r2 * f.c * w;       // :370-372
+    const RecFrag rf = rec_frag(a.recs + t, cx, cy);                           // :343-360
+    const float3 cw = frag_weights(rf.f, rf.r0, rf.r1, rf.r2);                 // :368-372
     const float *v = a.vary + (size_t)t * (size_t)(3 * K);
     float *o = a.out + i * (size_t)K;
     if constexpr (KT > 0) {
-        vary_sums<KT, VEC>(v, K, c0, c1, c2, o);
+        vary_sums<KT, VEC>(v, K, cw.x, cw.y, cw.z, o);
     } else {
         int k = 0;
-        for (; k + 4 <= K; k += 4) vary_sums<4, VEC>(v + k, K, c0, c1, c2, o + k);
-        for (; k < K; ++k) vary_sums<1, false>(v + k, K, c0, c1, c2, o + k);
+        for (; k + 4 <= K; k += 4) vary_sums<4, VEC>(v + k, K, cw.x, cw.y, cw.z, o + k);
+        for (; k < K; ++k) vary_sums<1, false>(v + k, K, cw.x, cw.y, cw.z, o + k);
     }
 }
 

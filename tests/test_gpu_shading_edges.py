@@ -151,3 +151,33 @@ def test_user_shader_phong_equals_the_builtin_and_the_oracle(oracle, user_phong,
         a, b = (x[k].view(np.uint32) if k == 1 else x[k] for x in (user, builtin))
         np.testing.assert_array_equal(a, b, err_msg=f"{name}: the user shader's {what} differ from the built-in's")
     _assert_equal(user, _want(oracle, name), f"{name} with the user shader")
+
+
+USER_PATH_SCENE = "normals_small/phong"
+
+
+def test_user_shader_on_the_entries_and_sweep_kernels_equals_the_builtin_and_the_oracle(oracle, user_phong):
+    """The user-shader builds of k_raster_entries (a window with x0 < 0) and of k_raster (option raster_sweep): the two tile
+    kernels of a user module that the test above does not launch.  No compile beyond the fixture's."""
+    r, sid = user_phong
+    sc = ss.all_scenes()[USER_PATH_SCENE]
+
+    def check(window, note):
+        f = _want(oracle, USER_PATH_SCENE, window)
+        drawn = f.tri_id.ravel() != 0xFFFFFFFF
+        shaded = drawn & (f.color.reshape(-1, 4) != np.array(ss.CLEAR, np.uint8)).any(axis=1)
+        assert shaded.any(), f"{note}: the oracle shades no pixel away from the clear colour"
+        builtin = ss.gpu_run(r, sc, window=window)
+        user = ss.gpu_run(r, sc, window=window, shader=sid)
+        _assert_equal(user, f, f"{USER_PATH_SCENE} with the user shader, {note}")
+        _assert_equal(builtin, f, f"{USER_PATH_SCENE} with the built-in pair, {note}")
+        for k, what in enumerate(("RGBA8", "depth", "ids")):
+            a, b = (x[k].view(np.uint32) if k == 1 else x[k] for x in (user, builtin))
+            np.testing.assert_array_equal(a, b, err_msg=f"{note}: the user shader's {what} differ from the built-in's")
+
+    check(ss.NEG_WINDOW, f"window {ss.NEG_WINDOW} (entries kernel)")
+    r.set_option("raster_sweep", 1)
+    try:
+        check(None, "raster_sweep (sweep kernel)")
+    finally:
+        r.set_option("raster_sweep", 0)
