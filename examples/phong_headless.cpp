@@ -10,6 +10,9 @@
 //       and FrameBuffer::load_file (renderer.rs:427-471, BGRA storage)
 //   a --wireframe anywhere among the arguments of the two forms above overlays the mesh's edges (FrameBuffer::draw_line,
 //       renderer.rs:540-588, over the setup triangles) in white after the shaded draw, on the device
+//   a --deferred anywhere among them shades the frame in a pass of its own: a depth-only pre-pass (FRR_PS_DEPTH), the pixel
+//       shader's input of every pixel's final owner read back (readback_varyings), and FRR_PS_PHONG run over that buffer
+//       (shade_varyings_host) -- the same bytes as the forward run
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
 //       loaders only (no GPU): what the two loaders produce, for the CPU-side check against the Python mirror
 #include <cmath>
@@ -29,10 +32,10 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false;
+    bool wireframe = false, deferred = false;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--wireframe") {
-            wireframe = true;
+        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred") {
+            (std::string(argv[i]) == "--wireframe" ? wireframe : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -53,7 +56,7 @@ int main(int argc, char **argv)
     if ((assets && argc < 7) || (!assets && argc < 8)) {
         std::cerr << "usage: phong_headless mesh.f32 ntris tex.rgba tex_size W H out.rgba [out.ppm]\n"
                      "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
-                     "       (--wireframe: overlay the mesh's edges)\n";
+                     "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -97,7 +100,14 @@ int main(int argc, char **argv)
 
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317
         renderer.geometry_processing(mesh);                                                     // loop A
-        renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_PHONG);                 // loop B
+        if (!deferred) {
+            renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_PHONG);             // loop B
+        } else {
+            renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_DEPTH);             // loop B without renderer.rs:380-381 ...
+            std::vector<float> varyings;
+            const int num_varyings = renderer.readback_varyings(varyings);                      // ... its `input` (:368-378) per pixel ...
+            renderer.shade_varyings_host(FRR_PS_PHONG, varyings, num_varyings);                 // ... and :380-381 over that buffer
+        }
         if (wireframe) renderer.draw_wireframe({255, 255, 255, 255});                           // the edges over the shaded frame
         renderer.read_frame_buffer(frame_buffer);                                               // phong.rs:386
 

@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("FRR_LIB") or os.path.join(_HERE, "libfrr_hip.so")  # FRR_LIB: developer override
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_lines.h", "frr_varyings.h", "frr_own.h")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_lines.h", "frr_varyings.h", "frr_shade.h", "frr_own.h")]
 _HDR = os.path.join(_ROOT, "include", "frr.h")
 
 HIPCC_FLAGS = [
@@ -129,6 +129,8 @@ SIGNATURES = {
     "frr_geometry_num_varyings": (C.c_int, [C.c_void_p]),
     "frr_resolve_varyings": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
     "frr_readback_varyings": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
+    "frr_shade_varyings": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32]),
+    "frr_shade_varyings_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32]),
     "frr_host_line_pixels": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
     "frr_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "frr_set_uniforms": (C.c_int, [C.c_void_p, _P(Uniforms)]),

@@ -4,6 +4,7 @@
 #include "frr_tile_order.h"
 #include "frr_lines.h"
 #include "frr_varyings.h"
+#include "frr_shade.h"
 #include "frr_own.h"
 
 #include <math.h>
@@ -30,9 +31,10 @@ FRR_EMBED(frr_src_device_h, "frr_device.h");
 FRR_EMBED(frr_src_exact_h, "frr_exact.h");
 FRR_EMBED(frr_src_kernels_h, "frr_kernels.h");
 FRR_EMBED(frr_src_raster_h, "frr_raster.h");
+FRR_EMBED(frr_src_shade_h, "frr_shade.h");
 FRR_EMBED(frr_src_frr_h, "../../include/frr.h");
 #endif
-extern "C" const char frr_src_device_h[], frr_src_exact_h[], frr_src_kernels_h[], frr_src_raster_h[], frr_src_frr_h[];
+extern "C" const char frr_src_device_h[], frr_src_exact_h[], frr_src_kernels_h[], frr_src_raster_h[], frr_src_shade_h[], frr_src_frr_h[];
 
 using namespace frr;
 
@@ -81,7 +83,7 @@ constexpr int kSpanShapes[6][2] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIG
 struct UserShader {
     int nf = 0, K = 0;
     std::vector<char> code;
-    std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel)
+    std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6], shade[2];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel; shade: k_shade_vary [16-byte loads])
 };
 std::mutex g_shader_mu;
 std::vector<UserShader *> g_shaders;      // id = FRR_SHADER_USER_BASE + index; never shrinks
@@ -116,7 +118,7 @@ void release_stream(int device, hipStream_t st)
 
 struct UserModule {
     hipModule_t mod = nullptr;
-    hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {};
+    hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {}, shade[2] = {};
 };
 
 // One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
@@ -202,7 +204,7 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER, LINES, VARY } kind;
+    enum Kind { GEOM, RASTER, LINES, VARY, SHADE } kind;
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -214,6 +216,9 @@ struct Cmd {
     int lines = -1; uint32_t wire_rgba = 0;
     // VARY (frr_resolve_varyings): the window in x0 .. y1 and the caller's buffer
     float *vary_out = nullptr;
+    // SHADE (frr_shade_varyings): the window in x0 .. y1, the shader in ps, the buffer ([shade_entries][shade_K]: the caller's,
+    // or one of frr_ctx::shade_tmp) and the range of triangle ids
+    const float *shade_in = nullptr; uint64_t shade_entries = 0; int shade_K = 0; uint32_t id_first = 0, id_count = 0;
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
@@ -275,6 +280,9 @@ struct frr_ctx {
     uint32_t join_epoch = 1, joined_g = 0;   // (joined_g: gstream's; a frame stream's is FrameStream::joined)
     // command log since the last synchronisation point / frr_clear (finish(): replay)
     std::vector<Cmd> log;
+    // frr_shade_varyings_host: the device copies of the callers' buffers, one per logged command that reads one (Cmd::shade_in
+    // is a view of it); freed whenever the log is (drop_log)
+    std::vector<DevBuf<float>> shade_tmp;
     uint32_t next_seq = 1, epoch = 1;
     uint32_t replays = 0;           // replays since frr_clear (frr_stats.replays)
     bool in_replay = false;
@@ -395,6 +403,14 @@ int ensure_own_set(frr_ctx *c, int t)
                     (c->own_depth[t] || c->own_depth[t].reset(npx) == hipSuccess) &&
                     (c->own_tri_id[t] || c->own_tri_id[t].reset(npx) == hipSuccess);
     return ok ? FRR_OK : nomem(c, "frame targets");
+}
+
+// the logged commands are history: nothing replays them any more, so the buffers they alone read go too (hipFree waits for
+// the device: a shade of a frame still in flight has read its copy by the time it is freed)
+void drop_log(frr_ctx *c)
+{
+    c->log.clear();
+    c->shade_tmp.clear();
 }
 
 // all streams idle
@@ -615,6 +631,8 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
     HIP_TRY(c, hipModuleGetFunction(&m.entries, m.mod, us->entries.c_str()));
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) HIP_TRY(c, hipModuleGetFunction(&m.span[cnt][sh], m.mod, us->span[cnt][sh].c_str()));
+    for (int vec = 0; vec < 2; ++vec)
+        if (!us->shade[vec].empty()) HIP_TRY(c, hipModuleGetFunction(&m.shade[vec], m.mod, us->shade[vec].c_str()));   // ([1]: only where K is a multiple of 4)
     *out = &(c->user_modules[id] = m);
     return FRR_OK;
 }
@@ -1200,6 +1218,54 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_shade_varyings: a pixel shader over a buffer of varyings into the colour target (frr_shade.h).  It writes a target, so it
+// is ordered like a line list: on the targets' stream, behind a pending frr_clear and the streams of pending frr_frame_wait
+// calls (the caller's writes of the buffer).  It reads nothing of a geometry pass, cannot fail on the device and owns no
+// device table, so a replay runs it again in its place -- behind a failed command it writes nothing (seq_cancelled).
+template <int K, int PS> void launch_shade(hipStream_t ts, dim3 grid, const ShadeArgs &a, const DevUniforms &du, bool vec)
+{
+    if constexpr (K > 0 && K % 4 == 0) { if (vec) { hipLaunchKernelGGL((k_shade_vary<K, PS, true>), grid, dim3(SHADE_WG), 0, ts, a, du); return; } }
+    hipLaunchKernelGGL((k_shade_vary<K, PS, false>), grid, dim3(SHADE_WG), 0, ts, a, du);
+}
+int exec_shade(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    int rc;
+    const UserModule *um = nullptr;
+    if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
+    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    hipStream_t ts;
+    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    ShadeArgs a;
+    memset(&a, 0, sizeof a);
+    a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
+    a.cstride = (int32_t)c->W;
+    a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
+    a.id_first = cmd.id_first; a.id_count = cmd.id_count;
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    a.tri_id = f.tri_id; a.in = cmd.shade_in; a.in_entries = cmd.shade_entries;
+    a.color = (uint32_t *)f.color;
+    const dim3 grid((unsigned)((ww + SHADE_WG - 1) / SHADE_WG), (unsigned)wh);
+    // 16-byte loads where every entry's address allows them: K a multiple of 4 and an aligned buffer
+    const bool vec = cmd.shade_K > 0 && (cmd.shade_K & 3) == 0 && ((uintptr_t)cmd.shade_in & 15u) == 0u;
+    if (um) {
+        ShadeArgs sa = a; DevUniforms d = cmd.duni;
+        void *args[] = {&sa, &d};
+        (void)hipModuleLaunchKernel(um->shade[vec ? 1 : 0], grid.x, grid.y, 1, SHADE_WG, 1, 1, 0, ts, args, nullptr);
+    } else {
+        switch (cmd.ps) {
+        case FRR_PS_FLAT: launch_shade<0, FRR_PS_FLAT>(ts, grid, a, cmd.duni, false); break;   // (reads no varying, whatever K the buffer has)
+        case FRR_PS_COLOR: launch_shade<3, FRR_PS_COLOR>(ts, grid, a, cmd.duni, false); break;
+        case FRR_PS_PHONG: launch_shade<8, FRR_PS_PHONG>(ts, grid, a, cmd.duni, vec); break;
+        case FRR_PS_BLINN: launch_shade<8, FRR_PS_BLINN>(ts, grid, a, cmd.duni, vec); break;
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    cmd.lane = f.lane;
+    return FRR_OK;
+}
+
 int finish(frr_ctx *c);
 
 // run a command and remember it (finish() replays the commands from a failed one onwards)
@@ -1208,7 +1274,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : exec_vary(c, cmd);
+    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : exec_shade(c, cmd);
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1276,10 +1342,10 @@ int finish(frr_ctx *c)
         // the device tables as they were before the failed command: it has used its own parity's cursors (and, when its
         // block sums were scanned inside the next raster pass's binning launch, that pass has reserved bin space)
         h.first_bad = SEQ_NONE; h.overflow = 0u;
-        // (line and varyings commands in between own no table: the "next" command is the next geometry or raster pass)
+        // (line, varyings and shade commands in between own no table: the "next" command is the next geometry or raster pass)
         for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
-            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY) continue;
+            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE) continue;
             ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
@@ -1310,7 +1376,7 @@ int finish(frr_ctx *c)
         c->fs.rank = now.rank; c->fs.world = now.world; c->fs.part_blocked = now.part_blocked;
         if ((rc = settle(c)) != FRR_OK) return rc;
     }
-    c->log.clear();
+    drop_log(c);
     c->epoch = c->next_seq;
     if (c->next_seq > 0xF0000000u) {   // sequence numbers start over (nothing is in flight)
         const uint32_t none = SEQ_NONE;
@@ -1770,11 +1836,11 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     src += "#define FRR_USER_NF " + std::to_string(vs_input_floats) + "\n#define FRR_USER_K " + std::to_string(num_varyings) + "\n";
     src += "#include \"frr_device.h\"\n#line 1 \"user_shader\"\n";
     src += hip_source;
-    src += "\n#include \"frr_kernels.h\"\n";
-    const char *hdr_txt[] = {frr_src_device_h, frr_src_exact_h, frr_src_kernels_h, frr_src_raster_h, frr_src_frr_h};
-    const char *hdr_name[] = {"frr_device.h", "frr_exact.h", "frr_kernels.h", "frr_raster.h", "../../include/frr.h"};
+    src += "\n#include \"frr_kernels.h\"\n#include \"frr_shade.h\"\n";
+    const char *hdr_txt[] = {frr_src_device_h, frr_src_exact_h, frr_src_kernels_h, frr_src_raster_h, frr_src_shade_h, frr_src_frr_h};
+    const char *hdr_name[] = {"frr_device.h", "frr_exact.h", "frr_kernels.h", "frr_raster.h", "frr_shade.h", "../../include/frr.h"};
     hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "frr_user_program.hip", 5, hdr_txt, hdr_name) != HIPRTC_SUCCESS) return fail(c, FRR_ERR_HIP, "hiprtcCreateProgram");
+    if (hiprtcCreateProgram(&prog, src.c_str(), "frr_user_program.hip", 6, hdr_txt, hdr_name) != HIPRTC_SUCCESS) return fail(c, FRR_ERR_HIP, "hiprtcCreateProgram");
     UserShader *us = new UserShader();
     us->nf = vs_input_floats; us->K = num_varyings;
     const std::string U = std::to_string(FRR_SHADER_USER_BASE), Ks = std::to_string(num_varyings);
@@ -1786,6 +1852,10 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     (void)hiprtcAddNameExpression(prog, sweep_expr.c_str());
     const std::string entries_expr = "frr::k_raster_entries<" + Ks + ", " + U + ">";   // windows whose rows share depth entries (x0 < 0)
     (void)hiprtcAddNameExpression(prog, entries_expr.c_str());
+    // frr_shade_varyings (frr_shade.h): scalar loads, and -- where K allows them -- 16-byte loads
+    const bool shade_vec = num_varyings > 0 && num_varyings % 4 == 0;
+    const std::string shade_expr[2] = {"frr::k_shade_vary<" + Ks + ", " + U + ", false>", "frr::k_shade_vary<" + Ks + ", " + U + ", true>"};
+    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) (void)hiprtcAddNameExpression(prog, shade_expr[vec].c_str());
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh)
             exprs.push_back("frr::k_raster_span<" + Ks + ", " + U + ", " + (cnt ? "true" : "false") + ", " + std::to_string(kSpanShapes[sh][0]) + ", " + std::to_string(kSpanShapes[sh][1]) + ">");
@@ -1804,6 +1874,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     bool ok = true;
     auto lowered = [&](const std::string &e) { const char *n = nullptr; ok = ok && hiprtcGetLoweredName(prog, e.c_str(), &n) == HIPRTC_SUCCESS && n; return std::string(n ? n : ""); };
     us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->geom_idx = lowered(geom_idx_expr); us->clip_idx = lowered(clip_idx_expr); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
+    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) us->shade[vec] = lowered(shade_expr[vec]);
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
     size_t cs = 0;
@@ -1829,7 +1900,7 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
     if (c->host_bad && *(volatile uint32_t *)c->host_bad != c->seen_bad) { const int rc = finish(c); if (rc != FRR_OK) return rc; }
     // A new frame: the commands logged so far are history.  (One of them may have failed unseen: it and everything after
     // it left the targets untouched, and they are overwritten now.  Device statistics are tagged with the frame number.)
-    c->log.clear();
+    drop_log(c);
     c->epoch = c->next_seq;
     c->replays = 0;
     f.frame_no += 1;
@@ -2114,6 +2185,77 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     if (rc != FRR_OK) return rc;
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy varyings: ") + hipGetErrorString(e));
     return FRR_OK;
+}
+
+// argument checks of frr_shade_varyings / frr_shade_varyings_host; *nothing: the call is valid and writes nothing
+static int shade_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t in_entries, int K, uint32_t id_count, bool *nothing)
+{
+    if (!c) return FRR_ERR_INVALID;
+    if (x1 <= x0 || y1 <= y0) return fail(c, FRR_ERR_INVALID, "empty or inverted window");
+    if (x0 < 0) return fail(c, FRR_ERR_UNSUPPORTED, "x0 < 0: pixels of neighbouring rows share depth entries, an entry has no single pixel");
+    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
+    if (ww > (int64_t)c->W || wh > (int64_t)c->H) return fail(c, FRR_ERR_INVALID, "window larger than the FrameBuffer");
+    if (y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_INVALID, "window coordinates outside the i16 range");
+    if ((wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H)
+        return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
+    // the rule frr_raster applies between a pixel shader and the geometry's K (raster_check), with the buffer's K
+    if (ps_id >= FRR_SHADER_USER_BASE) {
+        const UserShader *us = user_shader(ps_id);
+        if (!us) return fail(c, FRR_ERR_INVALID, "unknown shader id");
+        if (us->K != K) return fail(c, FRR_ERR_INVALID, "the user pixel shader's varyings do not match the buffer's K");
+    } else if (ps_id == FRR_PS_DEPTH) {
+        return fail(c, FRR_ERR_INVALID, "FRR_PS_DEPTH: nothing to shade");
+    } else if (ps_id < 0 || ps_id > FRR_PS_BLINN || K < 0 || K > FRR_MAX_VARYINGS || (ps_id == FRR_PS_COLOR && K != 3) || ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && K != 8)) {
+        return fail(c, FRR_ERR_INVALID, "pixel shader does not match the buffer's K");
+    }
+    if ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && !c->duni.tex) return fail(c, FRR_ERR_INVALID, "no texture bound to uniforms.texture_slot");
+    if ((K > 0 && !buf) || ((uintptr_t)buf & 3u)) return fail(c, FRR_ERR_INVALID, "varyings buffer is NULL or not 4-byte aligned");
+    if (in_entries < (uint64_t)wh * (uint64_t)x1) return fail(c, FRR_ERR_INVALID, "in_entries < (y1 - y0) * x1");
+    *nothing = id_count == 0u;
+    return FRR_OK;
+}
+static Cmd shade_cmd(const frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *dev_in, uint64_t in_entries, int K, uint32_t id_first, uint32_t id_count)
+{
+    Cmd cmd;
+    cmd.kind = Cmd::SHADE; cmd.ps = ps_id; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.duni = c->duni;
+    cmd.shade_in = dev_in; cmd.shade_entries = in_entries; cmd.shade_K = K; cmd.id_first = id_first; cmd.id_count = id_count;
+    return cmd;
+}
+
+int frr_shade_varyings(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *dev_in_f32, uint64_t in_entries, int K,
+                       uint32_t id_first, uint32_t id_count)
+{
+    bool nothing = false;
+    const int rc = shade_check(c, ps_id, x0, x1, y0, y1, dev_in_f32, in_entries, K, id_count, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return exec_cmd(c, shade_cmd(c, ps_id, x0, x1, y0, y1, (const float *)dev_in_f32, in_entries, K, id_first, id_count));
+}
+
+int frr_shade_varyings_host(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *host_in, uint64_t in_entries, int K,
+                            uint32_t id_first, uint32_t id_count)
+{
+    bool nothing = false;
+    int rc = shade_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, id_count, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the part of the caller's array the window can index, as a device buffer the ctx owns for as long as the command is logged
+    const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
+    DevBuf<float> tmp;
+    if (K > 0) {
+        if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
+        // (returns when the copy is done: in front of the command on any stream)
+        HIP_TRY(c, hipMemcpy(tmp, host_in, (size_t)entries * (size_t)K * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const float *dev = tmp;
+    if (K > 0) c->shade_tmp.push_back(std::move(tmp));
+    rc = exec_cmd(c, shade_cmd(c, ps_id, x0, x1, y0, y1, dev, entries, K, id_first, id_count));
+    // a command that failed on the host is not logged, and nothing will replay it: its copy goes now.  (A synchronisation
+    // point inside exec_cmd has dropped log and copies alike.)
+    bool logged = false;
+    for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == Cmd::SHADE && c->log[k].shade_in == dev;
+    if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
+    return rc;
 }
 
 int frr_get_stats(frr_ctx *c, frr_stats *out)

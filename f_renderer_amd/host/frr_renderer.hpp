@@ -453,6 +453,41 @@ public:
         return num_varyings > 0 ? num_varyings : 0;
     }
     int readback_varyings(std::vector<float> &out, float fill = 0.0f) { return readback_varyings(out, {0, (int32_t)width_}, {0, (int32_t)height_}, fill); }
+    int geometry_num_varyings()
+    {
+        const int num_varyings = frr_geometry_num_varyings(ctx_);
+        if (num_varyings < 0) throw Error(FRR_ERR_INVALID, "geometry_num_varyings before geometry_processing");
+        return num_varyings;
+    }
+    // pixel_shader over a buffer of varyings, f32 [entries][K], into the colour target: every pixel of the window whose triangle
+    // id is not 0xFFFFFFFF and satisfies id - id_first < id_count becomes vec4_to_u8_array(pixel_shader(uniforms, &in[i * K])),
+    // i = (cy - y0) * x1 + (cx - x0); every other pixel, depth, ids and stats() are untouched (include/frr.h:
+    // frr_shade_varyings).  Device memory that stays allocated and unchanged until sync or the next clear; no host wait.
+    void shade_varyings(int pixel_shader, const void *dev_in_f32, uint64_t entries, int num_varyings, std::pair<int32_t, int32_t> width_range,
+                        std::pair<int32_t, int32_t> height_range, uint32_t id_first = 0, uint32_t id_count = 0xFFFFFFFFu)
+    {
+        check(frr_shade_varyings(ctx_, pixel_shader, width_range.first, width_range.second, height_range.first, height_range.second, dev_in_f32, entries,
+                                 num_varyings, id_first, id_count));
+    }
+    void shade_varyings(int pixel_shader, const void *dev_in_f32, uint64_t entries, int num_varyings, uint32_t id_first = 0, uint32_t id_count = 0xFFFFFFFFu)
+    {
+        shade_varyings(pixel_shader, dev_in_f32, entries, num_varyings, {0, (int32_t)width_}, {0, (int32_t)height_}, id_first, id_count);
+    }
+    // the same from host memory: `in` holds entries * K floats, entries = in.size() / K (K == 0: none are read); copied to the
+    // device inside the call
+    void shade_varyings_host(int pixel_shader, const std::vector<float> &in, int num_varyings, std::pair<int32_t, int32_t> width_range,
+                             std::pair<int32_t, int32_t> height_range, uint32_t id_first = 0, uint32_t id_count = 0xFFFFFFFFu)
+    {
+        const int64_t rows = (int64_t)height_range.second - height_range.first;
+        const uint64_t window = rows > 0 && width_range.second > 0 ? (uint64_t)rows * (uint64_t)width_range.second : 0;
+        const uint64_t entries = num_varyings > 0 ? (uint64_t)in.size() / (uint64_t)num_varyings : window;
+        check(frr_shade_varyings_host(ctx_, pixel_shader, width_range.first, width_range.second, height_range.first, height_range.second,
+                                      in.empty() ? nullptr : in.data(), entries, num_varyings, id_first, id_count));
+    }
+    void shade_varyings_host(int pixel_shader, const std::vector<float> &in, int num_varyings, uint32_t id_first = 0, uint32_t id_count = 0xFFFFFFFFu)
+    {
+        shade_varyings_host(pixel_shader, in, num_varyings, {0, (int32_t)width_}, {0, (int32_t)height_}, id_first, id_count);
+    }
     frr_stats stats() { frr_stats s; check(frr_get_stats(ctx_, &s)); return s; }
     frr_ctx *raw() { return ctx_; }
 

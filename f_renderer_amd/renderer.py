@@ -430,6 +430,43 @@ class Renderer:
         self._check(self._lib.frr_readback_varyings(self._ctx, int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), buf.ctypes.data, entries))
         return out
 
+    def geometry_num_varyings(self):
+        """K of the last geometry_processing / draw: what sizes the buffers of resolve_varyings and shade_varyings."""
+        k = self._lib.frr_geometry_num_varyings(self._ctx)
+        if k < 0:
+            raise FrrError(N.FRR_ERR_INVALID, "geometry_num_varyings before geometry_processing")
+        return k
+
+    def shade_varyings(self, pixel_shader, buf, entries=None, K=None, width_range=None, height_range=None, ids=(0, 0xFFFFFFFF)):
+        """pixel_shader over a buffer of varyings into the colour target (frr_shade_varyings): every pixel of the window whose
+        triangle id lies in ids = (first, count) -- id != 0xFFFFFFFF and id - first < count -- becomes
+        vec4_to_u8_array(pixel_shader(uniforms, buf[i])), i = (cy - y0) * x1 + (cx - x0); every other pixel, depth, ids and
+        stats() are untouched.  `buf`: a device pointer to float32 [entries][K] (e.g. a torch tensor's data_ptr(); it stays
+        allocated and unchanged until sync() or the next clear(); no host wait), or a NumPy array [entries, K], which is
+        copied to the device inside the call (frr_shade_varyings_host).  entries defaults to (y1 - y0) * x1 (or the
+        array's rows), K to the array's columns, else to geometry_num_varyings().  The uniforms are those of the call."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        host = isinstance(buf, np.ndarray)
+        if host:
+            a = np.ascontiguousarray(buf, np.float32)
+            if K is None:
+                K = a.shape[-1] if a.ndim >= 2 else self.geometry_num_varyings()
+            if entries is None:
+                entries = a.size // K if K else max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
+            need = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0) * int(K)
+            if a.size < min(int(entries) * int(K), need):
+                raise FrrError(N.FRR_ERR_INVALID, "shade_varyings: the array is smaller than entries * K")
+            ptr, fn = (a.ctypes.data if a.size else 0), self._lib.frr_shade_varyings_host
+        else:
+            if K is None:
+                K = self.geometry_num_varyings()
+            if entries is None:
+                entries = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
+            ptr, fn = int(buf or 0), self._lib.frr_shade_varyings
+        self._check(fn(self._ctx, int(pixel_shader), int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), C.c_void_p(ptr), int(entries), int(K),
+                       int(ids[0]) & 0xFFFFFFFF, int(ids[1]) & 0xFFFFFFFF))
+
     def frame_fence(self, stream=None):
         """`stream` (a hipStream_t handle, e.g. torch's stream.cuda_stream; None = the ctx's stream) waits for every frame
         issued so far -- no host wait (frr_frame_fence; option bound_targets_in_flight)."""

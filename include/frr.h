@@ -355,6 +355,50 @@ int frr_geometry_num_varyings(const frr_ctx *ctx);
 int frr_resolve_varyings(frr_ctx *ctx, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_f32, uint64_t out_entries);
 int frr_readback_varyings(frr_ctx *ctx, int32_t x0, int32_t x1, int32_t y0, int32_t y1, float *host_inout, uint64_t out_entries);
 
+/* ---- shading a varyings buffer (the other half of deferred shading) ------------------------- */
+/* The step from the pixel shader's input to the colour target -- renderer.rs:380-381 with vec4_to_u8_array (:7-14) and
+ * set_pixel (:497-503) -- over a buffer of varyings, pixel-major f32 [in_entries][K]: what frr_resolve_varyings wrote, or
+ * anything the caller made.
+ *   window  (x0, x1) x (y0, y1).  Pixel (cx, cy) has the depth index i = (cy - y0) * x1 + (cx - x0) (renderer.rs:362).
+ *   id      the current frame's triangle-id target at i: the frame-global emission index of the pixel's owner, 0xFFFFFFFF
+ *           where nothing was drawn.
+ * The pixel is shaded where id != 0xFFFFFFFF and id - id_first < id_count (unsigned).  A shaded pixel's colour, at
+ * (cx - x0, cy - y0) with row stride = the ctx's width -- exactly where frr_raster writes it -- becomes
+ * vec4_to_u8_array(pixel_shader(uniforms, &in[i * K])): the shader and the quantisation of the tile kernel's resolve, the
+ * same functions with no contraction, so a FRR_PS_DEPTH draw + frr_resolve_varyings + frr_shade_varyings leaves the colour
+ * of the forward draw bit for bit.  EVERY OTHER COLOUR PIXEL IS LEFT UNTOUCHED, and so are depth, triangle ids and every
+ * field of frr_stats.  id_first = 0, id_count = 0xFFFFFFFF: every drawn pixel; id_count = 0: FRR_OK, nothing written.
+ * Ranges of ids are how one G-buffer takes pixel uniforms per range of triangles: set the uniforms, shade a range, set
+ * others, shade the next (phong.rs:361-370 as three calls).
+ * It needs no geometry pass: it reads only the buffer, the id target and the uniforms, so it also works after a frr_draw
+ * that filtered the setup list on a partitioned ctx, and after a frr_clear (nothing is drawn: nothing is written).
+ * Uniforms: textures, frr_set_uniforms and frr_set_user_uniforms as of the call travel with the command, as with a draw; a
+ * replay shades with the uniforms of the original call.
+ * ps_id and K follow the rule frr_raster applies between a pixel shader and its geometry's K: FRR_PS_COLOR needs K = 3,
+ * FRR_PS_PHONG / FRR_PS_BLINN K = 8 and a texture in uniforms.texture_slot, a user id the K it was registered with;
+ * FRR_PS_FLAT takes any 0 <= K <= FRR_MAX_VARYINGS (with K == 0 the buffer may be NULL); FRR_PS_DEPTH has nothing to shade.
+ * frr_shade_varyings: dev_in_f32 is device memory, 4-byte aligned; where K is a multiple of 4 and the buffer 16-byte
+ * aligned the entries are read with 16-byte loads.  It is a command that writes a target, like frr_draw_lines: it runs on
+ * the current frame's stream behind the draws, resolves and lines issued before it and before those issued after it,
+ * settles a pending frr_clear first, waits for the streams of pending frr_frame_wait calls (how a caller who filled the
+ * buffer on a stream of its own orders that write before the shade), uses the current target set (own or caller-bound, one
+ * or two frames in flight) and waits for nothing on the host.  Behind a command that found a work list too small it writes
+ * nothing and is replayed with that command, so THE BUFFER MUST STAY ALLOCATED AND UNCHANGED until the next
+ * synchronisation point or frr_clear, like the output of frr_resolve_varyings.  On a partitioned ctx only the pixels of
+ * the window's tile rows this rank owns are written.
+ * frr_shade_varyings_host: the same from host memory -- the first (y1 - y0) * x1 entries of host_in are copied into a
+ * temporary device buffer (the call returns when the copy is done: host_in may be reused at once) that the ctx keeps
+ * until the next synchronisation point or frr_clear, where a replay still finds it.
+ * Errors.  FRR_ERR_INVALID: in_entries < (y1 - y0) * x1; x1 <= x0, y1 <= y0 or a window beyond what frr_raster accepts; a
+ * NULL buffer (with K > 0) or one not 4-byte aligned; a ps_id or K the rule above refuses.  FRR_ERR_UNSUPPORTED: x0 < 0 --
+ * as for frr_resolve_varyings, an entry has no single pixel there. */
+int frr_shade_varyings(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                       const void *dev_in_f32, uint64_t in_entries, int K,
+                       uint32_t id_first, uint32_t id_count);
+int frr_shade_varyings_host(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                            const float *host_in, uint64_t in_entries, int K,
+                            uint32_t id_first, uint32_t id_count);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to
