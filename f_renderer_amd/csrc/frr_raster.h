@@ -589,6 +589,7 @@ __device__ __forceinline__ void hiz_rebuild(const unsigned long long *s_key, uin
 // With B = 16 staged triangles per wave and NW = 4 that is 18.0 KiB (19.0 textured): eight workgroups per CU;
 // with B = 32 it is 23.9 KiB: six.
 template <int NW, int B> struct SpanLds {
+    static constexpr int WAVES = NW, BATCH = B;
     static constexpr int KEY = 0;
     static constexpr int U0 = KEY + TILE_PX * 8;
     // main loop, per wave
@@ -608,59 +609,336 @@ template <int NW, int B> struct SpanLds {
     static constexpr int U1 = M_END > P_END ? M_END : P_END;
     static constexpr int HZ = U1;                       // u32[HZ_SIZE] hierarchical z (see hiz_rebuild)
     static constexpr int BKT = HZ + ((HZ_SIZE + 3) & ~3) * 4; // u32[BKT_N]
-    static constexpr int SCAL = BKT + BKT_N * 4;        // u32[8]: next, dirty, ebase, -, w4[4]
+    static constexpr int SCAL = BKT + BKT_N * 4;        // u32[8]: next, dirty, ebase, nanflag, w4[4]
     static constexpr int U8 = SCAL + 8 * 4;             // float[256] (textured shaders)
     static constexpr int bytes(bool textured) { return U8 + (textured ? 256 * 4 : 0); }
+    static_assert(B <= 32, "staging slots are five bits of a span descriptor, first rows ten bits of SpanTri::misc");
+    static_assert(U1 - U0 >= TILE_PX * 4, "the NaN pass keeps one u32 per pixel in the staging region");
+    // The typed view of it: what lies where in the kernel's buffer `lds` (per-wave arrays: [wave][slot]).  The pointers are formed
+    // where a phase uses them: held in a struct they would reach the phases through memory, and the code generated changes.
+    template <class T> static __device__ __forceinline__ T *at(unsigned char *lds, int off) { return reinterpret_cast<T *>(lds + off); }
+    static __device__ __forceinline__ unsigned long long *key(unsigned char *lds) { return at<unsigned long long>(lds, KEY); }
+    static __device__ __forceinline__ auto tri(unsigned char *lds) { return at<SpanTri[B]>(lds, TRI); }
+    static __device__ __forceinline__ auto fa(unsigned char *lds) { return at<float4[B]>(lds, FA); }
+    static __device__ __forceinline__ auto fb(unsigned char *lds) { return at<float4[B]>(lds, FB); }
+    static __device__ __forceinline__ auto fc(unsigned char *lds) { return at<float2[B]>(lds, FC); }
+    static __device__ __forceinline__ auto hrow(unsigned char *lds) { return at<unsigned long long[B / 2]>(lds, HROW); }
+    static __device__ __forceinline__ auto hfrag(unsigned char *lds) { return at<unsigned long long[32]>(lds, HFRAG); }
+    static __device__ __forceinline__ auto q(unsigned char *lds) { return at<uint32_t[64]>(lds, Q); }
+    static __device__ __forceinline__ uint32_t *segpre(unsigned char *lds) { return at<uint32_t>(lds, SEGPRE); }
+    static __device__ __forceinline__ uint32_t *segsrc(unsigned char *lds) { return at<uint32_t>(lds, SEGSRC); }
+    static __device__ __forceinline__ uint4 *exch(unsigned char *lds) { return at<uint4>(lds, EXCH); }
+    static __device__ __forceinline__ uint32_t *hz(unsigned char *lds) { return at<uint32_t>(lds, HZ); }
+    static __device__ __forceinline__ uint32_t *bkt(unsigned char *lds) { return at<uint32_t>(lds, BKT); }
+    static __device__ __forceinline__ uint32_t &next(unsigned char *lds) { return *at<uint32_t>(lds, SCAL); }
+    static __device__ __forceinline__ uint32_t &dirty(unsigned char *lds) { return *at<uint32_t>(lds, SCAL + 4); }     // keys changed since the hierarchical z was last rebuilt
+    static __device__ __forceinline__ uint32_t &ebase(unsigned char *lds) { return *at<uint32_t>(lds, SCAL + 8); }
+    static __device__ __forceinline__ uint32_t &nanflag(unsigned char *lds) { return *at<uint32_t>(lds, SCAL + 12); }  // some fragment of this tile had a NaN rhw: second pass (tile_nan_begin)
+    static __device__ __forceinline__ uint32_t *w4(unsigned char *lds) { return at<uint32_t>(lds, SCAL + 16); }
+    static __device__ __forceinline__ uint32_t *nanL(unsigned char *lds) { return at<uint32_t>(lds, U0); }             // that pass's per-pixel ids; over the staging, after the main loop
+    static __device__ __forceinline__ float *u8(unsigned char *lds) { return at<float>(lds, U8); }                     // (float)i / 255.0f for the texture taps of the resolve
+};
+// FRR_DEBUG_COUNTERS builds (tools/debug_counters.py, tools/tile_timeline.py): the funnel counters, the wave-cycles per
+// phase and the workgroup's timeline, added to Counters::dbg (slots 0..10, 12..19, 20) and written to RasterArgs::dbg_tiles.
+// Every other build gets the empty twin below: the kernel calls the same methods and nothing is left of them.
+#ifdef FRR_DEBUG_COUNTERS
+struct SpanDbg {
+    // wave-cycles per phase (s_memtime): 0 pre-pass, 1 phase 1a, 2 hi-z rebuild, 3 phase 1b, 4 phase 2, 5 phase 3,
+    // 6 wait at the final barrier, 7 resolve
+    unsigned long long tlast = __builtin_amdgcn_s_memtime();
+    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime(); // 100 MHz, the same counter on every XCD
+    unsigned long long rt1 = 0, rt2 = 0;
+    uint32_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t tri = 0, alive = 0, rows = 0, spans = 0, spans_live = 0, frags = 0, fwin = 0, rwin = 0;
+    uint32_t pre = 0, win = 0, rebuilds = 0; // fragments a per-pixel zub test would skip; fragments that took the pixel; hi-z rebuilds
+    __device__ __forceinline__ void T(int i) { const unsigned long long now = __builtin_amdgcn_s_memtime(); t[i] += (uint32_t)(now - tlast); tlast = now; }
+    __device__ __forceinline__ void main_loop_begins() { rt1 = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void rebuilt() { ++rebuilds; }
+    __device__ __forceinline__ void culled(bool nonempty, bool survives) { tri += __popcll(__ballot(nonempty)); alive += __popcll(__ballot(survives)); }
+    __device__ __forceinline__ void row_window(bool ractive, int len) { rwin++; rows += __popcll(__ballot(ractive)); spans += __popcll(__ballot(len > 0)); }
+    __device__ __forceinline__ void live_spans(unsigned long long nz) { spans_live += __popcll(nz); }
+    __device__ __forceinline__ void fragments(int F) { frags += F; fwin += (F + 63) / 64; }
+    __device__ __forceinline__ void key_update(unsigned long long old, unsigned long long key, const SpanTri &t)
+    {
+        pre += __popcll(__ballot(t.zub < (uint32_t)(old >> 32)));
+        win += __popcll(__ballot(key > old));
+    }
+    __device__ __forceinline__ void main_loop_ends(const RasterArgs &a, int lane)
+    {
+        rt2 = __builtin_amdgcn_s_memrealtime();
+        if (lane != 0) return;
+        unsigned long long *d = a.cnt->dbg[blockIdx.x % DBG_COPIES];
+        const uint32_t v[11] = {tri, alive, rows, spans, spans_live, frags, fwin, rwin, pre, win, rebuilds};
+#pragma unroll
+        for (int i = 0; i < 11; ++i) atomicAdd(d + i, (unsigned long long)v[i]);
+    }
+    __device__ __forceinline__ void kernel_ends(const RasterArgs &a, const TileCtx &c, int lane, int w)
+    {
+        T(7);
+        if (lane != 0) return;
+        unsigned long long *d = a.cnt->dbg[blockIdx.x % DBG_COPIES];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) atomicAdd(d + 12 + i, (unsigned long long)t[i]);
+        atomicAdd(d + 20, 1ull); // waves that ran the main loop
+        if (a.dbg_tiles && w == 0) {
+            // timeline of this workgroup: start / main loop / end on the 100 MHz clock, where it ran, how much it had to do
+            unsigned long long *tl = a.dbg_tiles + (size_t)c.ltile * 8;   // (by tile; tl[7] carries the block)
+            tl[0] = rt0; tl[1] = rt1; tl[2] = rt2; tl[3] = __builtin_amdgcn_s_memrealtime();
+            tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32); // HW_ID, XCC_ID
+            tl[5] = (unsigned long long)(c.end - c.beg) | ((unsigned long long)(uint32_t)c.tile << 32);
+            tl[6] = t[1] + t[3] + t[4] + t[5]; tl[7] = t[0] | ((unsigned long long)blockIdx.x << 32);
+        }
+    }
+};
+#else
+struct SpanDbg {
+    __device__ __forceinline__ void T(int) {}
+    __device__ __forceinline__ void main_loop_begins() {}
+    __device__ __forceinline__ void rebuilt() {}
+    __device__ __forceinline__ void culled(bool, bool) {}
+    __device__ __forceinline__ void row_window(bool, int) {}
+    __device__ __forceinline__ void live_spans(unsigned long long) {}
+    __device__ __forceinline__ void fragments(int) {}
+    __device__ __forceinline__ void key_update(unsigned long long, unsigned long long, const SpanTri &) {}
+    __device__ __forceinline__ void main_loop_ends(const RasterArgs &, int) {}
+    __device__ __forceinline__ void kernel_ends(const RasterArgs &, const TileCtx &, int, int) {}
+};
+#endif
+
+// k-th record of this tile, k in [0, c.end - c.beg): straight from the CSR list, or through the tables step 0a left in LDS
+struct TileSource {
+    const RasterArgs &a;
+    const TileCtx &c;
+    const bool segmented;
+    const uint32_t *segpre, *segsrc;
+    __device__ __forceinline__ uint4 operator()(uint32_t k) const
+    {
+        if (!segmented) return a.bins[c.beg + k];
+        uint32_t g = 0;
+#pragma unroll
+        for (int st = BIN_MAX_G / 2; st >= 1; st >>= 1) if (segpre[g + st] <= k) g += st;
+        return a.bins[segsrc[g] + (k - segpre[g])];
+    }
 };
 
+// ---- step 0b: this tile's 16-byte cull records {triangle, zkey of an upper bound of its rhw (cull_zub), pixel bbox} in
+// NEAR-FIRST order (a 64-bucket sort on 4 exponent + 2 mantissa bits of the bound).  The order cannot change any output
+// (the z resolution is order independent); it only makes the hierarchical early-z of step 1 reject more. ----
+// A tile with few records (<= DIRECT_MAX, at most one per thread) never goes through bins2: the records are ordered
+// near-first through LDS (the bucket sort on an exchange buffer that shares its bytes with the main loop's staging), wave w
+// keeps the records at sorted positions w, w+NW, ... in registers (nearest in lane 0) and culls them in DIRECT_STEPS steps,
+// so that later steps already see the depths the nearer triangles left behind.
+struct DirectRecs {
+    uint4 ent;
+    bool valid;
+    int count, pos, step; // lanes of this wave that hold a record; next lane to cull; lanes per step
+};
+template <bool COUNT, class L>
+__device__ __forceinline__ DirectRecs span_order_direct(const RasterArgs &a, const TileCtx &c, unsigned char *lds, uint32_t nent, int lane, int w)
+{
+    constexpr int NW = L::WAVES;
+    const TileSource source = {a, c, a.nseg != 0, L::segpre(lds), L::segsrc(lds)};
+    const bool have = threadIdx.x < nent;
+    const uint4 rec = have ? source(threadIdx.x) : make_uint4(0, 0, 0, 0);
+    const uint32_t bkt = COUNT ? 0u : z_bucket(rec.y);
+    if (have) atomicAdd(&L::bkt(lds)[bkt], 1u);
+    __syncthreads();
+    if (w == 0) bucket_scan(L::bkt(lds), lane, 0u);
+    __syncthreads();
+    if (have) L::exch(lds)[atomicAdd(&L::bkt(lds)[bkt], 1u)] = rec;
+    __syncthreads();
+    const uint32_t q = (uint32_t)lane * NW + (uint32_t)w;
+    DirectRecs d = {make_uint4(0, 0, 0, 0), q < nent, 0, 0, 64};
+    if (d.valid) d.ent = L::exch(lds)[q];
+    d.count = __popcll(__ballot(d.valid));
+    d.step = max(DIRECT_MIN, (d.count + DIRECT_STEPS - 1) / DIRECT_STEPS);   // (the kernel settles it once it knows B)
+    __syncthreads(); // the staging is written again by phase 1b
+    return d;
+}
+// More records: copied in that order into the tile's own range [c.beg, c.beg + nent) of `ents` (bins2).
+template <bool COUNT, class L>
+__device__ __forceinline__ void span_order_bins2(const RasterArgs &a, const TileCtx &c, unsigned char *lds, uint4 *ents, uint32_t nent, int lane, int w)
+{
+    constexpr int NW = L::WAVES, B = L::BATCH;
+    const TileSource source = {a, c, a.nseg != 0, L::segpre(lds), L::segsrc(lds)};
+    const bool sorted = !COUNT && nent > 2u * B;
+    auto bucket_of = [&](const uint4 &e) { return sorted ? z_bucket(e.y) : 0u; };
+    uint4 ce[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t e = threadIdx.x + (uint32_t)(NW * 64) * k;
+        ce[k] = make_uint4(0, 0, 0, 0);
+        if (e < nent) { ce[k] = source(e); atomicAdd(&L::bkt(lds)[bucket_of(ce[k])], 1u); }
+    }
+    for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) atomicAdd(&L::bkt(lds)[bucket_of(source(e))], 1u);
+    __syncthreads();
+    if (w == 0) bucket_scan(L::bkt(lds), lane, c.beg);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t e = threadIdx.x + (uint32_t)(NW * 64) * k;
+        if (e < nent) ents[atomicAdd(&L::bkt(lds)[bucket_of(ce[k])], 1u)] = ce[k];
+    }
+    for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) {
+        const uint4 en = source(e);
+        ents[atomicAdd(&L::bkt(lds)[bucket_of(en)], 1u)] = en;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// ---- step 1a, the cull half of one cull step: lane = bin entry `en` (where `valid`).  bbox-in-tile + whole-triangle early-z on
+// the 16-byte cull record; triangles outside the span algebra's safe range are swept at once.  (1b, staging the survivors, follows
+// in the kernel behind the wave's "nobody survived" exit.) ----
+struct Culled {
+    int bx0, bx1, by0, by1;        // the clamped bbox in this tile
+    bool alive;
+};
+template <int PS, bool COUNT, class L>
+__device__ __forceinline__ Culled span_cull(const RasterArgs &a, const TileCtx &c, unsigned char *lds, int win_safe, bool valid, const uint4 &en,
+                                            int lane, uint32_t &n_cov, uint32_t &n_nan, SpanDbg &dbg)
+{
+    const int mnx = (int)(short)(en.z & 0xFFFFu), mny = (int)(short)(en.z >> 16);
+    const int mxx = (int)(short)(en.w & 0xFFFFu), mxy = (int)(short)(en.w >> 16);
+    // clamped bbox (renderer.rs:285-298) in this tile: the i16 box is the saturated min/max of spi and the window
+    // lies inside the i16 range, so clamping it equals clamping the i32 values
+    const int bx0 = max(clampi(mnx, a.x0, a.x1), c.ax0), bx1 = min(clampi(mxx, a.x0, a.x1), c.ax0 + c.tw);
+    const int by0 = max(clampi(mny, a.y0, a.y1), c.ay0), by1 = min(clampi(mxy, a.y0, a.y1), c.ay0 + c.th);
+    const bool nonempty = valid && bx1 > bx0 && by1 > by0;
+    // (the bbox saturates at +-32767, so out-of-range vertices show up here too)
+    const int amax = max(max(abs(mnx), abs(mxx)), max(abs(mny), abs(mxy)));
+    const bool safe = nonempty && win_safe && amax <= SPAN_SAFE;
+    bool alive = safe;
+    if (!COUNT && safe) {
+        // against the 8x8 block minima when the bbox touches <= 2x2 blocks, else against the
+        // 16x16 quad minima (a tile has 2x2 quads, so this always applies)
+        const int gx0 = (bx0 - c.ax0) >> 3, gx1 = (bx1 - 1 - c.ax0) >> 3, gy0 = (by0 - c.ay0) >> 3, gy1 = (by1 - 1 - c.ay0) >> 3;
+        const bool small = gx1 - gx0 <= 1 && gy1 - gy0 <= 1;
+        const uint32_t *lv = L::hz(lds) + (small ? HZ_BLK : HZ_QUAD);
+        const int sh = small ? 0 : 1, st = small ? 4 : 2;
+        const int ix0 = gx0 >> sh, ix1 = gx1 >> sh, iy0 = gy0 >> sh, iy1 = gy1 >> sh;
+        const uint32_t hm = min(min(lv[iy0 * st + ix0], lv[iy0 * st + ix1]), min(lv[iy1 * st + ix0], lv[iy1 * st + ix1]));
+        alive = !(en.y < hm);
+    }
+    dbg.culled(nonempty, alive);
+    // triangles outside the span algebra's safe range: exact brute-force sweep, right away
+    unsigned long long um = __ballot(nonempty && !safe);
+    while (um) {
+        const int src = __builtin_ctzll(um);
+        um &= um - 1;
+        const uint32_t tu = (uint32_t)__builtin_amdgcn_readlane((int)en.x, src);
+        uint32_t ncv = 0;
+        sweep_triangle(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, L::key(lds), ncv, n_nan, &L::nanflag(lds));
+        n_cov += ncv;
+    }
+    return {bx0, bx1, by0, by1, alive};
+}
+// ---- step 2, one row window: lane = (triangle, row) for rows r0 .. r0 + 63 of the step.  Exact covered span of that row,
+// shrunk by the cell-level early-z; then the spans of the window laid end to end for step 3.  jbase: heads seen in
+// earlier row windows. ----
+struct RowWindow {
+    bool any;                       // some span is left: fragments follow
+    int F;                          // fragments of all spans, laid end to end
+    unsigned long long hfrag_mine;  // lane i keeps the heads of fragment window i
+};
+template <bool COUNT, class L>
+__device__ __forceinline__ RowWindow span_row_window(unsigned char *lds, int R, unsigned long long hrow_mine, int r0, int lane, int w, uint32_t le_lo, uint32_t le_hi,
+                                                     int &jbase, uint32_t &n_cov, SpanDbg &dbg)
+{
+    const uint32_t h_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)hrow_mine, r0 >> 6);
+    const uint32_t h_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(hrow_mine >> 32), r0 >> 6);
+    const bool ractive = r0 + lane < R;
+    const int j = seg_rank(h_lo, h_hi, le_lo, le_hi, jbase - 1);       // staging slot = rank of the triangle
+    int len = 0, xl = 0, yl = 0;
+    uint32_t zu = 0xFFFFFFFFu;
+    if (ractive) {
+        const SpanTri ti = L::tri(lds)[w][j];
+        const int row = r0 + lane - (int)(ti.misc >> 19);
+        const int bwj = (int)((ti.misc >> 10) & 63u);
+        int lo = 0, hi = bwj;
+        span_edge_bound(ti.m01, ti.kd01, ti.r01, (int)(ti.misc << 15) >> 31, row, lo, hi);
+        span_edge_bound(ti.m12, ti.kd12, ti.r12, (int)(ti.misc << 14) >> 31, row, lo, hi);
+        span_edge_bound(ti.m20, ti.kd20, ti.r20, (int)(ti.misc << 13) >> 31, row, lo, hi);
+        len = max(hi - lo, 0);
+        xl = (int)(ti.misc & 31u) + lo;
+        yl = (int)((ti.misc >> 5) & 31u) + row;
+        zu = ti.zub;
+    }
+    dbg.row_window(ractive, len);
+    jbase += __popc(h_lo) + __popc(h_hi);
+    if (COUNT) n_cov += (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_dpp((uint32_t)len), 63);
+    // span-level early-z against the minima of the row's eight 4-pixel cells: the span shrinks to
+    // the hull of the cells in which the triangle's depth bound could still win
+    if (len > 0) {
+        const uint4 ca = *reinterpret_cast<const uint4 *>(&L::hz(lds)[HZ_C4 + yl * 8]);
+        const uint4 cb = *reinterpret_cast<const uint4 *>(&L::hz(lds)[HZ_C4 + yl * 8 + 4]);
+        // the cells hold (minimum >> 1): "zu >> 1 below it" implies zu < minimum (conservative in the last bit), and
+        // with both operands below 2^31 the sign of the difference is the comparison -- a subtraction and a funnel
+        // shift per cell instead of a compare and a select.  Bit i of cm: the bound cannot win in cell i.
+        const uint32_t zh = zu >> 1;
+        uint32_t cm = 0u;
+        cm = __builtin_amdgcn_alignbit(cm, zh - cb.w, 31); cm = __builtin_amdgcn_alignbit(cm, zh - cb.z, 31);
+        cm = __builtin_amdgcn_alignbit(cm, zh - cb.y, 31); cm = __builtin_amdgcn_alignbit(cm, zh - cb.x, 31);
+        cm = __builtin_amdgcn_alignbit(cm, zh - ca.w, 31); cm = __builtin_amdgcn_alignbit(cm, zh - ca.z, 31);
+        cm = __builtin_amdgcn_alignbit(cm, zh - ca.y, 31); cm = __builtin_amdgcn_alignbit(cm, zh - ca.x, 31);
+        const int xr = xl + len - 1;
+        const int c0 = xl >> 2, c1 = xr >> 2;
+        const uint32_t pm = ~cm & ((2u << c1) - (1u << c0));
+        if (pm == 0u) {
+            len = 0;
+        } else {
+            const int f = __builtin_ctz(pm), l2 = 31 - __builtin_clz(pm);
+            const int nxl = max(xl, f << 2), nxr = min(xr, (l2 << 2) + 3);
+            xl = nxl;
+            len = nxr - nxl + 1;
+        }
+    }
+    // ---- spans of this window laid end to end: heads mark where each span's fragments start ----
+    const unsigned long long nz = __ballot(len > 0);
+    dbg.live_spans(nz);
+    if (nz == 0ull) { dbg.T(4); return {false, 0, 0ull}; }
+    const int srank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
+    const uint32_t fincl = wave_incl_scan_dpp((uint32_t)len);
+    const int F = (int)__builtin_amdgcn_readlane((int)fincl, 63);
+    if (lane < 32) L::hfrag(lds)[w][lane] = 0ull;
+    wave_lds_fence();
+    if (len > 0) {
+        const uint32_t st = fincl - (uint32_t)len;
+        atomicOr(reinterpret_cast<uint32_t *>(&L::hfrag(lds)[w][0]) + (st >> 5), 1u << (st & 31));
+        // span descriptor: staging slot, row, and x of the span's first pixel MINUS its first fragment's position (+ 2048:
+        // a window holds at most 64 * 32 fragments), so that fragment f of the window is pixel x = field + f - 2048
+        L::q(lds)[w][srank] = (uint32_t)j | ((uint32_t)yl << 5) | (((uint32_t)xl + 2048u - st) << 10);
+    }
+    wave_lds_fence();
+    const unsigned long long hfrag_mine = L::hfrag(lds)[w][lane & 31];
+    dbg.fragments(F);
+    dbg.T(4);
+    return {true, F, hfrag_mine};
+}
+
+// The tile kernel, in the steps of DESIGN.md section 5.  Steps 0b, 1a and 2 are the functions above; 0a, 1b, 3 and 4 are written out
+// here: moved into functions (their early exits, their staging stores, their loops over shared per-kernel functions) they compile
+// to other code than they do in place.
 template <int K, int PS, bool COUNT, int NW, int OCC>
 __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevUniforms u, int win_safe)
 {
     constexpr int B = NW <= 3 ? LIGHT_B : (OCC >= 8 || NW >= 16) ? 16 : SPAN_BATCH; // staged triangles per wave (LDS budget: 8 workgroups per CU; 64 KiB of static LDS at NW = 16)
     constexpr bool TEXTURED = PS == FRR_PS_PHONG || PS == FRR_PS_BLINN || PS >= FRR_SHADER_USER_BASE;   // (the u8 -> float table of sample_2d)
-    static_assert(B <= 32, "staging slots are five bits of a span descriptor, first rows ten bits of SpanTri::misc");
+    static_assert(NW >= 3, "the workgroup's threads (three waves: + a second column of wave 0) read all BIN_MAX_G segments; w4[0..3] are all written");
     using L = SpanLds<NW, B>;
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[L::bytes(TEXTURED)];
-    unsigned long long *const s_key = reinterpret_cast<unsigned long long *>(s_raw + L::KEY);
-    SpanTri (*const s_tri)[B] = reinterpret_cast<SpanTri (*)[B]>(s_raw + L::TRI);
-    float4 (*const s_fa)[B] = reinterpret_cast<float4 (*)[B]>(s_raw + L::FA);
-    float4 (*const s_fb)[B] = reinterpret_cast<float4 (*)[B]>(s_raw + L::FB);
-    float2 (*const s_fc)[B] = reinterpret_cast<float2 (*)[B]>(s_raw + L::FC);
-    unsigned long long (*const s_hrow)[B / 2] = reinterpret_cast<unsigned long long (*)[B / 2]>(s_raw + L::HROW);
-    unsigned long long (*const s_hfrag)[32] = reinterpret_cast<unsigned long long (*)[32]>(s_raw + L::HFRAG);
-    uint32_t (*const s_q)[64] = reinterpret_cast<uint32_t (*)[64]>(s_raw + L::Q);
-    uint32_t *const s_segpre = reinterpret_cast<uint32_t *>(s_raw + L::SEGPRE);
-    uint32_t *const s_segsrc = reinterpret_cast<uint32_t *>(s_raw + L::SEGSRC);
-    uint4 *const s_exch = reinterpret_cast<uint4 *>(s_raw + L::EXCH);
-    uint32_t *const s_hz = reinterpret_cast<uint32_t *>(s_raw + L::HZ);
-    uint32_t *const s_bkt = reinterpret_cast<uint32_t *>(s_raw + L::BKT);
-    uint32_t &s_next = *reinterpret_cast<uint32_t *>(s_raw + L::SCAL);
-    uint32_t &s_dirty = *reinterpret_cast<uint32_t *>(s_raw + L::SCAL + 4); // keys changed since the hierarchical z was last rebuilt
-    uint32_t &s_ebase = *reinterpret_cast<uint32_t *>(s_raw + L::SCAL + 8);
-    uint32_t &s_nanflag = *reinterpret_cast<uint32_t *>(s_raw + L::SCAL + 12); // some fragment of this tile had a NaN rhw: second pass (tile_nan_begin)
-    uint32_t *const s_nanL = reinterpret_cast<uint32_t *>(s_raw + L::U0);      // that pass's per-pixel ids; over the staging, after the main loop
-    static_assert(L::U1 - L::U0 >= TILE_PX * 4, "the NaN pass keeps one u32 per pixel in the staging region");
-    uint32_t *const s_w4 = reinterpret_cast<uint32_t *>(s_raw + L::SCAL + 16);
-    float *const s_u8 = reinterpret_cast<float *>(s_raw + L::U8);  // (float)i / 255.0f for the texture taps of the resolve
-    if (TEXTURED) for (int i = threadIdx.x; i < 256; i += NW * 64) s_u8[i] = (float)i / 255.0f; // ordered by the barriers below
+    __shared__ __attribute__((aligned(16))) unsigned char lds[L::bytes(TEXTURED)];
+    if (TEXTURED) for (int i = threadIdx.x; i < 256; i += NW * 64) L::u8(lds)[i] = (float)i / 255.0f; // ordered by the barriers below
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef FRR_DEBUG_COUNTERS
-    // wave-cycles per phase (s_memtime): 0 pre-pass, 1 phase 1a, 2 hi-z rebuild, 3 phase 1b, 4 phase 2, 5 phase 3,
-    // 6 wait at the final barrier, 7 resolve
-    unsigned long long d_tlast = __builtin_amdgcn_s_memtime();
-    const unsigned long long d_rt0 = __builtin_amdgcn_s_memrealtime(); // 100 MHz, the same counter on every XCD
-    unsigned long long d_rt1 = 0, d_rt2 = 0;
-    uint32_t d_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define FRR_T(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); d_t[i] += (uint32_t)(now_ - d_tlast); d_tlast = now_; } while (0)
-#else
-#define FRR_T(i) do { } while (0)
-#endif
+    SpanDbg dbg;
     // the pre-pass is a chain of dependent loads and barriers: its waves issue ahead of the waves that sit in the row /
     // fragment loops of other tiles on the same SIMD (the sooner its loads are out, the more of their latency those cover)
     __builtin_amdgcn_s_setprio(3);
     const uint32_t first_bad = seq_first_bad(a.cnt);   // (tested below, where the first loads are waited for anyway)
     TileCtx c = tile_ctx(a);
+    // ---- step 0a: segments -> this tile's record range.  The exits (the pass is cancelled; nothing is binned here, the tile only
+    // takes the pending clear) are the same for every thread of the workgroup. ----
     const bool segmented = a.nseg != 0;
     if (!segmented && seq_is_cancelled(first_bad, a.seq, a.epoch, true)) return;
     if (segmented) {
@@ -674,7 +952,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
         // this or an earlier command failed: the targets stay as they are, the host replays (frr_device.h: Counters::first_bad)
         if (seq_is_cancelled(first_bad, a.seq, a.epoch, true)) return;
         const uint32_t inc = wave_incl_scan_dpp(cn);
-        if (lane == 63 && w < 4) s_w4[w] = inc;
+        if (lane == 63 && w < 4) L::w4(lds)[w] = inc;
         // three waves: segments 192..255 are a second column read of wave 0 (the host keeps nseg <= 256 then, else <= NW * 64)
         uint32_t s0x = 0, cnx = 0, incx = 0;
         if (NW == 3 && w == 0) {
@@ -684,204 +962,101 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
                 cnx = r[1] - s0x;
             }
             incx = wave_incl_scan_dpp(cnx);
-            if (lane == 63) s_w4[3] = incx;
+            if (lane == 63) L::w4(lds)[3] = incx;
         }
-        if (NW < 3 && threadIdx.x == 0) { s_w4[2] = 0u; s_w4[3] = 0u; }
         __syncthreads();
-        const uint32_t w0 = s_w4[0], w1 = s_w4[1], w2 = s_w4[2], w3 = s_w4[3];
+        const uint32_t w0 = L::w4(lds)[0], w1 = L::w4(lds)[1], w2 = L::w4(lds)[2], w3 = L::w4(lds)[3];
         const uint32_t total = __builtin_amdgcn_readfirstlane((w0 + w1) + (w2 + w3)); // wave-uniform, and the compiler should know
         if (threadIdx.x == 0 && a.tile_cost) a.tile_cost[c.ltile] = total;            // the cost a later pass orders this tile by
         if (total == 0u) { tile_fill_clear(a, c); return; }
         if (threadIdx.x < BIN_MAX_G) {
-            s_segpre[threadIdx.x] = (w > 0 ? w0 : 0u) + (w > 1 ? w1 : 0u) + (w > 2 ? w2 : 0u) + inc - cn;
-            s_segsrc[threadIdx.x] = s0;
+            L::segpre(lds)[threadIdx.x] = (w > 0 ? w0 : 0u) + (w > 1 ? w1 : 0u) + (w > 2 ? w2 : 0u) + inc - cn;
+            L::segsrc(lds)[threadIdx.x] = s0;
         }
-        if (NW == 3 && w == 0) { s_segpre[192 + lane] = (w0 + w1) + w2 + incx - cnx; s_segsrc[192 + lane] = s0x; }
-        if (NW < 3) for (int i = threadIdx.x + NW * 64; i < BIN_MAX_G; i += NW * 64) { s_segpre[i] = total; s_segsrc[i] = 0u; }
+        if (NW == 3 && w == 0) { L::segpre(lds)[192 + lane] = (w0 + w1) + w2 + incx - cnx; L::segsrc(lds)[192 + lane] = s0x; }
         if (threadIdx.x == 0) {
-            s_segpre[BIN_MAX_G] = total;
+            L::segpre(lds)[BIN_MAX_G] = total;
             // where this tile's near-first copy goes: its own fixed slot of bins2, or -- a tile hotter than
             // the slot -- space from the shared overflow arena behind the slots.  (One atomic per tile on a
             // single address costs ~17 ns each, serialised across the whole launch; hence the slots.)
             const uint32_t ntiles = gridDim.x;
-            s_ebase = total <= a.ent_slot ? (uint32_t)c.ltile * a.ent_slot
+            L::ebase(lds) = total <= a.ent_slot ? (uint32_t)c.ltile * a.ent_slot
                                           : ntiles * a.ent_slot + atomicAdd(&a.cnt->lane[a.lane].btab[a.bpar].ent_cursor, total);
         }
         __syncthreads();
-        c.beg = __builtin_amdgcn_readfirstlane(s_ebase); // this tile's range of the near-first copy (bins2)
+        c.beg = __builtin_amdgcn_readfirstlane(L::ebase(lds)); // this tile's range of the near-first copy (bins2)
         c.end = c.beg + total;
     } else if (c.beg >= c.end) {
         tile_fill_clear(a, c);
         return;
     }
-    // k-th record of this tile, k in [0, c.end - c.beg)
-    auto source = [&](uint32_t k) -> uint4 {
-        if (!segmented) return a.bins[c.beg + k];
-        uint32_t g = 0;
-#pragma unroll
-        for (int st = BIN_MAX_G / 2; st >= 1; st >>= 1) if (s_segpre[g + st] <= k) g += st;
-        return a.bins[s_segsrc[g] + (k - s_segpre[g])];
-    };
-    tile_load_keys(a, c, s_key, ~0ull);
+    tile_load_keys(a, c, L::key(lds), ~0ull);
     // A draw that carries the frame's clear starts from ONE depth: the minima are that constant (pixels of a partial tile
     // beyond the window would only raise them), and nothing has to be rebuilt before the first fragments land.  Else:
     // "nothing can be culled" until the first rebuild.
     const uint32_t hz0 = a.fused_clear ? zkey_depth(a.clear_depth) : 0u;
-    if (threadIdx.x == 0) { s_next = 0; s_dirty = a.fused_clear ? 0u : 1u; s_nanflag = 0u; }
-    for (int i = threadIdx.x; i < BKT_N; i += NW * 64) s_bkt[i] = 0;
-    for (int i = threadIdx.x; i < HZ_SIZE; i += NW * 64) s_hz[i] = i >= HZ_C4 ? hz0 >> 1 : hz0;
+    if (threadIdx.x == 0) { L::next(lds) = 0; L::dirty(lds) = a.fused_clear ? 0u : 1u; L::nanflag(lds) = 0u; }
+    for (int i = threadIdx.x; i < BKT_N; i += NW * 64) L::bkt(lds)[i] = 0;
+    for (int i = threadIdx.x; i < HZ_SIZE; i += NW * 64) L::hz(lds)[i] = i >= HZ_C4 ? hz0 >> 1 : hz0;
     __syncthreads();
 
-    // ---- pre-pass: this tile's 16-byte cull records {triangle, zkey of an upper bound of its rhw
-    // (cull_zub), pixel bbox} are copied in NEAR-FIRST order (a 64-bucket sort on 4 exponent + 2
-    // mantissa bits of the bound) into the tile's own range of `ents`.  The order cannot change any
-    // output (the z resolution is order independent); it only makes the hierarchical early-z below
-    // reject more.
+    // ---- step 0b: near-first order, into registers (few records) or into the tile's range of bins2 ----
     uint4 *__restrict__ ents = a.bins2;
-    // A tile with few records (<= DIRECT_MAX, at most one per thread) never goes through bins2: the records
-    // are ordered near-first through LDS (the bucket sort below on an exchange buffer that shares its bytes
-    // with the main loop's staging), wave w keeps the records at sorted positions w, w+NW, ... in registers (nearest in
-    // lane 0) and culls them in DIRECT_STEPS steps, so that later steps already see the depths the
-    // nearer triangles left behind.
     const uint32_t nent = c.end - c.beg;
     const bool direct = nent <= (uint32_t)(DIRECT_MAX < NW * 64 ? DIRECT_MAX : NW * 64);
-    uint4 dent = make_uint4(0, 0, 0, 0);
-    bool dvalid = false;
-    int dcount = 0, dpos = 0, dstep = 64; // lanes of this wave that hold a record; next lane to cull; lanes per step
-    if (direct) {
-        const bool have = threadIdx.x < nent;
-        const uint4 rec = have ? source(threadIdx.x) : make_uint4(0, 0, 0, 0);
-        const uint32_t bkt = COUNT ? 0u : z_bucket(rec.y);
-        if (have) atomicAdd(&s_bkt[bkt], 1u);
-        __syncthreads();
-        if (w == 0) bucket_scan(s_bkt, lane, 0u);
-        __syncthreads();
-        uint4 *const exch = s_exch;
-        if (have) exch[atomicAdd(&s_bkt[bkt], 1u)] = rec;
-        __syncthreads();
-        const uint32_t q = (uint32_t)lane * NW + (uint32_t)w;
-        dvalid = q < nent;
-        if (dvalid) dent = exch[q];
-        dcount = __popcll(__ballot(dvalid));
-        dstep = max(DIRECT_MIN, (dcount + DIRECT_STEPS - 1) / DIRECT_STEPS);
-        __syncthreads(); // the staging is written again by phase 1b
-    } else {
-        const bool sorted = !COUNT && nent > 2u * B;
-        auto bucket_of = [&](const uint4 &e) { return sorted ? z_bucket(e.y) : 0u; };
-        uint4 ce[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t e = threadIdx.x + (uint32_t)(NW * 64) * k;
-            ce[k] = make_uint4(0, 0, 0, 0);
-            if (e < nent) { ce[k] = source(e); atomicAdd(&s_bkt[bucket_of(ce[k])], 1u); }
-        }
-        for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) atomicAdd(&s_bkt[bucket_of(source(e))], 1u);
-        __syncthreads();
-        if (w == 0) bucket_scan(s_bkt, lane, c.beg);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t e = threadIdx.x + (uint32_t)(NW * 64) * k;
-            if (e < nent) ents[atomicAdd(&s_bkt[bucket_of(ce[k])], 1u)] = ce[k];
-        }
-        for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) {
-            const uint4 en = source(e);
-            ents[atomicAdd(&s_bkt[bucket_of(en)], 1u)] = en;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
+    DirectRecs d = {make_uint4(0, 0, 0, 0), false, 0, 0, 64};
+    if (direct) d = span_order_direct<COUNT, L>(a, c, lds, nent, lane, w);                              // step 0b
+    else span_order_bins2<COUNT, L>(a, c, lds, ents, nent, lane, w);
 
     __builtin_amdgcn_s_setprio(0);
     const uint32_t le_lo = lane < 32 ? (2u << lane) - 1u : 0xFFFFFFFFu;
     const uint32_t le_hi = lane < 32 ? 0u : (2u << (lane - 32)) - 1u;
     uint32_t n_cov = 0, n_nan = 0;
-#ifdef FRR_DEBUG_COUNTERS
-    uint32_t d_tri = 0, d_alive = 0, d_rows = 0, d_spans = 0, d_spans_live = 0, d_frags = 0, d_fwin = 0, d_rwin = 0;
-    uint32_t d_pre = 0, d_win = 0, d_rebuild = 0; // fragments a per-pixel zub test would skip; fragments that took the pixel; hi-z rebuilds
-#endif
 
     // bin entries culled per step: every survivor of a step gets a staging slot (<= B per wave), and its fragments are
     // resolved before the next step culls (fresh z minima: the early-z of the later, farther records lives on them)
     constexpr int CULL = SPAN_CULL < B ? SPAN_CULL : B;
     if (direct) { // (B can be smaller than half a wave)
-        const int nsteps = max(DIRECT_STEPS, (dcount + B - 1) / B);
-        dstep = max(min(DIRECT_MIN, B), (dcount + nsteps - 1) / nsteps);
+        const int nsteps = max(DIRECT_STEPS, (d.count + B - 1) / B);
+        d.step = max(min(DIRECT_MIN, B), (d.count + nsteps - 1) / nsteps);
     }
-    FRR_T(0);
-#ifdef FRR_DEBUG_COUNTERS
-    d_rt1 = __builtin_amdgcn_s_memrealtime();
-#endif
+    dbg.T(0);
+    dbg.main_loop_begins();
     for (;;) {
-        // ---- phase 1: lane = bin entry, CULL per step.  bbox-in-tile + whole-triangle early-z on the 16-byte cull
-        // record; a survivor then fetches its 64-byte setup record and stages its edge data at its RANK among the
-        // survivors (lanes and ranks ascend together, so "the k-th head" below is staging slot k) ----
+        // ---- step 1: lane = bin entry, CULL per step: the next lanes of the registers, or the next entries of the near-first copy ----
         uint32_t e0 = 0;
         int dlo = 0;
         if (direct) {
-            dlo = dpos;
-            dpos += dstep;
-            if (dlo >= dcount) break;
+            dlo = d.pos;
+            d.pos += d.step;
+            if (dlo >= d.count) break;
         } else {
             uint32_t b = 0;
-            if (lane == 0) b = atomicAdd(&s_next, 1u);
+            if (lane == 0) b = atomicAdd(&L::next(lds), 1u);
             b = __builtin_amdgcn_readfirstlane(b);
             e0 = c.beg + b * (uint32_t)CULL;
             if (e0 >= c.end) break;
         }
         // the minima are rebuilt only if some wave has resolved fragments since the last rebuild
         // (a stale minimum is a lower one: still conservative)
-        if (__builtin_amdgcn_readfirstlane(s_dirty) != 0u) {
-            FRR_T(1);
-            if (lane == 0) s_dirty = 0u;
-            hiz_rebuild(s_key, s_hz, lane);
-#ifdef FRR_DEBUG_COUNTERS
-            ++d_rebuild;
-#endif
-            FRR_T(2);
+        if (__builtin_amdgcn_readfirstlane(L::dirty(lds)) != 0u) {
+            dbg.T(1);
+            if (lane == 0) L::dirty(lds) = 0u;
+            hiz_rebuild(L::key(lds), L::hz(lds), lane);
+            dbg.rebuilt();
+            dbg.T(2);
         }
         wave_lds_fence();
-        const bool valid = direct ? (dvalid && lane >= dlo && lane < dlo + dstep) : lane < (int)min((uint32_t)CULL, c.end - e0);
-        const uint4 en = direct ? dent : (valid ? ents[e0 + lane] : make_uint4(0, 0, 0, 0));
-        const int mnx = (int)(short)(en.z & 0xFFFFu), mny = (int)(short)(en.z >> 16);
-        const int mxx = (int)(short)(en.w & 0xFFFFu), mxy = (int)(short)(en.w >> 16);
-        // clamped bbox (renderer.rs:285-298) in this tile: the i16 box is the saturated min/max of spi and the window
-        // lies inside the i16 range, so clamping it equals clamping the i32 values
-        const int bx0 = max(clampi(mnx, a.x0, a.x1), c.ax0), bx1 = min(clampi(mxx, a.x0, a.x1), c.ax0 + c.tw);
-        const int by0 = max(clampi(mny, a.y0, a.y1), c.ay0), by1 = min(clampi(mxy, a.y0, a.y1), c.ay0 + c.th);
-        const bool nonempty = valid && bx1 > bx0 && by1 > by0;
-        // (the bbox saturates at +-32767, so out-of-range vertices show up here too)
-        const int amax = max(max(abs(mnx), abs(mxx)), max(abs(mny), abs(mxy)));
-        const bool safe = nonempty && win_safe && amax <= SPAN_SAFE;
-        bool alive = safe;
-        if (!COUNT && safe) {
-            // against the 8x8 block minima when the bbox touches <= 2x2 blocks, else against the
-            // 16x16 quad minima (a tile has 2x2 quads, so this always applies)
-            const int gx0 = (bx0 - c.ax0) >> 3, gx1 = (bx1 - 1 - c.ax0) >> 3, gy0 = (by0 - c.ay0) >> 3, gy1 = (by1 - 1 - c.ay0) >> 3;
-            const bool small = gx1 - gx0 <= 1 && gy1 - gy0 <= 1;
-            const uint32_t *lv = s_hz + (small ? HZ_BLK : HZ_QUAD);
-            const int sh = small ? 0 : 1, st = small ? 4 : 2;
-            const int ix0 = gx0 >> sh, ix1 = gx1 >> sh, iy0 = gy0 >> sh, iy1 = gy1 >> sh;
-            const uint32_t hm = min(min(lv[iy0 * st + ix0], lv[iy0 * st + ix1]), min(lv[iy1 * st + ix0], lv[iy1 * st + ix1]));
-            alive = !(en.y < hm);
-        }
-#ifdef FRR_DEBUG_COUNTERS
-        d_tri += __popcll(__ballot(nonempty)); d_alive += __popcll(__ballot(alive));
-#endif
-        // triangles outside the span algebra's safe range: exact brute-force sweep, right away
-        unsigned long long um = __ballot(nonempty && !safe);
-        while (um) {
-            const int src = __builtin_ctzll(um);
-            um &= um - 1;
-            const uint32_t tu = (uint32_t)__builtin_amdgcn_readlane((int)en.x, src);
-            uint32_t ncv = 0;
-            sweep_triangle(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, s_key, ncv, n_nan, &s_nanflag);
-            n_cov += ncv;
-        }
-        const unsigned long long am = __ballot(alive);
-        FRR_T(1);
+        const bool valid = direct ? (d.valid && lane >= dlo && lane < dlo + d.step) : lane < (int)min((uint32_t)CULL, c.end - e0);
+        const uint4 en = direct ? d.ent : (valid ? ents[e0 + lane] : make_uint4(0, 0, 0, 0));
+        const Culled k = span_cull<PS, COUNT, L>(a, c, lds, win_safe, valid, en, lane, n_cov, n_nan, dbg);   // step 1a
+        const unsigned long long am = __ballot(k.alive);
+        dbg.T(1);
         if (am == 0ull) continue;
+        // ---- step 1b: a survivor fetches its 64-byte setup record and stages its edge data at its RANK among the
+        // survivors (lanes and ranks ascend together, so "the k-th head" of step 2 is staging slot k) ----
+        const bool alive = k.alive;
+        const int bx0 = k.bx0, bx1 = k.bx1, by0 = k.by0, by1 = k.by1;
         const int trank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
         const uint32_t rows = alive ? (uint32_t)(by1 - by0) : 0u;
         // rows of all survivors laid end to end (at most B * 32 = 1024 of them): heads mark where each triangle's rows start
@@ -902,190 +1077,84 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
                      (((q3.w >> REC_POS_SHIFT) & 7u) << 16) | ((rincl - rows) << 19);
             t.r01 = r_of(q0.x); t.r12 = r_of(q0.z); t.r20 = r_of(q1.x);
             t.pad = 0.0f;
-            s_tri[w][trank] = t;
-            s_fa[w][trank] = make_float4(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y));
-            s_fb[w][trank] = make_float4(u2f(q2.z), u2f(q2.w), u2f(q3.x), u2f(q3.y));
-            s_fc[w][trank] = make_float2(u2f(q3.z), u2f(PS == FRR_PS_DEPTH ? emission_id_rec(a, en.x, q3.w) : order_id(a, en.x)));
+            L::tri(lds)[w][trank] = t;
+            L::fa(lds)[w][trank] = make_float4(u2f(q1.z), u2f(q1.w), u2f(q2.x), u2f(q2.y));
+            L::fb(lds)[w][trank] = make_float4(u2f(q2.z), u2f(q2.w), u2f(q3.x), u2f(q3.y));
+            L::fc(lds)[w][trank] = make_float2(u2f(q3.z), u2f(PS == FRR_PS_DEPTH ? emission_id_rec(a, en.x, q3.w) : order_id(a, en.x)));
         }
         const int R = (int)__builtin_amdgcn_readlane((int)rincl, 63);
-        if (lane < B / 2) s_hrow[w][lane] = 0ull;
+        if (lane < B / 2) L::hrow(lds)[w][lane] = 0ull;
         wave_lds_fence();
         if (rows) {
             const uint32_t st = rincl - rows;
-            atomicOr(reinterpret_cast<uint32_t *>(&s_hrow[w][0]) + (st >> 5), 1u << (st & 31));
+            atomicOr(reinterpret_cast<uint32_t *>(&L::hrow(lds)[w][0]) + (st >> 5), 1u << (st & 31));
         }
         wave_lds_fence();
-        const unsigned long long hrow_mine = s_hrow[w][lane & (B / 2 - 1)]; // lane i keeps the heads of row window i
+        const unsigned long long hrow_mine = L::hrow(lds)[w][lane & (B / 2 - 1)];
         wave_lds_fence();
-
+        dbg.T(3);
         int jbase = 0;             // heads seen in earlier row windows
-        FRR_T(3);
         for (int r0 = 0; r0 < R; r0 += 64) {
-            // ---- phase 2: lane = (triangle, row).  Exact covered span of that row. ----
-            const uint32_t h_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)hrow_mine, r0 >> 6);
-            const uint32_t h_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(hrow_mine >> 32), r0 >> 6);
-            const bool ractive = r0 + lane < R;
-            const int j = seg_rank(h_lo, h_hi, le_lo, le_hi, jbase - 1);       // staging slot = rank of the triangle
-            int len = 0, xl = 0, yl = 0;
-            uint32_t zu = 0xFFFFFFFFu;
-            if (ractive) {
-                const SpanTri ti = s_tri[w][j];
-                const int row = r0 + lane - (int)(ti.misc >> 19);
-                const int bwj = (int)((ti.misc >> 10) & 63u);
-                int lo = 0, hi = bwj;
-                span_edge_bound(ti.m01, ti.kd01, ti.r01, (int)(ti.misc << 15) >> 31, row, lo, hi);
-                span_edge_bound(ti.m12, ti.kd12, ti.r12, (int)(ti.misc << 14) >> 31, row, lo, hi);
-                span_edge_bound(ti.m20, ti.kd20, ti.r20, (int)(ti.misc << 13) >> 31, row, lo, hi);
-                len = max(hi - lo, 0);
-                xl = (int)(ti.misc & 31u) + lo;
-                yl = (int)((ti.misc >> 5) & 31u) + row;
-                zu = ti.zub;
-            }
-#ifdef FRR_DEBUG_COUNTERS
-            d_rwin++; d_rows += __popcll(__ballot(ractive)); d_spans += __popcll(__ballot(len > 0));
-#endif
-            jbase += __popc(h_lo) + __popc(h_hi);
-            if (COUNT) n_cov += (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_dpp((uint32_t)len), 63);
-            // span-level early-z against the minima of the row's eight 4-pixel cells: the span shrinks to
-            // the hull of the cells in which the triangle's depth bound could still win
-            if (len > 0) {
-                const uint4 ca = *reinterpret_cast<const uint4 *>(&s_hz[HZ_C4 + yl * 8]);
-                const uint4 cb = *reinterpret_cast<const uint4 *>(&s_hz[HZ_C4 + yl * 8 + 4]);
-                // the cells hold (minimum >> 1): "zu >> 1 below it" implies zu < minimum (conservative in the last bit), and
-                // with both operands below 2^31 the sign of the difference is the comparison -- a subtraction and a funnel
-                // shift per cell instead of a compare and a select.  Bit i of cm: the bound cannot win in cell i.
-                const uint32_t zh = zu >> 1;
-                uint32_t cm = 0u;
-                cm = __builtin_amdgcn_alignbit(cm, zh - cb.w, 31); cm = __builtin_amdgcn_alignbit(cm, zh - cb.z, 31);
-                cm = __builtin_amdgcn_alignbit(cm, zh - cb.y, 31); cm = __builtin_amdgcn_alignbit(cm, zh - cb.x, 31);
-                cm = __builtin_amdgcn_alignbit(cm, zh - ca.w, 31); cm = __builtin_amdgcn_alignbit(cm, zh - ca.z, 31);
-                cm = __builtin_amdgcn_alignbit(cm, zh - ca.y, 31); cm = __builtin_amdgcn_alignbit(cm, zh - ca.x, 31);
-                const int xr = xl + len - 1;
-                const int c0 = xl >> 2, c1 = xr >> 2;
-                const uint32_t pm = ~cm & ((2u << c1) - (1u << c0));
-                if (pm == 0u) {
-                    len = 0;
-                } else {
-                    const int f = __builtin_ctz(pm), l = 31 - __builtin_clz(pm);
-                    const int nxl = max(xl, f << 2), nxr = min(xr, (l << 2) + 3);
-                    xl = nxl;
-                    len = nxr - nxl + 1;
-                }
-            }
-            // ---- spans of this window laid end to end: heads mark where each span's fragments start ----
-            const unsigned long long nz = __ballot(len > 0);
-#ifdef FRR_DEBUG_COUNTERS
-            d_spans_live += __popcll(nz);
-#endif
-            if (nz == 0ull) { FRR_T(4); continue; }
-            const int srank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
-            const uint32_t fincl = wave_incl_scan_dpp((uint32_t)len);
-            const int F = (int)__builtin_amdgcn_readlane((int)fincl, 63);
-            if (lane < 32) s_hfrag[w][lane] = 0ull;
-            wave_lds_fence();
-            if (len > 0) {
-                const uint32_t st = fincl - (uint32_t)len;
-                atomicOr(reinterpret_cast<uint32_t *>(&s_hfrag[w][0]) + (st >> 5), 1u << (st & 31));
-                // span descriptor: staging slot, row, and x of the span's first pixel MINUS its first fragment's position (+ 2048:
-                // a window holds at most 64 * 32 fragments), so that fragment f of the window is pixel x = field + f - 2048
-                s_q[w][srank] = (uint32_t)j | ((uint32_t)yl << 5) | (((uint32_t)xl + 2048u - st) << 10);
-            }
-            wave_lds_fence();
-            const unsigned long long hfrag_mine = s_hfrag[w][lane & 31]; // lane i keeps the heads of fragment window i
-
-            // ---- phase 3: lane = fragment.  Barycentrics, rhw, z key, LDS atomic max ----
-#ifdef FRR_DEBUG_COUNTERS
-            d_frags += F; d_fwin += (F + 63) / 64;
-#endif
+            const RowWindow rw = span_row_window<COUNT, L>(lds, R, hrow_mine, r0, lane, w, le_lo, le_hi, jbase, n_cov, dbg); // step 2
+            if (!rw.any) continue;
             int qbase = 0;
-            FRR_T(4);
-            for (int f0 = 0; f0 < F; f0 += 64) {
-                const uint32_t g_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)hfrag_mine, f0 >> 6);
-                const uint32_t g_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(hfrag_mine >> 32), f0 >> 6);
-                if (f0 + lane < F) {
-                    const uint32_t d = s_q[w][seg_rank(g_lo, g_hi, le_lo, le_hi, qbase - 1)];
+            // ---- step 3: lane = fragment.  Barycentrics, rhw, z key, LDS atomic max ----
+            for (int f0 = 0; f0 < rw.F; f0 += 64) {
+                const uint32_t g_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)rw.hfrag_mine, f0 >> 6);
+                const uint32_t g_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rw.hfrag_mine >> 32), f0 >> 6);
+                if (f0 + lane < rw.F) {
+                    const uint32_t d = L::q(lds)[w][seg_rank(g_lo, g_hi, le_lo, le_hi, qbase - 1)];
                     const int sj = (int)(d & 31u), y = (int)((d >> 5) & 31u), x = (int)(d >> 10) + (f0 - 2048) + lane;
-                    const float4 fa = s_fa[w][sj], fb = s_fb[w][sj];
-                    const float2 fc = s_fc[w][sj];
+                    const float4 fa = L::fa(lds)[w][sj], fb = L::fb(lds)[w][sj];
+                    const float2 fc = L::fc(lds)[w][sj];
                     Frag f = frag_eval(fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w, fc.x, c.ax0 + x, c.ay0 + y);
                     if (f.valid) {
-                        if (f.rhw != f.rhw) { ++n_nan; s_nanflag = 1u; }
+                        if (f.rhw != f.rhw) { ++n_nan; L::nanflag(lds) = 1u; }
                         const unsigned long long key = ((unsigned long long)zkey_frag(f.rhw) << 32) | (unsigned long long)f2u(fc.y);
-#ifdef FRR_DEBUG_COUNTERS
-                        const unsigned long long old = atomicMax(&s_key[y * TILE + x], key);
-                        d_pre += __popcll(__ballot(s_tri[w][sj].zub < (uint32_t)(old >> 32)));
-                        d_win += __popcll(__ballot(key > old));
-#else
-                        atomicMax(&s_key[y * TILE + x], key);
-#endif
+                        dbg.key_update(atomicMax(&L::key(lds)[y * TILE + x], key), key, L::tri(lds)[w][sj]);
                     }
                 }
                 qbase += __popc(g_lo) + __popc(g_hi);
             }
-            if (lane == 0) s_dirty = 1u;
-            wave_lds_fence(); // s_q / s_hfrag are rewritten by the next row window
-            FRR_T(5);
+            if (lane == 0) L::dirty(lds) = 1u;
+            wave_lds_fence(); // the span queue and the fragment heads are rewritten by the next row window
+            dbg.T(5);
         }
 
         wave_lds_fence(); // staging is rewritten by the next step
     }
-    FRR_T(1);
+    dbg.T(1);
     if (lane == 0 && n_cov) atomicAdd(&a.cnt->lane[a.lane].gtab[a.gpar].frag_covered, (unsigned long long)n_cov);
-#ifdef FRR_DEBUG_COUNTERS
-    d_rt2 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {
-        unsigned long long *d = a.cnt->dbg[blockIdx.x % DBG_COPIES];
-        atomicAdd(d + 0, (unsigned long long)d_tri); atomicAdd(d + 1, (unsigned long long)d_alive); atomicAdd(d + 2, (unsigned long long)d_rows);
-        atomicAdd(d + 3, (unsigned long long)d_spans); atomicAdd(d + 4, (unsigned long long)d_spans_live); atomicAdd(d + 5, (unsigned long long)d_frags);
-        atomicAdd(d + 6, (unsigned long long)d_fwin); atomicAdd(d + 7, (unsigned long long)d_rwin);
-        atomicAdd(d + 8, (unsigned long long)d_pre); atomicAdd(d + 9, (unsigned long long)d_win); atomicAdd(d + 10, (unsigned long long)d_rebuild);
-    }
-#endif
+    dbg.main_loop_ends(a, lane);
     if (n_nan) atomicAdd(&a.cnt->lane[a.lane].gtab[a.gpar].frag_nan, (unsigned long long)n_nan);
     __syncthreads();
-    if (s_nanflag != 0u) {
-        // NaN fragments (renderer.rs:363-366): the pixels they cover are decided by a second, unculled sweep of ALL the
+    if (L::nanflag(lds) != 0u) {
+        // ---- step 4, NaN fragments (renderer.rs:363-366): the pixels they cover are decided by a second, unculled sweep of ALL the
         // tile's records -- only what was submitted after a pixel's last NaN fragment counts there (tile_nan_begin)
-        tile_nan_begin(c, s_key, s_nanL);
+        tile_nan_begin(c, L::key(lds), L::nanL(lds));
         __syncthreads();
         uint32_t dummy_cov = 0, dummy_nan = 0;
         if (direct) {
-            unsigned long long m = __ballot(dvalid);
+            unsigned long long m = __ballot(d.valid);
             while (m) {
                 const int src = __builtin_ctzll(m);
                 m &= m - 1;
-                const uint32_t tu = (uint32_t)__builtin_amdgcn_readlane((int)dent.x, src);
-                sweep_triangle<true>(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, s_key, dummy_cov, dummy_nan, nullptr, s_nanL);
+                const uint32_t tu = (uint32_t)__builtin_amdgcn_readlane((int)d.ent.x, src);
+                sweep_triangle<true>(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, L::key(lds), dummy_cov, dummy_nan, nullptr, L::nanL(lds));
             }
         } else {
             for (uint32_t e = c.beg + (uint32_t)w; e < c.end; e += NW) {
                 const uint32_t tu = __builtin_amdgcn_readfirstlane(ents[e].x);
-                sweep_triangle<true>(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, s_key, dummy_cov, dummy_nan, nullptr, s_nanL);
+                sweep_triangle<true>(a, c, tu, PS == FRR_PS_DEPTH ? emission_id(a, tu) : order_id(a, tu), lane, L::key(lds), dummy_cov, dummy_nan, nullptr, L::nanL(lds));
             }
         }
         __syncthreads();
     }
-    FRR_T(6);
-    if constexpr (PS == FRR_PS_DEPTH) tile_resolve_depth4(a, c, s_key);
-    else tile_resolve<K, PS>(a, u, c, s_key, TEXTURED ? s_u8 : nullptr);
-#ifdef FRR_DEBUG_COUNTERS
-    FRR_T(7);
-    if (lane == 0) {
-        unsigned long long *d = a.cnt->dbg[blockIdx.x % DBG_COPIES];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) atomicAdd(d + 12 + i, (unsigned long long)d_t[i]);
-        atomicAdd(d + 20, 1ull); // waves that ran the main loop
-        if (a.dbg_tiles && w == 0) {
-            // timeline of this workgroup: start / main loop / end on the 100 MHz clock, where it ran, how much it had to do
-            unsigned long long *tl = a.dbg_tiles + (size_t)c.ltile * 8;   // (by tile; tl[7] carries the block)
-            tl[0] = d_rt0; tl[1] = d_rt1; tl[2] = d_rt2; tl[3] = __builtin_amdgcn_s_memrealtime();
-            tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32); // HW_ID, XCC_ID
-            tl[5] = (unsigned long long)(c.end - c.beg) | ((unsigned long long)(uint32_t)c.tile << 32);
-            tl[6] = d_t[1] + d_t[3] + d_t[4] + d_t[5]; tl[7] = d_t[0] | ((unsigned long long)blockIdx.x << 32);
-        }
-    }
-#endif
-#undef FRR_T
+    dbg.T(6);
+    // ---- step 5: resolve ----
+    if constexpr (PS == FRR_PS_DEPTH) tile_resolve_depth4(a, c, L::key(lds));
+    else tile_resolve<K, PS>(a, u, c, L::key(lds), TEXTURED ? L::u8(lds) : nullptr);
+    dbg.kernel_ends(a, c, lane, w);
 }
 
 // debug: the DPP scan against a serial sum (tests)

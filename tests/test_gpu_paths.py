@@ -367,3 +367,46 @@ def test_binning_chunks_of_more_than_64_blocks(oracle, world):
         r.close()
     np.testing.assert_array_equal(got_t, f.tri_id)
     np.testing.assert_array_equal(got_d.view(np.uint32), f.depth.view(np.uint32))
+
+
+_SEGMENT_COLUMN_FRAMES = {}
+
+
+def _segment_column_frames(oracle):
+    """The two small scenes of test_second_segment_column_at_three_waves and the oracle's frames of them, made once."""
+    if not _SEGMENT_COLUMN_FRAMES:
+        from f_renderer_amd import scenes
+        from . import varyings_scenes
+        W, H = 96, 64
+        for name, mesh, ovs, ops in (("depth", scenes.random_clip_triangles(400, W, H, seed=91, spread=1.2), oracle.VS_CLIP, oracle.PS_DEPTH),
+                                     ("color", varyings_scenes.clip_color_scene(seed=13, n=400), oracle.VS_CLIP_COLOR, oracle.PS_COLOR)):
+            f = oracle.Frame(W, H)
+            f.clear()
+            f.draw(mesh, ovs, ops, oracle.make_uniforms())
+            assert f.counters.tris_setup > mesh.shape[0]          # some inputs were clipped into fans
+            _SEGMENT_COLUMN_FRAMES[name] = (mesh, f)
+    return _SEGMENT_COLUMN_FRAMES
+
+
+@pytest.mark.parametrize("nw", [3, 4])
+def test_second_segment_column_at_three_waves(oracle, nw):
+    """With three waves per tile the tile kernel reads the binning segments 192..255 as a second column of wave 0.  Only
+    more than 192 binning chunks reach it, which small meshes never ask for: option bin_chunks = 256 forces them on a
+    96 x 64 frame (six tiles) of a few hundred triangles, clipped ones among them, depth-only and shaded; four waves per
+    tile (one segment per thread) are the control.  Ids, depth bits, RGBA8 and the counters are the oracle's."""
+    import f_renderer_amd as fr
+    W, H = 96, 64
+    for name, (mesh, f) in _segment_column_frames(oracle).items():
+        vs, ps = (fr.VS_CLIP, fr.PS_DEPTH) if name == "depth" else (fr.VS_CLIP_COLOR, fr.PS_COLOR)
+        r = fr.Renderer(W, H)
+        r.set_option("raster_nw", nw)
+        r.set_option("bin_chunks", 256)
+        r.clear()
+        r.draw(r.upload_mesh(mesh, vs), ps)
+        c, d, t = r.readback()
+        np.testing.assert_array_equal(t, f.tri_id, err_msg=name)
+        np.testing.assert_array_equal(d.view(np.uint32), f.depth.view(np.uint32), err_msg=name)
+        np.testing.assert_array_equal(c, f.color, err_msg=name)
+        st = r.stats()
+        assert st["tris_setup"] == f.counters.tris_setup and st["frag_covered"] == f.counters.frag_covered, (name, st)
+        r.close()
