@@ -13,8 +13,11 @@
 //   a --deferred anywhere among them shades the frame in a pass of its own: a depth-only pre-pass (FRR_PS_DEPTH), the pixel
 //       shader's input of every pixel's final owner read back (readback_varyings), and FRR_PS_PHONG run over that buffer
 //       (shade_varyings_host) -- the same bytes as the forward run
+//   --instances N anywhere among them draws the mesh N times, on a grid of translations (scaled down to fit), with ONE call:
+//       the loop over objects of phong.rs:319-331 as one instanced pass (draw_instanced)
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
 //       loaders only (no GPU): what the two loaders produce, for the CPU-side check against the Python mirror
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +42,13 @@ int main(int argc, char **argv)
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
+    long instances = -1;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (std::string(argv[i]) == "--instances") {
+            instances = std::atol(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2; --i;
+        }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -56,7 +66,8 @@ int main(int argc, char **argv)
     if ((assets && argc < 7) || (!assets && argc < 8)) {
         std::cerr << "usage: phong_headless mesh.f32 ntris tex.rgba tex_size W H out.rgba [out.ppm]\n"
                      "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
-                     "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade)\n";
+                     "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade;\n"
+                     "        --instances N: N copies on a grid in one instanced pass)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -99,6 +110,22 @@ int main(int argc, char **argv)
         frr::FrameBuffer frame_buffer = frr::FrameBuffer::create(W, H);                         // phong.rs:207
 
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317
+        if (instances >= 0) {
+            // N objects that share the mesh: model_i = translate(grid cell i) * scale(1 / columns), column-major
+            const long cols = std::max(1L, (long)std::ceil(std::sqrt((double)std::max(instances, 1L))));
+            const float s = 1.0f / (float)cols;
+            std::vector<frr::Mat4> models((size_t)instances, frr::set_identity());
+            for (long i = 0; i < instances; ++i) {
+                frr::Mat4 &m = models[(size_t)i];
+                m[0] = m[5] = m[10] = s;
+                m[12] = (((float)(i % cols) + 0.5f) * s - 0.5f) * 3.0f;
+                m[13] = (((float)(i / cols) + 0.5f) * s - 0.5f) * 2.0f;
+                m[14] = -0.25f * (float)(i % 3);
+            }
+            const frr::Instances table = renderer.upload_instances(models);
+            renderer.geometry_processing_instanced(mesh, table);                                // loop A for every object, one pass
+            std::printf("instances: n=%ld tris_in=%llu\n", instances, (unsigned long long)renderer.stats().tris_in);
+        } else
         renderer.geometry_processing(mesh);                                                     // loop A
         if (!deferred) {
             renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_PHONG);             // loop B

@@ -5,4 +5,5 @@ from . import scenes  # noqa: F401
 from ._native import (FRR_ERR_CAPACITY, FRR_ERR_HIP, FRR_ERR_INVALID, FRR_ERR_NOMEM, FRR_ERR_UNSUPPORTED,  # noqa: F401
                       FRR_OK, FrrError, build, lib)
 from .renderer import (PS_BLINN, PS_COLOR, PS_DEPTH, PS_FLAT, PS_PHONG, VS_CLIP, VS_CLIP_COLOR, VS_GOURAUD,  # noqa: F401
-                       VS_PHONG, Camera, FrameBuffer, Lines, Mesh, Renderer, set_identity, set_look_at, set_perspective)
+                       VS_PHONG, Camera, FrameBuffer, Instances, Lines, Mesh, Renderer, host_instance_mvp, set_identity, set_look_at,
+                       set_perspective)

@@ -121,6 +121,12 @@ SIGNATURES = {
     "frr_mesh_upload_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_bind_device_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_int)]),
     "frr_mesh_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_instances_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_instances_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_instances_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_geometry_instanced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_uint64)]),
+    "frr_draw_instanced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frr_host_instance_mvp": (None, [_P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "frr_lines_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_lines_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_lines_free": (C.c_int, [C.c_void_p, C.c_int]),

@@ -67,7 +67,15 @@ struct Lines {
     uint64_t n = 0;
     bool used = false;
 };
-// slot tables (frr_ctx::meshes, lines): a record goes into the first unused slot, or behind the last; its index is its id
+// an instance table (frr_instances_upload / frr_instances_bind_device): one model matrix per instance of an instanced pass
+struct Instances {
+    DevBuf<float> own;             // a host upload: the library's copy; else empty, and dev is the caller's
+    const float *dev = nullptr;    // [n][16], column-major like frr_uniforms.model
+    uint64_t n = 0;
+    bool used = false;
+    uint64_t gen = 0;              // which registration of the ctx this is (DrawSig, like Mesh::gen)
+};
+// slot tables (frr_ctx::meshes, lines, instances): a record goes into the first unused slot, or behind the last; its index is its id
 template <typename R> int slot_put(std::vector<R> &v, R &&r)
 {
     size_t i = 0;
@@ -83,6 +91,7 @@ constexpr int kSpanShapes[6][2] = {{16, 4}, {8, 6}, {6, 6}, {4, 8}, {4, 6}, {LIG
 struct UserShader {
     int nf = 0, K = 0;
     std::vector<char> code;
+    std::string geom_inst[2], clip_inst[2];   // ... of an instanced pass ([indexed mesh])
     std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6], shade[2];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel; shade: k_shade_vary [16-byte loads])
 };
 std::mutex g_shader_mu;
@@ -118,6 +127,7 @@ void release_stream(int device, hipStream_t st)
 
 struct UserModule {
     hipModule_t mod = nullptr;
+    hipFunction_t geom_inst[2] = {}, clip_inst[2] = {};
     hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {}, shade[2] = {};
 };
 
@@ -150,6 +160,7 @@ struct GeomSet {
     DevBuf<uint4> pbox;              // [recs.cap()]
     DevBuf<uint32_t> bcount;         // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
     DevBuf<uint2> clipq;             // [input triangles] the clip kernel's queue (GeomArgs::clipq)
+    DevBuf<float> inst_tab;          // [instances][32] the matrices of an instanced pass (GeomArgs::inst)
     // frr_resolve_varyings: emission index within the draw -> slot, one table per parity of the geometry pass (allocated by
     // the first resolve of a pass on this set, at the set's setup capacity); vslot_stream: the stream of its latest user
     DevBuf<uint32_t> vslot[2]; hipStream_t vslot_stream[2] = {nullptr, nullptr};
@@ -199,6 +210,7 @@ struct FrameState {
     int geom_vs = -1;              // VS of the latest frr_geometry
     uint64_t geom_ntris = 0;
     const float *geom_mesh = nullptr; uint64_t geom_mesh_gen = 0, geom_duni_hash = 0;   // ... its mesh and (a digest of) its uniforms: DrawSig
+    const float *geom_inst = nullptr; uint64_t geom_inst_gen = 0, geom_ninst = 0;   // ... and, an instanced pass, its table: DrawSig
     uint64_t geom_tex_epoch = 0, geom_sync_epoch = 0;  // ... the texture uploads and (device-bound mesh) the frr_sync calls before it: DrawSig
     uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
 };
@@ -210,6 +222,7 @@ struct Cmd {
     DevUniforms duni;          // uniforms at the time of the call
     // GEOM
     int mesh = -1; bool filter = false; int32_t fy0 = 0, fy1 = 0;
+    int inst = -1; float pv[16] = {};   // an instanced pass: its table, and proj * view at the time of the call (the table's mvp = pv * model)
     // RASTER
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
     // LINES: a list, or (lines < 0) the wireframe of the latest geometry pass in one colour
@@ -231,6 +244,7 @@ struct Cmd {
 // (An indexed mesh needs no field of its own: its index list and vertex count belong to its registration, mesh_gen, and
 // binding it again after a rewrite is a new registration.)
 struct DrawSig {
+    const float *inst; uint64_t inst_gen, ninst;   // an instanced pass: its table (bound again, or device-bound and behind a frr_sync: unproven again, like a mesh)
     const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
     int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset;
 };
@@ -327,6 +341,8 @@ struct frr_ctx {
     bool lds_attr_set = false;
     std::vector<Mesh> meshes;
     std::vector<Lines> lines;
+    std::vector<Instances> instances;
+    uint64_t inst_gen = 0;          // instance tables registered so far (Instances::gen)
     // draw_line order is resolved per pixel on a u32 plane of W * H (frr_lines.h), all-zero between commands: one per stream
     // that can carry target writes -- [0] `stream`, [1] / [2] the frame streams tstream[0] / tstream[1] -- because the line
     // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
@@ -627,6 +643,10 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
     HIP_TRY(c, hipModuleGetFunction(&m.clip, m.mod, us->clip.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.geom_idx, m.mod, us->geom_idx.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.clip_idx, m.mod, us->clip_idx.c_str()));
+    for (int idx = 0; idx < 2; ++idx) {
+        HIP_TRY(c, hipModuleGetFunction(&m.geom_inst[idx], m.mod, us->geom_inst[idx].c_str()));
+        HIP_TRY(c, hipModuleGetFunction(&m.clip_inst[idx], m.mod, us->clip_inst[idx].c_str()));
+    }
     HIP_TRY(c, hipModuleGetFunction(&m.sweep, m.mod, us->sweep.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.entries, m.mod, us->entries.c_str()));
     for (int cnt = 0; cnt < 2; ++cnt)
@@ -640,31 +660,41 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
 constexpr uint32_t kClipGrid = 2048;      // workgroups of k_geom_clip (four wavefronts each, one triangle per wavefront and step)
 
 // (IDX, an indexed mesh, is a template flag and not a null test in the kernels: the instantiations for expanded meshes keep
-// their code)
-template <int VS, bool IDX> void launch_geometry_as(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
+// their code; so is INST, an instanced pass)
+template <int VS, bool IDX, bool INST> void launch_geometry_as(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
 {
     hipStream_t st = gstream_of(c);
-    ProfScope p(c, KID_GEOM, st);
-    hipLaunchKernelGGL((k_geom_single<VS, IDX>), dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
-    if (g.use_clipq) hipLaunchKernelGGL((k_geom_clip<VS, IDX>), dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
+    hipLaunchKernelGGL((k_geom_single<VS, IDX, INST>), dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
+    if (g.use_clipq) hipLaunchKernelGGL((k_geom_clip<VS, IDX, INST>), dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
 }
 
 template <int VS> void launch_geometry(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
 {
-    if (g.idx) launch_geometry_as<VS, true>(c, g, nblocks, du);
-    else launch_geometry_as<VS, false>(c, g, nblocks, du);
+    if (g.inst) {
+        if (g.idx) launch_geometry_as<VS, true, true>(c, g, nblocks, du);
+        else launch_geometry_as<VS, false, true>(c, g, nblocks, du);
+    } else if (g.idx) launch_geometry_as<VS, true, false>(c, g, nblocks, du);
+    else launch_geometry_as<VS, false, false>(c, g, nblocks, du);
 }
 
-// the geometry kernel for the VS of the mesh
-void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const DevUniforms &du, const UserModule *um)
+// the geometry kernel for the VS of the mesh; models: the table of an instanced pass, whose matrices (GeomArgs::inst = pv * model
+// and model, per instance) are filled first -- on the pass's stream and inside the command, so a replay fills them again
+void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const DevUniforms &du, const UserModule *um, const float *models, const float *pv)
 {
+    hipStream_t st = gstream_of(c);
+    ProfScope p(c, KID_GEOM, st);
+    if (g.inst) {
+        Mat4Arg m;
+        memcpy(m.m, pv, sizeof m.m);
+        hipLaunchKernelGGL(k_instance_mvp, dim3((g.ninst * 4u + 255u) / 256u), dim3(256), 0, st, models, m, const_cast<float *>(g.inst), g.ninst);
+    }
     if (um) {   // a user shader: the same kernels, compiled with the user's functions (frr_shader_register)
-        hipStream_t st = gstream_of(c);
-        ProfScope p(c, KID_GEOM, st);
         DevUniforms d = du;
         void *args[] = {&g, &d};
-        (void)hipModuleLaunchKernel(g.idx ? um->geom_idx : um->geom, nblocks, 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
-        if (g.use_clipq) (void)hipModuleLaunchKernel(g.idx ? um->clip_idx : um->clip, std::min<uint32_t>(kClipGrid, nblocks * 4u), 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
+        const hipFunction_t geom = g.inst ? um->geom_inst[g.idx ? 1 : 0] : g.idx ? um->geom_idx : um->geom;
+        const hipFunction_t clip = g.inst ? um->clip_inst[g.idx ? 1 : 0] : g.idx ? um->clip_idx : um->clip;
+        (void)hipModuleLaunchKernel(geom, nblocks, 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
+        if (g.use_clipq) (void)hipModuleLaunchKernel(clip, std::min<uint32_t>(kClipGrid, nblocks * 4u), 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
         return;
     }
     switch (vs) {
@@ -793,13 +823,15 @@ int settle(frr_ctx *c)
 
 // ---- the two commands ------------------------------------------------------------------------------------------------
 // Loop A (phong.rs:321-331) over the mesh: one geometry pass.  Nothing of the host state is committed before the last
-// step that can fail.
+// step that can fail.  An instanced pass (cmd.inst >= 0) is the loop of phong.rs:319-331 over the objects around it as
+// well: its inputs are the (instance, triangle) pairs in that order, and every list below is sized by their number.
 int exec_geometry(frr_ctx *c, Cmd &cmd)
 {
     FrameState &f = c->fs;
     const Mesh &m = c->meshes[cmd.mesh];
+    const Instances *const it = cmd.inst >= 0 ? &c->instances[cmd.inst] : nullptr;
     const int K = frr_vs_num_varyings(m.vs);
-    const uint64_t nt = m.ntris;
+    const uint64_t nt = it ? m.ntris * it->n : m.ntris;   // (below 2^27: frr_geometry_instanced)
     const int par = f.gpar() ^ 1;
     // Beside the previous pass's tile kernel (second stream, the other workspace set) or after it (the targets' stream,
     // set 0: one set stays hot in the 256 MB Infinity Cache -- two sets of the 1M-triangle frame do not, which costs its
@@ -837,6 +869,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if (K > 0 && (rc = ensure(c, S.vary, S.recs.cap() * 3 * std::max(K, 8) /* (K <= 8 in the shader table) */)) != FRR_OK) return rc;
     const bool use_clipq = nt > 0 && (c->clip_queue > 0 || (c->clip_queue < 0 && c->clip_queue_auto));
     if (use_clipq && (rc = ensure(c, S.clipq, (size_t)nt)) != FRR_OK) return rc;
+    if (it && nt > 0 && (rc = ensure(c, S.inst_tab, (size_t)it->n * 32)) != FRR_OK) return rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // the previous pass's n_emit feeds this pass's tri_base
     if (on_g && !c->gstream) {
         // created on first use: a process maps its HIP streams onto a handful of hardware queues, and two streams that
@@ -868,6 +901,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.recs = S.recs; g.vary = S.vary; g.pbox = S.pbox; g.cnt = c->cnt;
     g.clipq = S.clipq; g.use_clipq = use_clipq ? 1 : 0;
     g.bcount = S.bcount;
+    g.inst = it && nt > 0 ? S.inst_tab.get() : nullptr; g.ntris_mesh = (uint32_t)m.ntris; g.ninst = it ? (uint32_t)it->n : 1u;
     // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it)
     f.geom_filter = GeomFilter{cmd.filter, cmd.fy0, cmd.fy1, f.rank, f.world, f.part_blocked};
     f.gpars[f.lane] = par; cmd.par = par; cmd.lane = f.lane; f.gset = si;
@@ -885,12 +919,13 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
         f.geom_duni_hash = h;
     }
     f.geom_tex_epoch = c->tex_epoch;
-    f.geom_sync_epoch = m.own_dev ? 0 : c->sync_epoch;   // (a host-uploaded mesh cannot change under the library)
+    f.geom_inst = it ? it->dev : nullptr; f.geom_inst_gen = it ? it->gen : 0; f.geom_ninst = it ? it->n : 0;
+    f.geom_sync_epoch = m.own_dev && (!it || it->own || !it->n) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
     f.tris_in += nt; f.draws += 1;
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
     } else {
-        launch_geometry_vs(c, g, nblocks, m.vs, cmd.duni, um);
+        launch_geometry_vs(c, g, nblocks, m.vs, cmd.duni, um, it ? it->dev : nullptr, cmd.pv);
         f.scan_pending = true;
     }
     HIP_TRY(c, hipGetLastError());
@@ -1030,6 +1065,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         // does this pass's need of the work lists fit for sure?  (exec_cmd waits for the event if not: frr_ctx::proven)
         DrawSig sig;
         memset(&sig, 0, sizeof sig);
+        sig.inst = f.geom_inst; sig.inst_gen = f.geom_inst_gen; sig.ninst = f.geom_ninst;
         sig.mesh = f.geom_mesh; sig.mesh_gen = f.geom_mesh_gen; sig.ntris = f.geom_ntris; sig.duni_hash = f.geom_duni_hash; sig.join_epoch = c->join_epoch;
         sig.tex_epoch = f.geom_tex_epoch; sig.sync_epoch = f.geom_sync_epoch;
         sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
@@ -1848,6 +1884,13 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     const std::string geom_idx_expr = "frr::k_geom_single<" + U + ", true>", clip_idx_expr = "frr::k_geom_clip<" + U + ", true>";   // indexed meshes
     (void)hiprtcAddNameExpression(prog, geom_idx_expr.c_str());
     (void)hiprtcAddNameExpression(prog, clip_idx_expr.c_str());
+    std::string geom_inst_expr[2], clip_inst_expr[2];   // instanced passes ([indexed mesh])
+    for (int idx = 0; idx < 2; ++idx) {
+        geom_inst_expr[idx] = "frr::k_geom_single<" + U + (idx ? ", true, true>" : ", false, true>");
+        clip_inst_expr[idx] = "frr::k_geom_clip<" + U + (idx ? ", true, true>" : ", false, true>");
+        (void)hiprtcAddNameExpression(prog, geom_inst_expr[idx].c_str());
+        (void)hiprtcAddNameExpression(prog, clip_inst_expr[idx].c_str());
+    }
     const std::string sweep_expr = "frr::k_raster<" + Ks + ", " + U + ">";   // the brute-force tile kernel (option raster_sweep)
     (void)hiprtcAddNameExpression(prog, sweep_expr.c_str());
     const std::string entries_expr = "frr::k_raster_entries<" + Ks + ", " + U + ">";   // windows whose rows share depth entries (x0 < 0)
@@ -1874,6 +1917,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     bool ok = true;
     auto lowered = [&](const std::string &e) { const char *n = nullptr; ok = ok && hiprtcGetLoweredName(prog, e.c_str(), &n) == HIPRTC_SUCCESS && n; return std::string(n ? n : ""); };
     us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->geom_idx = lowered(geom_idx_expr); us->clip_idx = lowered(clip_idx_expr); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
+    for (int idx = 0; idx < 2; ++idx) { us->geom_inst[idx] = lowered(geom_inst_expr[idx]); us->clip_inst[idx] = lowered(clip_inst_expr[idx]); }
     for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) us->shade[vec] = lowered(shade_expr[vec]);
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
@@ -1961,6 +2005,70 @@ int frr_geometry(frr_ctx *c, int mesh, uint64_t *ntris_setup)
     return FRR_OK;
 }
 
+// ---- instanced passes: one mesh under a table of model matrices (the loop over objects of phong.rs:319-331) ----------
+static int instances_register(frr_ctx *c, Instances &&t, uint64_t ninst, int *inst_out)
+{
+    if (t.own) t.dev = t.own;
+    t.n = ninst; t.used = true; t.gen = ++c->inst_gen;
+    *inst_out = slot_put(c->instances, std::move(t));
+    return FRR_OK;
+}
+int frr_instances_upload(frr_ctx *c, const float *models, uint64_t ninst, int *inst_out)
+{
+    if (!c || !inst_out || (ninst && !models)) return fail(c, FRR_ERR_INVALID, "bad instance table");
+    if (ninst >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Instances t;
+    if (ninst) { const int rc = upload(c, t.own, models, (size_t)ninst * 16 * sizeof(float), "instance table"); if (rc != FRR_OK) return rc; }
+    return instances_register(c, std::move(t), ninst, inst_out);
+}
+int frr_instances_bind_device(frr_ctx *c, const void *dev_models, uint64_t ninst, int *inst_out)
+{
+    if (!c || !inst_out || (ninst && !dev_models)) return fail(c, FRR_ERR_INVALID, "bad instance table");
+    if (ninst >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
+    if (((uintptr_t)dev_models & 15u) != 0) return fail(c, FRR_ERR_INVALID, "instance table pointer must be 16-byte aligned");
+    c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
+    Instances t; t.dev = (const float *)dev_models;
+    return instances_register(c, std::move(t), ninst, inst_out);
+}
+int frr_instances_free(frr_ctx *c, int inst)
+{
+    if (!c || !slot_ok(c->instances, inst)) return fail(c, FRR_ERR_INVALID, "bad instance table id");
+    { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a pass over it
+    c->instances[inst] = Instances();
+    return FRR_OK;
+}
+// the GEOM command of an instanced pass, checked: nothing is allocated for a pass that is refused
+static int instanced_cmd(frr_ctx *c, int mesh, int inst, Cmd *cmd)
+{
+    if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
+    if (!slot_ok(c->instances, inst)) return fail(c, FRR_ERR_INVALID, "bad instance table id");
+    const uint64_t ntris = c->meshes[mesh].ntris, ninst = c->instances[inst].n;
+    if (ntris && ninst && ntris * ninst >= (1ull << 27))   // (both factors are below 2^27: no wrap)
+        return fail(c, FRR_ERR_UNSUPPORTED, "2^27 (instance, triangle) pairs or more in one pass (order keys: 32 per input triangle)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    cmd->kind = Cmd::GEOM; cmd->mesh = mesh; cmd->inst = inst; cmd->duni = c->duni;
+    h_mat4_mul(c->uni.proj, c->uni.view, cmd->pv);   // as refresh_dev_uniforms builds u.mvp
+    return FRR_OK;
+}
+int frr_geometry_instanced(frr_ctx *c, int mesh, int inst, uint64_t *ntris_setup)
+{
+    Cmd cmd;
+    int rc = instanced_cmd(c, mesh, inst, &cmd);
+    if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
+    if (ntris_setup) {
+        if ((rc = finish(c)) != FRR_OK) return rc;
+        *ntris_setup = c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit;
+    }
+    return FRR_OK;
+}
+void frr_host_instance_mvp(const float proj[16], const float view[16], const float model[16], float out[16])
+{
+    float pv[16];
+    h_mat4_mul(proj, view, pv);
+    h_mat4_mul(pv, model, out);
+}
+
 // argument checks of frr_raster; *nothing: the call is valid and draws nothing
 static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, bool *nothing)
 {
@@ -2018,6 +2126,16 @@ int frr_draw(frr_ctx *c, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0
     cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
     const int rc = exec_cmd(c, cmd);
     if (rc != FRR_OK) return rc;
+    return frr_raster(c, ps_id, x0, x1, y0, y1);
+}
+
+int frr_draw_instanced(frr_ctx *c, int mesh, int inst, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
+{
+    Cmd cmd;
+    int rc = instanced_cmd(c, mesh, inst, &cmd);
+    if (rc != FRR_OK) return rc;
+    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;   // as frr_draw
+    if ((rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
     return frr_raster(c, ps_id, x0, x1, y0, y1);
 }
 

@@ -189,6 +189,12 @@ struct GeomArgs {
                             // the rest of that range is zero (= an empty box); fan triangle at fan slot f: entry ntris + f
     uint32_t *bcount;       // [nblocks] see pbox
     Counters *cnt;
+    // An instanced pass (frr_geometry_instanced; the INST instantiations of the geometry kernels): input t' of the pass is
+    // triangle t' % ntris_mesh of the mesh under the matrices of instance t' / ntris_mesh -- dense, an instance is not
+    // padded to whole blocks -- and ntris = ntris_mesh * ninst.  Everything above is indexed by t' as it is by t.
+    const float *inst;      // [ninst][mvp 16 | model 16]: k_instance_mvp; else null
+    uint32_t ntris_mesh;    // the mesh's own triangle count
+    uint32_t ninst;
 };
 
 // tile-row ownership over a range of tile rows: ty % world == rank (interleaved), or, blocked != 0, the rows [brow0, brow1); world <= 1: all

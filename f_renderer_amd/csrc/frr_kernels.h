@@ -326,9 +326,16 @@ constexpr int CLIP_INBLOCK = GEOM_BLOCK / 64;   // clipped inputs a geometry blo
 // u32 loads (12 contiguous bytes per thread), then the same 16-byte vector loads of run_vs at in + idx * NF.  The clamp is
 // not the error path -- registration refuses a mesh with an index >= nverts -- it keeps the loads inside the vertex array
 // whatever an index buffer that was rewritten in place without a re-bind holds.
-template <int NF, bool IDX>
-__device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const float *vp[3])
+// With INST (an instanced pass, GeomArgs::inst) t is the pass's input t' and the corners are those of mesh triangle
+// t' % ntris_mesh; *inst: the matrices of instance t' / ntris_mesh.
+template <int NF, bool IDX, bool INST = false>
+__device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const float *vp[3], const float **inst = nullptr)
 {
+    if constexpr (INST) {
+        const uint32_t i = t / g.ntris_mesh;
+        t -= i * g.ntris_mesh;
+        *inst = g.inst + (size_t)i * 32;
+    }
     if constexpr (IDX) {
         const uint32_t *ix = g.idx + (size_t)t * 3;
         const uint32_t last = g.nverts - 1u;
@@ -341,18 +348,41 @@ __device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const 
     }
 }
 
+// The vertex shader over the three corners of one input (renderer.rs:113-116).  INST: under the matrices of the input's
+// instance (im: 32 floats of GeomArgs::inst) -- only the vertex shader sees them (VSUniform.model, phong.rs:26-31, :119);
+// every other field is the call's.  The copy is per thread: a block spans many instances.  What the shader does not read
+// of it costs nothing (the fields it does read and that are not replaced stay kernel arguments).
+template <int VS, bool INST>
+__device__ __forceinline__ void run_vs3(const DevUniforms &u, const float *im, const float *const in[3], float pos[3][4], float ctx[3][VSInfo<VS>::K > 0 ? VSInfo<VS>::K : 1])
+{
+    if constexpr (INST) {
+        DevUniforms ui = u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 a = reinterpret_cast<const float4 *>(im)[k], b = reinterpret_cast<const float4 *>(im)[4 + k];
+            ui.mvp[4 * k] = a.x; ui.mvp[4 * k + 1] = a.y; ui.mvp[4 * k + 2] = a.z; ui.mvp[4 * k + 3] = a.w;
+            ui.model[4 * k] = b.x; ui.model[4 * k + 1] = b.y; ui.model[4 * k + 2] = b.z; ui.model[4 * k + 3] = b.w;
+        }
+#pragma unroll
+        for (int v = 0; v < 3; ++v) run_vs<VS, true>(ui, in[v], pos[v], ctx[v]);
+    } else {
+#pragma unroll
+        for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in[v], pos[v], ctx[v]);
+    }
+}
+
 // Returns the lane's binning record (all zero for lanes that emit no fan triangle).  eoff: the input's emission offset
 // within its geometry block (tinfo[t] >> FAN_BITS).
-template <int VS, bool IDX>
+template <int VS, bool IDX, bool INST = false>
 __device__ __forceinline__ uint4 clip_triangle_wave(const GeomArgs &g, const DevUniforms &u, uint32_t t, uint32_t fbase, uint32_t eoff, int lane,
                                                    float (*s_xy)[2], int32_t *s_key, float (*s_v)[7 + (VSInfo<VS>::K > 0 ? VSInfo<VS>::K : 1)])
 {
     constexpr int NF = VSInfo<VS>::NF, K = VSInfo<VS>::K, KS = K > 0 ? K : 1;
     float pos[3][4], ctx[3][KS];
-    const float *in[3];
-    tri_inputs<NF, IDX>(g, t, in);
-#pragma unroll
-    for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in[v], pos[v], ctx[v]);
+    const float *in[3], *im = nullptr;
+    if constexpr (INST) t = __builtin_amdgcn_readfirstlane(t);   // (one triangle per wave: its instance's matrices are wave-uniform)
+    tri_inputs<NF, IDX, INST>(g, t, in, &im);
+    run_vs3<VS, INST>(u, im, in, pos, ctx);
     // this lane's vertex
     float p[4], c[KS];
     bool keep;
@@ -552,7 +582,7 @@ __device__ __forceinline__ void geom_bookkeeping(const GeomArgs &g)
     me.tinfo = g.tinfo; me.fanbase = g.fanbase; me.fan_okey = g.fan_okey; me.block_prefix = g.block_prefix;
 }
 
-template <int VS, bool IDX>
+template <int VS, bool IDX, bool INST = false>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUniforms u)
 {
     __shared__ uint32_t s_w[4];
@@ -576,10 +606,9 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
     uint32_t n = 0;   // triangles this input emits (the reference's count)
     bool clipped = false;
     if (t < g.ntris) {
-        const float *in[3];
-        tri_inputs<NF, IDX>(g, t, in);
-#pragma unroll
-        for (int v = 0; v < 3; ++v) run_vs<VS, true>(u, in[v], pos[v], ctx[v]);
+        const float *in[3], *im = nullptr;
+        tri_inputs<NF, IDX, INST>(g, t, in, &im);
+        run_vs3<VS, INST>(u, im, in, pos, ctx);
         n = classify(pos, clipped);
     }
     if (seq_is_cancelled(first_bad, g.seq, g.epoch, false)) return;   // an earlier command failed: the host replays from there (nothing written yet)
@@ -728,13 +757,13 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         for (uint32_t e = (uint32_t)w; e < nin; e += GEOM_BLOCK / 64) {
             const uint32_t en = s_cl[e];
-            (void)clip_triangle_wave<VS, IDX>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
+            (void)clip_triangle_wave<VS, IDX, INST>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
         }
     }
 }
 
 // the clipped inputs the geometry blocks queued (GeomArgs::use_clipq), one wavefront per triangle over the whole chip
-template <int VS, bool IDX>
+template <int VS, bool IDX, bool INST = false>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniforms u)
 {
     __shared__ float s_cxy[GEOM_BLOCK / 64][CLIP_MAXV][2];
@@ -746,8 +775,26 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniform
     const uint32_t stride = gridDim.x * (GEOM_BLOCK / 64);
     for (uint32_t e = blockIdx.x * (GEOM_BLOCK / 64) + (uint32_t)w; e < n; e += stride) {
         const uint2 q = g.clipq[e];
-        (void)clip_triangle_wave<VS, IDX>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
+        (void)clip_triangle_wave<VS, IDX, INST>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
     }
+}
+
+// The matrices of an instanced pass (GeomArgs::inst): per instance mvp = pv * model (phong.rs:119: proj * view * model is
+// left-associative, pv = proj * view is the host's product of refresh_dev_uniforms), column by column with the
+// association of glam's Mat4 * Vec4, ((c0*x + c1*y) + c2*z) + c3*w -- frr_host_instance_mvp is its host build -- and a
+// copy of the model matrix.  One thread per (instance, column).
+struct Mat4Arg { float m[16]; };
+__global__ __launch_bounds__(256) void k_instance_mvp(const float *__restrict__ models, Mat4Arg pv, float *__restrict__ out, uint32_t ninst)
+{
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= ninst * 4u) return;
+    const uint32_t i = e >> 2, c = e & 3u;
+    const float4 b = reinterpret_cast<const float4 *>(models)[e];   // column c of instance i
+    float o[4];
+    mat4_mul_vec4(pv.m, b.x, b.y, b.z, b.w, o);
+    float4 *dst = reinterpret_cast<float4 *>(out + (size_t)i * 32);
+    dst[c] = make_float4(o[0], o[1], o[2], o[3]);
+    dst[4 + c] = b;
 }
 
 // An empty mesh launches no geometry kernel proper: the per-draw bookkeeping alone.

@@ -304,6 +304,7 @@ inline Model::Indexed Model::indexed_inputs() const
 
 struct Mesh { int id = -1; uint64_t ntris = 0; int vs = 0; };
 struct Lines { int id = -1; uint64_t nlines = 0; };   // a list of draw_line calls on the device
+struct Instances { int id = -1; uint64_t ninst = 0; };   // a table of model matrices on the device: one per instance of an instanced pass
 struct LineSegment { uint32_t x1, y1, x2, y2; };
 static_assert(sizeof(LineSegment) == 16, "LineSegment must be 4 packed u32");
 
@@ -364,6 +365,22 @@ public:
     }
     // A list of FrameBuffer::draw_line calls (renderer.rs:540-588), in call order.  A segment whose walk would leave the
     // buffer (the reference's panic) -> frr::Error naming it, and no list.
+    // The model matrices of the objects that share a mesh (phong.rs:319-331: vs_uniform.model per object), column-major like
+    // uniforms.model; bind_instances_device: a table already in device memory (16-byte aligned; after an in-place rewrite:
+    // frame_fence, rewrite, bind again).
+    Instances upload_instances(const std::vector<Mat4> &models)
+    {
+        Instances t; t.ninst = models.size();
+        check(frr_instances_upload(ctx_, models.empty() ? nullptr : models[0].data(), t.ninst, &t.id));
+        return t;
+    }
+    Instances bind_instances_device(const void *dev_models, uint64_t ninst)
+    {
+        Instances t; t.ninst = ninst;
+        check(frr_instances_bind_device(ctx_, dev_models, ninst, &t.id));
+        return t;
+    }
+    void free_instances(Instances &t) { if (t.id >= 0) { check(frr_instances_free(ctx_, t.id)); t.id = -1; } }
     Lines upload_lines(const std::vector<LineSegment> &segments, const std::vector<std::array<uint8_t, 4>> &colors)
     {
         if (segments.size() != colors.size()) throw Error(FRR_ERR_INVALID, "one colour per segment");
@@ -415,6 +432,14 @@ public:
     void draw(const Mesh &m, int pixel_shader)
     {
         check(frr_draw(ctx_, m.id, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
+    }
+    // Loop A under every matrix of the table in turn -- the loop over objects around it, phong.rs:319-331 -- into ONE setup list
+    // in (instance, triangle) order; draw_instanced: that and one rasterization over the list.  Bit for bit what one
+    // draw(mesh) per matrix gives with uniforms.model = that matrix.
+    void geometry_processing_instanced(const Mesh &m, const Instances &t) { check(frr_geometry_instanced(ctx_, m.id, t.id, nullptr)); }
+    void draw_instanced(const Mesh &m, const Instances &t, int pixel_shader)
+    {
+        check(frr_draw_instanced(ctx_, m.id, t.id, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
     }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream

@@ -168,6 +168,27 @@ class Lines:
             self.id = None
 
 
+class Instances:
+    """A table of model matrices on the device (Renderer.upload_instances / bind_instances_device): one per instance of an
+    instanced pass."""
+
+    def __init__(self, renderer, inst_id, ninst, keepalive=None):
+        self.renderer, self.id, self.ninst, self._keep = renderer, inst_id, ninst, keepalive
+
+    def free(self):
+        if self.id is not None:
+            self.renderer._check(N.lib().frr_instances_free(self.renderer._ctx, self.id))
+            self.id = None
+
+
+def host_instance_mvp(proj, view, model):
+    """(proj * view) * model as the device computes it per instance (frr_host_instance_mvp): float32 [16], column-major."""
+    p, v, m = (np.ascontiguousarray(x, np.float32).reshape(16) for x in (proj, view, model))
+    out = np.zeros(16, np.float32)
+    N.lib().frr_host_instance_mvp(_fp(p), _fp(v), _fp(m), _fp(out))
+    return out
+
+
 def _options_from_env():
     """The test-suite and the tools select code paths with FRR_* environment variables; the library reads none, so they
     are translated into frr_set_option calls here (every new Renderer)."""
@@ -289,6 +310,23 @@ class Renderer:
         self._check(self._lib.frr_mesh_bind_device_indexed(self._ctx, C.c_void_p(vert_ptr), nverts, C.c_void_p(idx_ptr), ntris, vs_id, C.byref(mid)))
         return Mesh(self, mid.value, ntris, vs_id, keepalive)
 
+    def upload_instances(self, models):
+        """The model matrices of the objects that share a mesh (phong.rs:319-331: vs_uniform.model per object) -> device.
+        models: float32 [ninst, 16] (or [ninst, 4, 4] in memory order), column-major like uniforms.model."""
+        a = np.ascontiguousarray(models, np.float32)
+        if a.size % 16:
+            raise FrrError(N.FRR_ERR_INVALID, "models size is not a multiple of 16")
+        iid = C.c_int()
+        self._check(self._lib.frr_instances_upload(self._ctx, a.ctypes.data if a.size else None, a.size // 16, C.byref(iid)))
+        return Instances(self, iid.value, a.size // 16)
+
+    def bind_instances_device(self, ptr, ninst, keepalive=None):
+        """Same, for a table already in HBM (float32 [ninst,16], 16-byte aligned, e.g. a torch tensor's data_ptr()).  After an
+        in-place rewrite: frame_fence, rewrite, bind again."""
+        iid = C.c_int()
+        self._check(self._lib.frr_instances_bind_device(self._ctx, C.c_void_p(ptr), ninst, C.byref(iid)))
+        return Instances(self, iid.value, ninst, keepalive)
+
     def upload_lines(self, xyxy, rgba):
         """A list of FrameBuffer::draw_line calls (renderer.rs:540-588) -> device.  xyxy: uint32 [n,4] = x1, y1, x2, y2;
         rgba: uint8 [n,4], or one colour for all.  A segment that would panic in the reference (its walk leaves the
@@ -393,6 +431,20 @@ class Renderer:
         wr = width_range or (0, self.width)
         hr = height_range or (0, self.height)
         self._check(self._lib.frr_draw(self._ctx, mesh.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
+
+    def geometry_processing_instanced(self, mesh, instances, count=False):
+        """Loop A under every matrix of the table in turn (phong.rs:319-331: the loop over objects around it), into ONE setup
+        list in (instance, triangle) order (frr_geometry_instanced)."""
+        n = C.c_uint64()
+        self._check(self._lib.frr_geometry_instanced(self._ctx, mesh.id, instances.id, C.byref(n) if count else None))
+        return int(n.value) if count else None
+
+    def draw_instanced(self, mesh, instances, pixel_shader, width_range=None, height_range=None):
+        """geometry_processing_instanced + rasterization: what one draw(mesh) per matrix with set_uniforms(model=...) in
+        between gives, bit for bit, in one pass (frr_draw_instanced)."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        self._check(self._lib.frr_draw_instanced(self._ctx, mesh.id, instances.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
 
     def draw_lines(self, lines):
         """for each segment of the list, in order: frame_buffer.draw_line(x1, y1, x2, y2, color) on the colour target (depth

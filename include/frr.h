@@ -277,6 +277,48 @@ int frr_raster(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int3
  * frr_readback_setup. */
 int frr_draw(frr_ctx *ctx, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
 
+/* ---- instanced passes --------------------------------------------------------------------- */
+
+/* One mesh under many model matrices in ONE geometry pass: the reference's loop over objects (phong.rs:319-331 runs
+ * geometry_processing with a fresh vs_uniform.model per object) without one draw per object.
+ * An instance table is ninst model matrices, 16 f32 each, column-major like frr_uniforms.model.
+ * frr_geometry_instanced(mesh, inst) is BY DEFINITION this loop, concatenated into one setup list in that order:
+ *     for i in 0..ninst:
+ *         vs_uniform.model = models[i]                   (phong.rs:26-31, :119: mvp = proj * view * model)
+ *         for t in 0..ntris: geometry_processing(mesh[t]) (renderer.rs:96-267)
+ * and frr_draw_instanced is that loop followed by one Loop B over the list (renderer.rs:269-384).  Hence:
+ * - Emission order is (instance, input triangle, fan triangle) (renderer.rs:245-266 within an input).  The id of a setup
+ *   triangle of instance i is the frame's running count before the pass + what instances < i emitted + its offset
+ *   within instance i; the ids of later draws of the frame continue behind the whole pass.  The ids of one instance are
+ *   one contiguous range (ranged frr_shade_varyings: per-instance pixel uniforms).
+ * - Where fragments tie in depth the later instance wins (renderer.rs:363: `rhw < depth` rejects, equal replaces), as
+ *   the later triangle of one mesh does.
+ * - Depth bits, ids, RGBA8, the setup list and tris_setup / frag_covered / frag_nan are, bit for bit, those of ninst
+ *   plain frr_draw calls of the mesh, each after an frr_set_uniforms that differs only in model = models[i].
+ * - Statistics: tris_in grows by ntris * ninst, draws by 1.
+ * - Only the vertex shader sees the instance's matrices (the model matrix belongs to VSUniform, phong.rs:26-31;
+ *   PSUniform, phong.rs:34-47, has none): in the geometry kernels u.mvp and u.model are the instance's, for built-in and
+ *   user vertex shaders alike; every other field is the call's; the pixel shader sees the call's uniforms unchanged,
+ *   u.model / u.mvp included.  A vertex shader that reads no matrix (FRR_VS_CLIP, FRR_VS_CLIP_COLOR) draws ninst
+ *   identical copies, which is valid.
+ * - mvp_i = (proj * view) * models[i] (phong.rs:119, left-associative), each product column by column as
+ *   ((c0*x + c1*y) + c2*z) + c3*w with no contraction, computed on the device; frr_host_instance_mvp below is the host
+ *   build of the same arithmetic.
+ * - NaN, +-inf and all-zero matrices are not refused: the reference would compute with them.
+ * ninst == 0 is a pass that emits nothing, like an empty mesh (draws still counts it); ninst == 1 is a plain draw under
+ * models[0].  ntris * ninst >= 2^27: FRR_ERR_UNSUPPORTED (the order-key limit of the mesh entry points, on the product),
+ * checked at the draw before anything is allocated.  FRR_ERR_INVALID: a NULL table with ninst > 0, a device pointer that
+ * is not 16-byte aligned, an unknown or freed id.
+ * A device-bound table is borrowed until frr_instances_free; rewriting it in place follows the rule of device-bound
+ * meshes: frr_frame_fence, rewrite, bind again.  The call is logged, verified and replayed like frr_geometry / frr_draw,
+ * and everything downstream of a geometry pass takes the instanced setup list as it is: frr_raster with any window,
+ * frr_readback_setup, frr_draw_wireframe, frr_resolve_varyings, frr_shade_varyings, the partition filter of a draw. */
+int frr_instances_upload(frr_ctx *ctx, const float *models, uint64_t ninst, int *inst_out);
+int frr_instances_bind_device(frr_ctx *ctx, const void *dev_models, uint64_t ninst, int *inst_out);
+int frr_instances_free(frr_ctx *ctx, int inst);
+int frr_geometry_instanced(frr_ctx *ctx, int mesh, int inst, uint64_t *ntris_setup);
+int frr_draw_instanced(frr_ctx *ctx, int mesh, int inst, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
+
 /* ---- lines ------------------------------------------------------------------------------- */
 
 /* FrameBuffer::draw_line(x1, y1, x2, y2, color) (renderer.rs:540-588), the reference's only drawing primitive besides the
@@ -477,7 +519,7 @@ int frr_set_option(frr_ctx *ctx, const char *name, int64_t value);
 /* per-kernel accumulated device time (ms) and launch count since frr_profile_reset.  `mask`:
  * 0 = off, -1 = every kernel, else OR of (1 << index) with index in the order k_clear,
  * k_geom, k_geom_scan, k_bin_count, k_tile_scan, k_bin_fill, k_raster,
- * k_bin_seg, k_lines_mark, k_lines_paint (k_geom covers the clip kernel too when the clip queue is in use).  A profiled launch is bracketed by two
+ * k_bin_seg, k_lines_mark, k_lines_paint (k_geom covers the clip kernel too when the clip queue is in use, and the kernel that fills an instanced pass's matrices).  A profiled launch is bracketed by two
  * HIP events on the ctx stream. */
 int frr_profile_enable(frr_ctx *ctx, int mask);
 /* bracket only every `period`-th launch of each selected kernel (default 1): an event pair costs the
@@ -502,6 +544,9 @@ float frr_host_atan2f(float y, float x);
 /* the line kernels' per-iteration arithmetic compiled for the host (cf. frr_host_atan2f): the linear pixel indices
  * y * width + x that draw_line(x1, y1, x2, y2) paints, in write order; returns their number (written up to cap) */
 int64_t frr_host_line_pixels(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2, uint32_t width, uint64_t *out, uint64_t cap);
+/* host build of the device's per-instance matrix product (cf. frr_host_atan2f, frr_host_line_pixels):
+ * out = (proj * view) * model, column-major, every element ((a0*b0 + a1*b1) + a2*b2) + a3*b3 */
+void frr_host_instance_mvp(const float proj[16], const float view[16], const float model[16], float out[16]);
 /* MVP x vertex contraction of a pos3/uv2/normal3 mesh with the current uniforms: clip xyzw per vertex
  * (ntris*3*4 floats) by the exact VALU form (use_mfma = 0, glam's association) or by
  * v_mfma_f32_16x16x4_f32 (use_mfma = 1, an fmaf chain: NOT bit-identical); *ms = kernel time. */

@@ -85,6 +85,13 @@ pub mod ffi {
         pub fn frr_geometry(ctx: *mut frr_ctx, mesh: c_int, ntris_setup: *mut u64) -> c_int;
         pub fn frr_raster(ctx: *mut frr_ctx, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
         pub fn frr_draw(ctx: *mut frr_ctx, mesh: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
+        // instanced passes: one mesh under a table of model matrices (the loop over objects of phong.rs:319-331) in one pass
+        pub fn frr_instances_upload(ctx: *mut frr_ctx, models: *const f32, ninst: u64, inst_out: *mut c_int) -> c_int;
+        pub fn frr_instances_bind_device(ctx: *mut frr_ctx, dev_models: *const c_void, ninst: u64, inst_out: *mut c_int) -> c_int;
+        pub fn frr_instances_free(ctx: *mut frr_ctx, inst: c_int) -> c_int;
+        pub fn frr_geometry_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ntris_setup: *mut u64) -> c_int;
+        pub fn frr_draw_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
+        pub fn frr_host_instance_mvp(proj: *const f32, view: *const f32, model: *const f32, out: *mut f32);
         pub fn frr_sync(ctx: *mut frr_ctx) -> c_int;
         pub fn frr_readback(ctx: *mut frr_ctx, rgba: *mut u8, depth: *mut f32, tri_id: *mut u32) -> c_int;
         pub fn frr_get_stats(ctx: *mut frr_ctx, out: *mut frr_stats) -> c_int;
