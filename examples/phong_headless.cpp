@@ -15,6 +15,8 @@
 //       (shade_varyings_host) -- the same bytes as the forward run
 //   --instances N anywhere among them draws the mesh N times, on a grid of translations (scaled down to fit), with ONE call:
 //       the loop over objects of phong.rs:319-331 as one instanced pass (draw_instanced)
+//   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
+//       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
 //       loaders only (no GPU): what the two loaders produce, for the CPU-side check against the Python mirror
 #include <algorithm>
@@ -49,6 +51,15 @@ int main(int argc, char **argv)
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
             argc -= 2; --i;
         }
+    int cull = FRR_CULL_NONE;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (std::string(argv[i]) == "--cull") {
+            const std::string v = argv[i + 1];
+            if (v != "neg" && v != "pos") { std::cerr << "--cull takes neg or pos\n"; return 2; }
+            cull = v == "neg" ? FRR_CULL_NEG : FRR_CULL_POS;
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2; --i;
+        }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -67,7 +78,8 @@ int main(int argc, char **argv)
         std::cerr << "usage: phong_headless mesh.f32 ntris tex.rgba tex_size W H out.rgba [out.ppm]\n"
                      "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
                      "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade;\n"
-                     "        --instances N: N copies on a grid in one instanced pass)\n";
+                     "        --instances N: N copies on a grid in one instanced pass;\n"
+                     "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -110,6 +122,7 @@ int main(int argc, char **argv)
         frr::FrameBuffer frame_buffer = frr::FrameBuffer::create(W, H);                         // phong.rs:207
 
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317
+        if (cull != FRR_CULL_NONE) renderer.set_cull(cull);
         if (instances >= 0) {
             // N objects that share the mesh: model_i = translate(grid cell i) * scale(1 / columns), column-major
             const long cols = std::max(1L, (long)std::ceil(std::sqrt((double)std::max(instances, 1L))));

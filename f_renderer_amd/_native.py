@@ -30,6 +30,7 @@ HIPCC_FLAGS = [
 FRR_OK, FRR_ERR_INVALID, FRR_ERR_HIP, FRR_ERR_NOMEM, FRR_ERR_UNSUPPORTED, FRR_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 VS_CLIP, VS_CLIP_COLOR, VS_PHONG, VS_GOURAUD = 0, 1, 2, 3
 PS_DEPTH, PS_FLAT, PS_COLOR, PS_PHONG, PS_BLINN = 0, 1, 2, 3, 4
+CULL_NONE, CULL_NEG, CULL_POS = 0, 1, 2
 MAX_VARYINGS = 16
 
 
@@ -141,6 +142,7 @@ SIGNATURES = {
     "frr_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "frr_set_uniforms": (C.c_int, [C.c_void_p, _P(Uniforms)]),
     "frr_shader_register": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _P(C.c_int)]),
+    "frr_set_cull": (C.c_int, [C.c_void_p, C.c_int]),
     "frr_set_user_uniforms": (C.c_int, [C.c_void_p, _P(C.c_float), C.c_int]),
     "frr_vs_input_floats": (C.c_int, [C.c_int]),
     "frr_vs_num_varyings": (C.c_int, [C.c_int]),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "frr_set_perspective": (None, [C.c_float, C.c_float, C.c_float, C.c_float, _P(C.c_float)]),
     "frr_debug_atan2f": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "frr_host_atan2f": (C.c_float, [C.c_float, C.c_float]),
+    "frr_host_cull_det": (C.c_float, [_P(C.c_float)]),
     "frr_debug_scan64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "frr_debug_rcp_check": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "frr_debug_gather_calib": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -212,6 +212,7 @@ struct FrameState {
     const float *geom_mesh = nullptr; uint64_t geom_mesh_gen = 0, geom_duni_hash = 0;   // ... its mesh and (a digest of) its uniforms: DrawSig
     const float *geom_inst = nullptr; uint64_t geom_inst_gen = 0, geom_ninst = 0;   // ... and, an instanced pass, its table: DrawSig
     uint64_t geom_tex_epoch = 0, geom_sync_epoch = 0;  // ... the texture uploads and (device-bound mesh) the frr_sync calls before it: DrawSig
+    int geom_cull = FRR_CULL_NONE;                     // ... and the cull mode it ran under: DrawSig
     uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
 };
 
@@ -222,6 +223,7 @@ struct Cmd {
     DevUniforms duni;          // uniforms at the time of the call
     // GEOM
     int mesh = -1; bool filter = false; int32_t fy0 = 0, fy1 = 0;
+    int cull = FRR_CULL_NONE;           // frr_set_cull at the time of the call (a replay runs the pass under it again)
     int inst = -1; float pv[16] = {};   // an instanced pass: its table, and proj * view at the time of the call (the table's mvp = pv * model)
     // RASTER
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
@@ -241,12 +243,13 @@ struct Cmd {
 // Everything the geometry pass reads can change what it emits: the mesh (its registration, and for a device-bound one the
 // frr_sync calls since -- the caller may rewrite it in place then), the uniforms (a user VS may read any field, texture
 // pointers and sizes included) and the texture contents (frr_texture_upload count).
+// So can the cull mode (frr_set_cull): a pass proven to fit under one mode says nothing about another.
 // (An indexed mesh needs no field of its own: its index list and vertex count belong to its registration, mesh_gen, and
 // binding it again after a rewrite is a new registration.)
 struct DrawSig {
     const float *inst; uint64_t inst_gen, ninst;   // an instanced pass: its table (bound again, or device-bound and behind a frr_sync: unproven again, like a mesh)
     const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
-    int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset;
+    int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset, cull;
 };
 static_assert(std::is_trivially_copyable<FrameState>::value && std::is_trivially_copyable<Cmd>::value, "the replay copies them: views only, no owner");
 inline bool same_sig(const DrawSig &a, const DrawSig &b) { return memcmp(&a, &b, sizeof a) == 0; }
@@ -283,6 +286,7 @@ struct frr_ctx {
     int frames_in_flight = 2;        // option frames_in_flight (1: one target set, everything on the caller's stream)
     DevBuf<Counters> cnt;
     FrameState fs;
+    int cull = FRR_CULL_NONE;       // frr_set_cull: travels with every geometry pass issued from now on (Cmd::cull), like the uniforms
     GeomSet gset[2];
     BinSet bset[2];
     // cross-stream ordering: every workspace set has an event that fires when the latest tile kernel reading it is done (the second
@@ -902,6 +906,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.clipq = S.clipq; g.use_clipq = use_clipq ? 1 : 0;
     g.bcount = S.bcount;
     g.inst = it && nt > 0 ? S.inst_tab.get() : nullptr; g.ntris_mesh = (uint32_t)m.ntris; g.ninst = it ? (uint32_t)it->n : 1u;
+    g.cull = cmd.cull;
     // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it)
     f.geom_filter = GeomFilter{cmd.filter, cmd.fy0, cmd.fy1, f.rank, f.world, f.part_blocked};
     f.gpars[f.lane] = par; cmd.par = par; cmd.lane = f.lane; f.gset = si;
@@ -918,7 +923,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
         h = fnv1a(du.slot_tex, offsetof(DevUniforms, slot_h) + sizeof du.slot_h - offsetof(DevUniforms, slot_tex), h);
         f.geom_duni_hash = h;
     }
-    f.geom_tex_epoch = c->tex_epoch;
+    f.geom_tex_epoch = c->tex_epoch; f.geom_cull = cmd.cull;
     f.geom_inst = it ? it->dev : nullptr; f.geom_inst_gen = it ? it->gen : 0; f.geom_ninst = it ? it->n : 0;
     f.geom_sync_epoch = m.own_dev && (!it || it->own || !it->n) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
     f.tris_in += nt; f.draws += 1;
@@ -1070,7 +1075,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         sig.tex_epoch = f.geom_tex_epoch; sig.sync_epoch = f.geom_sync_epoch;
         sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
         sig.blocked = f.part_blocked ? 1 : 0; sig.filter = f.geom_filter.active ? 1 : 0; sig.fy0 = f.geom_filter.y0; sig.fy1 = f.geom_filter.y1;
-        sig.gset = f.gset; sig.bset = bi;
+        sig.gset = f.gset; sig.bset = bi; sig.cull = f.geom_cull;
         bool known = false;
         for (const DrawSig &p : c->proven) known = known || same_sig(p, sig);
         if (!known) {
@@ -1860,6 +1865,14 @@ int frr_set_user_uniforms(frr_ctx *c, const float *values, int n)
     return FRR_OK;
 }
 
+int frr_set_cull(frr_ctx *c, int mode)
+{
+    if (!c) return FRR_ERR_INVALID;
+    if (mode != FRR_CULL_NONE && mode != FRR_CULL_NEG && mode != FRR_CULL_POS) return fail(c, FRR_ERR_INVALID, "unknown cull mode (FRR_CULL_NONE, FRR_CULL_NEG, FRR_CULL_POS)");
+    c->cull = mode;
+    return FRR_OK;
+}
+
 int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats, int num_varyings, int *shader_id)
 {
     if (!hip_source || !shader_id || vs_input_floats < 1 || vs_input_floats > 64 || num_varyings < 0 || num_varyings > FRR_MAX_VARYINGS)
@@ -1995,7 +2008,7 @@ int frr_geometry(frr_ctx *c, int mesh, uint64_t *ntris_setup)
     if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     HIP_TRY(c, hipSetDevice(c->device));
     Cmd cmd;
-    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni;
+    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni; cmd.cull = c->cull;
     int rc = exec_cmd(c, cmd);
     if (rc != FRR_OK) return rc;
     if (ntris_setup) {
@@ -2047,7 +2060,7 @@ static int instanced_cmd(frr_ctx *c, int mesh, int inst, Cmd *cmd)
     if (ntris && ninst && ntris * ninst >= (1ull << 27))   // (both factors are below 2^27: no wrap)
         return fail(c, FRR_ERR_UNSUPPORTED, "2^27 (instance, triangle) pairs or more in one pass (order keys: 32 per input triangle)");
     HIP_TRY(c, hipSetDevice(c->device));
-    cmd->kind = Cmd::GEOM; cmd->mesh = mesh; cmd->inst = inst; cmd->duni = c->duni;
+    cmd->kind = Cmd::GEOM; cmd->mesh = mesh; cmd->inst = inst; cmd->duni = c->duni; cmd->cull = c->cull;
     h_mat4_mul(c->uni.proj, c->uni.view, cmd->pv);   // as refresh_dev_uniforms builds u.mvp
     return FRR_OK;
 }
@@ -2122,7 +2135,7 @@ int frr_draw(frr_ctx *c, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0
     // frr_draw knows the raster window, so a partitioned ctx can skip the setup records of triangles
     // that touch none of its tile rows (frr_geometry alone cannot: the window comes later)
     Cmd cmd;
-    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni;
+    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni; cmd.cull = c->cull;
     cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
     const int rc = exec_cmd(c, cmd);
     if (rc != FRR_OK) return rc;
@@ -2501,6 +2514,12 @@ void frr_set_perspective(float fovy, float aspect, float zn, float zf, float m[1
 
 // ---- debug hooks ------------------------------------------------------------------------------
 float frr_host_atan2f(float y, float x) { return fd_atan2f(y, x); }
+float frr_host_cull_det(const float clip[12])
+{
+    float pos[3][4];
+    memcpy(pos, clip, sizeof pos);
+    return cull_det(pos);
+}
 
 int frr_debug_mvp(frr_ctx *c, int mesh, int use_mfma, float *clip_out, float *ms_out)
 {

@@ -195,6 +195,7 @@ struct GeomArgs {
     const float *inst;      // [ninst][mvp 16 | model 16]: k_instance_mvp; else null
     uint32_t ntris_mesh;    // the mesh's own triangle count
     uint32_t ninst;
+    int32_t cull;           // frr_set_cull as of the call (wave-uniform): an input the mode drops emits n = 0, like one with a w == 0
 };
 
 // tile-row ownership over a range of tile rows: ty % world == rank (interleaved), or, blocked != 0, the rows [brow0, brow1); world <= 1: all
@@ -458,6 +459,24 @@ __device__ __forceinline__ uint32_t classify(const float pos[3][4], bool &clippe
     // just the three originals, exactly the all-inside case -- one code path there, the fast path here.
     clipped = n != 3u;
     return n - 2;
+}
+
+// Face culling (frr_set_cull): the sign of the homogeneous determinant of the three clip positions the vertex shader
+// returned, in f32 with exactly this association (the library is built with -ffp-contract=off).  The reference sorts every
+// triangle's vertices (renderer.rs:205-218) and swaps them by orientation (:309-312), so facing cannot be read off the
+// setup list: it is decided here, before either.  frr_host_cull_det is the host build.
+FRR_HD float cull_det(const float pos[3][4])
+{
+    const float x0 = pos[0][0], y0 = pos[0][1], w0 = pos[0][3];
+    const float x1 = pos[1][0], y1 = pos[1][1], w1 = pos[1][3];
+    const float x2 = pos[2][0], y2 = pos[2][1], w2 = pos[2][3];
+    return (x0 * (y1 * w2 - y2 * w1) - x1 * (y0 * w2 - y2 * w0)) + x2 * (y0 * w1 - y1 * w0);
+}
+// does the mode drop an input with these clip positions?  (d == 0 and NaN: both comparisons are false, never dropped)
+FRR_HD bool cull_drops(int32_t cull, const float pos[3][4])
+{
+    const float d = cull_det(pos);
+    return cull == FRR_CULL_NEG ? d < 0.0f : d > 0.0f;
 }
 
 // renderer.rs:220-235 for one vertex

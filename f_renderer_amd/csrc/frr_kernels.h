@@ -610,6 +610,9 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
         tri_inputs<NF, IDX, INST>(g, t, in, &im);
         run_vs3<VS, INST>(u, im, in, pos, ctx);
         n = classify(pos, clipped);
+        // frr_set_cull: an input the mode drops emits nothing, like one with a w == 0 -- decided before the block scan, so
+        // the fan slots, the clip queue and the partition test below never see it
+        if (g.cull != FRR_CULL_NONE && cull_drops(g.cull, pos)) { n = 0; clipped = false; }
     }
     if (seq_is_cancelled(first_bad, g.seq, g.epoch, false)) return;   // an earlier command failed: the host replays from there (nothing written yet)
     if (bid == 0 && threadIdx.x == 0) geom_bookkeeping(g);

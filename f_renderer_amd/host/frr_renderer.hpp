@@ -441,6 +441,9 @@ public:
     {
         check(frr_draw_instanced(ctx_, m.id, t.id, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
     }
+    // Face culling of the geometry passes issued from now on (frr_set_cull): FRR_CULL_NONE, FRR_CULL_NEG (drop the inputs whose
+    // clip-space determinant is < 0) or FRR_CULL_POS (> 0).  The reference has no such switch: the default draws everything.
+    void set_cull(int mode) { check(frr_set_cull(ctx_, mode)); }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream
     // waits for every frame issued so far; frame_wait -- the next write of the frame targets waits for what the stream holds now

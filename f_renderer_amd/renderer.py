@@ -18,8 +18,8 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from ._native import (FrrError, PS_BLINN, PS_COLOR, PS_DEPTH, PS_FLAT, PS_PHONG, VS_CLIP, VS_CLIP_COLOR,  # noqa: F401
-                      VS_GOURAUD, VS_PHONG)
+from ._native import (CULL_NEG, CULL_NONE, CULL_POS, FrrError, PS_BLINN, PS_COLOR, PS_DEPTH, PS_FLAT, PS_PHONG,  # noqa: F401
+                      VS_CLIP, VS_CLIP_COLOR, VS_GOURAUD, VS_PHONG)
 
 SETUP_DTYPE = np.dtype([("spf", "<f4", (2,)), ("spi", "<i4", (2,)), ("rhw", "<f4"), ("ctx", "<f4", (N.MAX_VARYINGS,))])
 assert SETUP_DTYPE.itemsize == C.sizeof(N.SetupVertex)
@@ -187,6 +187,13 @@ def host_instance_mvp(proj, view, model):
     out = np.zeros(16, np.float32)
     N.lib().frr_host_instance_mvp(_fp(p), _fp(v), _fp(m), _fp(out))
     return out
+
+
+def host_cull_det(clip):
+    """The facing determinant of three clip positions (float32 [3][4]: x, y, z, w) as the geometry kernels compute it
+    (frr_host_cull_det): CULL_NEG drops an input whose value is < 0, CULL_POS one whose value is > 0."""
+    p = np.ascontiguousarray(clip, np.float32).reshape(12)
+    return np.float32(N.lib().frr_host_cull_det(_fp(p)))
 
 
 def _options_from_env():
@@ -377,6 +384,11 @@ class Renderer:
         """u.user[...] of the user shaders: what the reference's closures would have captured."""
         v = np.ascontiguousarray(values, np.float32).reshape(-1)
         self._check(self._lib.frr_set_user_uniforms(self._ctx, _fp(v), v.size))
+
+    def set_cull(self, mode):
+        """Face culling of the geometry passes issued from now on (frr_set_cull): CULL_NONE, CULL_NEG (drop inputs whose
+        clip-space determinant is < 0) or CULL_POS (> 0).  A culled pass is the plain pass over the inputs it keeps."""
+        self._check(self._lib.frr_set_cull(self._ctx, int(mode)))
 
     def set_partition(self, rank, world, blocked=False):
         """Tile-row ownership of a multi-GPU rank: interleaved rows (ty % world == rank) or, blocked=True,

@@ -67,6 +67,13 @@ typedef enum frr_ps {
     FRR_PS_BLINN = 4  /* half-vector variant of the same (not in the reference) */
 } frr_ps;
 
+/* Face-cull mode of the geometry passes (frr_set_cull), named by the sign of the determinant it drops. */
+typedef enum frr_cull {
+    FRR_CULL_NONE = 0, /* every input is processed (the reference's behaviour, and the default) */
+    FRR_CULL_NEG = 1,  /* drop inputs with d < 0 */
+    FRR_CULL_POS = 2   /* drop inputs with d > 0 */
+} frr_cull;
+
 /* ---- user shaders -------------------------------------------------------------------------------------------
  * The reference's shaders are closures: `vertex_shader: &F` with F: Fn(&VSUniform, &VSInput, &mut ShaderContext) -> Vec4
  * (renderer.rs:105,110,116) and `pixel_shader: &F` with F: Fn(&PSUniform, &ShaderContext) -> Vec4 (:273,283,380), over any
@@ -319,6 +326,44 @@ int frr_instances_free(frr_ctx *ctx, int inst);
 int frr_geometry_instanced(frr_ctx *ctx, int mesh, int inst, uint64_t *ntris_setup);
 int frr_draw_instanced(frr_ctx *ctx, int mesh, int inst, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
 
+/* ---- face culling ------------------------------------------------------------------------- */
+
+/* The reference draws every input triangle, whichever way it faces; frr_set_cull lets a geometry pass drop those that face
+ * one way.  The reference destroys winding -- renderer.rs:205-218 sorts every triangle's vertices by angle around the
+ * centroid, :309-312 swaps by orientation -- so facing cannot be read off the setup list: it is decided before the sort,
+ * from the three clip positions (x, y, z, w) the vertex shader returned for the input, by the sign of the homogeneous
+ * determinant
+ *     d = (x0*(y1*w2 - y2*w1) - x1*(y0*w2 - y2*w0)) + x2*(y0*w1 - y1*w0)
+ * in f32 with exactly this association and no contraction (frr_host_cull_det below is the host build of the device's
+ * code).  With all w > 0, d > 0 means vertices 0, 1, 2 run counter-clockwise in NDC (x right, y up), i.e. clockwise on
+ * the displayed image, whose y runs down; for a triangle that crosses w = 0 the sign is still a defined rule, which is
+ * why the determinant is used and not a screen-space area.  The rule is the f32 formula BY DEFINITION, not the exact sign:
+ * for near-degenerate triangles the two differ often.  FRR_CULL_NEG drops inputs with d < 0, FRR_CULL_POS those with
+ * d > 0; d == 0 and a NaN d are never dropped (both comparisons are false, and the reference would compute with such
+ * triangles).  The modes are named by sign, not front / back, because meshes differ in winding.
+ * A geometry pass under a cull mode is BY DEFINITION the plain pass over the sub-mesh of the inputs the mode keeps, in
+ * their original order.  Hence:
+ * - The setup list, emission order, triangle ids, depth bits, RGBA8, tris_setup, frag_covered and frag_nan are, bit for
+ *   bit, those of drawing that sub-mesh with FRR_CULL_NONE.  Ids stay dense over the survivors, and the frame's running
+ *   count continues behind them.
+ * - tris_in still grows by the number of inputs submitted, culled ones included; draws is as before.
+ * - The pos.w == 0.0 rule (geometry_processing returns None, renderer.rs:117-119) comes first and is unchanged; a culled
+ *   input is one more input that emits nothing.  One that would have been clipped gets no fan slots.
+ * - The determinant is taken on what the vertex shader returned: built-in or user vertex shaders, plain or indexed meshes
+ *   alike; in an instanced pass it is evaluated per (instance, triangle) under that instance's matrices (a mirrored
+ *   instance faces the other way).
+ * - Everything that consumes a setup list takes the culled one as it is: frr_raster with any window, frr_readback_setup,
+ *   frr_draw_wireframe (no edges for culled inputs), frr_resolve_varyings, ranged frr_shade_varyings, the partition
+ *   filter of frr_draw.
+ * - The culled frame is NOT in general the unculled frame, not even for a closed mesh: at a silhouette a back face can own
+ *   a pixel no front face covers (at 240 x 135: 34 depth entries / 12 colour pixels of the project's torus scene, 2 / 2 of
+ *   its sphere scene).
+ * frr_set_cull applies to the geometry passes issued from now on (frr_geometry, frr_draw and the _instanced pair); the
+ * mode travels with each pass like frr_uniforms, so a replayed pass runs under the mode of its call, and frr_clear does
+ * not reset it.  frr_raster after frr_geometry rasterizes the list as it was built, whatever the mode is by then.
+ * An unknown mode is FRR_ERR_INVALID and changes nothing. */
+int frr_set_cull(frr_ctx *ctx, int mode);
+
 /* ---- lines ------------------------------------------------------------------------------- */
 
 /* FrameBuffer::draw_line(x1, y1, x2, y2, color) (renderer.rs:540-588), the reference's only drawing primitive besides the
@@ -547,6 +592,9 @@ int64_t frr_host_line_pixels(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2,
 /* host build of the device's per-instance matrix product (cf. frr_host_atan2f, frr_host_line_pixels):
  * out = (proj * view) * model, column-major, every element ((a0*b0 + a1*b1) + a2*b2) + a3*b3 */
 void frr_host_instance_mvp(const float proj[16], const float view[16], const float model[16], float out[16]);
+/* host build of the device's facing determinant (frr_set_cull; cf. frr_host_atan2f): d of the three clip positions
+ * clip[0..3], clip[4..7], clip[8..11] (x, y, z, w each) */
+float frr_host_cull_det(const float clip[12]);
 /* MVP x vertex contraction of a pos3/uv2/normal3 mesh with the current uniforms: clip xyzw per vertex
  * (ntris*3*4 floats) by the exact VALU form (use_mfma = 0, glam's association) or by
  * v_mfma_f32_16x16x4_f32 (use_mfma = 1, an fmaf chain: NOT bit-identical); *ms = kernel time. */

@@ -92,6 +92,9 @@ pub mod ffi {
         pub fn frr_geometry_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ntris_setup: *mut u64) -> c_int;
         pub fn frr_draw_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
         pub fn frr_host_instance_mvp(proj: *const f32, view: *const f32, model: *const f32, out: *mut f32);
+        // face culling of the geometry passes issued from now on (0 none, 1 drop d < 0, 2 drop d > 0): set beside the uniforms
+        pub fn frr_set_cull(ctx: *mut frr_ctx, mode: c_int) -> c_int;
+        pub fn frr_host_cull_det(clip: *const f32) -> f32;
         pub fn frr_sync(ctx: *mut frr_ctx) -> c_int;
         pub fn frr_readback(ctx: *mut frr_ctx, rgba: *mut u8, depth: *mut f32, tri_id: *mut u32) -> c_int;
         pub fn frr_get_stats(ctx: *mut frr_ctx, out: *mut frr_stats) -> c_int;
@@ -137,6 +140,15 @@ pub enum Ps {
     /// phong.rs:133-154
     Phong = 3,
     Blinn = 4,
+}
+/// face culling of the geometry passes (frr_set_cull), named by the sign of the clip-space determinant it drops; the reference
+/// has no such switch (it draws every triangle): `None` is its behaviour and the default
+#[repr(i32)]
+#[derive(Clone, Copy, Debug)]
+pub enum Cull {
+    None = 0,
+    Neg = 1,
+    Pos = 2,
 }
 
 /// `VSInput` of phong.rs:49-54 -- the FRR_VS_PHONG / FRR_VS_GOURAUD vertex layout (8 packed floats)
@@ -201,6 +213,10 @@ impl Renderer {
     }
     pub fn set_uniforms(&mut self, u: &Uniforms) -> Result<(), Error> {
         self.check(unsafe { ffi::frr_set_uniforms(self.ctx, u) })
+    }
+    /// set beside the uniforms: the mode travels with every geometry pass issued from now on; `clear` does not reset it
+    pub fn set_cull(&mut self, mode: Cull) -> Result<(), Error> {
+        self.check(unsafe { ffi::frr_set_cull(self.ctx, mode as c_int) })
     }
     /// `frame_buffer.fill(color); depth_buffer.fill(depth)` (phong.rs:316-317)
     pub fn clear(&mut self, color: [u8; 4], depth: f32) -> Result<(), Error> {
