@@ -15,6 +15,8 @@
 //       (shade_varyings_host) -- the same bytes as the forward run
 //   --instances N anywhere among them draws the mesh N times, on a grid of translations (scaled down to fit), with ONE call:
 //       the loop over objects of phong.rs:319-331 as one instanced pass (draw_instanced)
+//   --list anywhere among them draws the objects -- the N copies of --instances, else the one mesh -- as (mesh, model matrix) items
+//       of ONE list pass (draw_list): the setup loop of phong.rs:319-359, where every object may name a mesh of its own
 //   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
 //       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
@@ -37,10 +39,10 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false;
+    bool wireframe = false, deferred = false, list = false;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred") {
-            (std::string(argv[i]) == "--wireframe" ? wireframe : deferred) = true;
+        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list") {
+            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -78,7 +80,7 @@ int main(int argc, char **argv)
         std::cerr << "usage: phong_headless mesh.f32 ntris tex.rgba tex_size W H out.rgba [out.ppm]\n"
                      "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
                      "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade;\n"
-                     "        --instances N: N copies on a grid in one instanced pass;\n"
+                     "        --instances N: N copies on a grid in one instanced pass; --list: the objects as one list pass;\n"
                      "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign)\n";
         return 2;
     }
@@ -123,11 +125,12 @@ int main(int argc, char **argv)
 
         renderer.clear({30, 30, 30, 255}, 0.0f);                                                // phong.rs:316-317
         if (cull != FRR_CULL_NONE) renderer.set_cull(cull);
+        std::vector<frr::Mat4> models;
         if (instances >= 0) {
             // N objects that share the mesh: model_i = translate(grid cell i) * scale(1 / columns), column-major
             const long cols = std::max(1L, (long)std::ceil(std::sqrt((double)std::max(instances, 1L))));
             const float s = 1.0f / (float)cols;
-            std::vector<frr::Mat4> models((size_t)instances, frr::set_identity());
+            models.assign((size_t)instances, frr::set_identity());
             for (long i = 0; i < instances; ++i) {
                 frr::Mat4 &m = models[(size_t)i];
                 m[0] = m[5] = m[10] = s;
@@ -135,6 +138,14 @@ int main(int argc, char **argv)
                 m[13] = (((float)(i / cols) + 0.5f) * s - 0.5f) * 2.0f;
                 m[14] = -0.25f * (float)(i % 3);
             }
+        } else if (list) models.assign(1, model);
+        if (list) {
+            const frr::DrawList items = renderer.upload_draw_list(std::vector<frr::Mesh>(models.size(), mesh), models);
+            renderer.geometry_list(items);                                                      // loop A for every item, one pass
+            std::vector<uint32_t> first, count;
+            renderer.item_ranges(first, count);                                                 // body_offset, face_offset, ... (phong.rs:333-359)
+            std::printf("list: n=%zu tris_in=%llu last_first=%u\n", models.size(), (unsigned long long)renderer.stats().tris_in, first.empty() ? 0u : first.back());
+        } else if (instances >= 0) {
             const frr::Instances table = renderer.upload_instances(models);
             renderer.geometry_processing_instanced(mesh, table);                                // loop A for every object, one pass
             std::printf("instances: n=%ld tris_in=%llu\n", instances, (unsigned long long)renderer.stats().tris_in);

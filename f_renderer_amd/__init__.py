@@ -5,5 +5,5 @@ from . import scenes  # noqa: F401
 from ._native import (FRR_ERR_CAPACITY, FRR_ERR_HIP, FRR_ERR_INVALID, FRR_ERR_NOMEM, FRR_ERR_UNSUPPORTED,  # noqa: F401
                       FRR_OK, FrrError, build, lib)
 from .renderer import (CULL_NEG, CULL_NONE, CULL_POS, PS_BLINN, PS_COLOR, PS_DEPTH, PS_FLAT, PS_PHONG, VS_CLIP,  # noqa: F401
-                       VS_CLIP_COLOR, VS_GOURAUD, VS_PHONG, Camera, FrameBuffer, Instances, Lines, Mesh, Renderer, host_cull_det,
-                       host_instance_mvp, set_identity, set_look_at, set_perspective)
+                       VS_CLIP_COLOR, VS_GOURAUD, VS_PHONG, Camera, DrawList, FrameBuffer, Instances, Lines, Mesh, Renderer, host_cull_det,
+                       host_instance_mvp, host_list_item, set_identity, set_look_at, set_perspective)

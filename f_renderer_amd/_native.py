@@ -53,6 +53,10 @@ class SetupVertex(C.Structure):
     _fields_ = [("spf", C.c_float * 2), ("spi", C.c_int32 * 2), ("rhw", C.c_float), ("ctx", C.c_float * MAX_VARYINGS)]
 
 
+class DrawItem(C.Structure):
+    _fields_ = [("mesh", C.c_int32), ("reserved", C.c_int32), ("model", C.c_float * 16)]
+
+
 class Xfer(C.Structure):
     _fields_ = [("kind", C.c_int32), ("peer", C.c_int32), ("offset", C.c_uint64), ("count", C.c_uint64)]
 
@@ -128,6 +132,12 @@ SIGNATURES = {
     "frr_geometry_instanced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_uint64)]),
     "frr_draw_instanced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frr_host_instance_mvp": (None, [_P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "frr_drawlist_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_drawlist_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_geometry_list": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_uint64)]),
+    "frr_draw_list": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frr_geometry_item_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "frr_host_list_item": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
     "frr_lines_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_lines_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_lines_free": (C.c_int, [C.c_void_p, C.c_int]),

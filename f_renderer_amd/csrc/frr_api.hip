@@ -75,7 +75,21 @@ struct Instances {
     bool used = false;
     uint64_t gen = 0;              // which registration of the ctx this is (DrawSig, like Mesh::gen)
 };
-// slot tables (frr_ctx::meshes, lines, instances): a record goes into the first unused slot, or behind the last; its index is its id
+// a draw list (frr_drawlist_upload): a snapshot of its items -- per item the mesh's pointers, counts and generation, and the
+// model matrix -- so a pass over it reads nothing of frr_ctx::meshes.  Freeing a mesh it names kills it for good (dead).
+struct DrawList {
+    DevBuf<ListRow> rows;          // [n] GeomArgs::items
+    DevBuf<uint32_t> first;        // [2 n] first[n] | ntris[n]: GeomArgs::item_first / item_ntris
+    DevBuf<float> models;          // [n][16] the k_instance_mvp input
+    std::vector<int> mesh; std::vector<uint64_t> mesh_gen;   // [n] who the rows were taken from (frr_mesh_free)
+    uint64_t n = 0, total = 0;     // items, and the sum of their triangle counts (< 2^27)
+    int vs = FRR_VS_CLIP;          // the one vertex shader of all items (no items: any pixel shader goes with nothing)
+    bool any_dev = false;          // some item's mesh is device-bound (DrawSig: sync_epoch)
+    bool dead = false;
+    bool used = false;
+    uint64_t gen = 0;              // which upload of the ctx this is (DrawSig, Cmd: an id is reused)
+};
+// slot tables (frr_ctx::meshes, lines, instances, lists): a record goes into the first unused slot, or behind the last; its index is its id
 template <typename R> int slot_put(std::vector<R> &v, R &&r)
 {
     size_t i = 0;
@@ -92,6 +106,7 @@ struct UserShader {
     int nf = 0, K = 0;
     std::vector<char> code;
     std::string geom_inst[2], clip_inst[2];   // ... of an instanced pass ([indexed mesh])
+    std::string geom_list, clip_list;         // ... of a list pass
     std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6], shade[2];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel; shade: k_shade_vary [16-byte loads])
 };
 std::mutex g_shader_mu;
@@ -127,7 +142,7 @@ void release_stream(int device, hipStream_t st)
 
 struct UserModule {
     hipModule_t mod = nullptr;
-    hipFunction_t geom_inst[2] = {}, clip_inst[2] = {};
+    hipFunction_t geom_inst[2] = {}, clip_inst[2] = {}, geom_list = nullptr, clip_list = nullptr;
     hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {}, shade[2] = {};
 };
 
@@ -213,6 +228,9 @@ struct FrameState {
     const float *geom_inst = nullptr; uint64_t geom_inst_gen = 0, geom_ninst = 0;   // ... and, an instanced pass, its table: DrawSig
     uint64_t geom_tex_epoch = 0, geom_sync_epoch = 0;  // ... the texture uploads and (device-bound mesh) the frr_sync calls before it: DrawSig
     int geom_cull = FRR_CULL_NONE;                     // ... and the cull mode it ran under: DrawSig
+    int geom_list = -1; uint64_t geom_list_gen = 0;    // ... and, a list pass, its list: DrawSig
+    // its items (frr_geometry_item_ranges): the items of a list pass, the instances of an instanced pass (geom_stride inputs each), else one
+    uint64_t geom_nitems = 1, geom_stride = 0;
     uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
 };
 
@@ -224,6 +242,7 @@ struct Cmd {
     // GEOM
     int mesh = -1; bool filter = false; int32_t fy0 = 0, fy1 = 0;
     int cull = FRR_CULL_NONE;           // frr_set_cull at the time of the call (a replay runs the pass under it again)
+    int list = -1; uint64_t list_gen = 0;   // a list pass: its list, and which upload that id meant (mesh is unused then; pv as below)
     int inst = -1; float pv[16] = {};   // an instanced pass: its table, and proj * view at the time of the call (the table's mvp = pv * model)
     // RASTER
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
@@ -248,8 +267,9 @@ struct Cmd {
 // binding it again after a rewrite is a new registration.)
 struct DrawSig {
     const float *inst; uint64_t inst_gen, ninst;   // an instanced pass: its table (bound again, or device-bound and behind a frr_sync: unproven again, like a mesh)
+    uint64_t list_gen;   // a list pass: which upload its id meant -- a pass proven for one list says nothing about a later list with that id
     const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
-    int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset, cull;
+    int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset, cull, list;
 };
 static_assert(std::is_trivially_copyable<FrameState>::value && std::is_trivially_copyable<Cmd>::value, "the replay copies them: views only, no owner");
 inline bool same_sig(const DrawSig &a, const DrawSig &b) { return memcmp(&a, &b, sizeof a) == 0; }
@@ -347,6 +367,9 @@ struct frr_ctx {
     std::vector<Lines> lines;
     std::vector<Instances> instances;
     uint64_t inst_gen = 0;          // instance tables registered so far (Instances::gen)
+    std::vector<DrawList> lists;
+    uint64_t list_gen = 0;          // draw lists uploaded so far (DrawList::gen)
+    DevBuf<uint32_t> item_tmp;      // frr_geometry_item_ranges: the device side of its answer
     // draw_line order is resolved per pixel on a u32 plane of W * H (frr_lines.h), all-zero between commands: one per stream
     // that can carry target writes -- [0] `stream`, [1] / [2] the frame streams tstream[0] / tstream[1] -- because the line
     // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
@@ -651,6 +674,8 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
         HIP_TRY(c, hipModuleGetFunction(&m.geom_inst[idx], m.mod, us->geom_inst[idx].c_str()));
         HIP_TRY(c, hipModuleGetFunction(&m.clip_inst[idx], m.mod, us->clip_inst[idx].c_str()));
     }
+    HIP_TRY(c, hipModuleGetFunction(&m.geom_list, m.mod, us->geom_list.c_str()));
+    HIP_TRY(c, hipModuleGetFunction(&m.clip_list, m.mod, us->clip_list.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.sweep, m.mod, us->sweep.c_str()));
     HIP_TRY(c, hipModuleGetFunction(&m.entries, m.mod, us->entries.c_str()));
     for (int cnt = 0; cnt < 2; ++cnt)
@@ -664,24 +689,25 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
 constexpr uint32_t kClipGrid = 2048;      // workgroups of k_geom_clip (four wavefronts each, one triangle per wavefront and step)
 
 // (IDX, an indexed mesh, is a template flag and not a null test in the kernels: the instantiations for expanded meshes keep
-// their code; so is INST, an instanced pass)
-template <int VS, bool IDX, bool INST> void launch_geometry_as(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
+// their code; so is INST, an instanced pass, and LIST, a list pass, which takes INST's matrices and branches on the item for IDX)
+template <int VS, bool IDX, bool INST, bool LIST = false> void launch_geometry_as(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
 {
     hipStream_t st = gstream_of(c);
-    hipLaunchKernelGGL((k_geom_single<VS, IDX, INST>), dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
-    if (g.use_clipq) hipLaunchKernelGGL((k_geom_clip<VS, IDX, INST>), dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
+    hipLaunchKernelGGL((k_geom_single<VS, IDX, INST, LIST>), dim3(nblocks), dim3(GEOM_BLOCK), 0, st, g, du);
+    if (g.use_clipq) hipLaunchKernelGGL((k_geom_clip<VS, IDX, INST, LIST>), dim3(std::min<uint32_t>(kClipGrid, nblocks * 4u)), dim3(GEOM_BLOCK), 0, st, g, du);
 }
 
 template <int VS> void launch_geometry(frr_ctx *c, GeomArgs &g, uint32_t nblocks, const DevUniforms &du)
 {
-    if (g.inst) {
+    if (g.items) launch_geometry_as<VS, false, true, true>(c, g, nblocks, du);
+    else if (g.inst) {
         if (g.idx) launch_geometry_as<VS, true, true>(c, g, nblocks, du);
         else launch_geometry_as<VS, false, true>(c, g, nblocks, du);
     } else if (g.idx) launch_geometry_as<VS, true, false>(c, g, nblocks, du);
     else launch_geometry_as<VS, false, false>(c, g, nblocks, du);
 }
 
-// the geometry kernel for the VS of the mesh; models: the table of an instanced pass, whose matrices (GeomArgs::inst = pv * model
+// the geometry kernel for the VS of the mesh; models: the table of an instanced pass (or the matrices of a list's items), whose matrices (GeomArgs::inst = pv * model
 // and model, per instance) are filled first -- on the pass's stream and inside the command, so a replay fills them again
 void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const DevUniforms &du, const UserModule *um, const float *models, const float *pv)
 {
@@ -695,8 +721,8 @@ void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const
     if (um) {   // a user shader: the same kernels, compiled with the user's functions (frr_shader_register)
         DevUniforms d = du;
         void *args[] = {&g, &d};
-        const hipFunction_t geom = g.inst ? um->geom_inst[g.idx ? 1 : 0] : g.idx ? um->geom_idx : um->geom;
-        const hipFunction_t clip = g.inst ? um->clip_inst[g.idx ? 1 : 0] : g.idx ? um->clip_idx : um->clip;
+        const hipFunction_t geom = g.items ? um->geom_list : g.inst ? um->geom_inst[g.idx ? 1 : 0] : g.idx ? um->geom_idx : um->geom;
+        const hipFunction_t clip = g.items ? um->clip_list : g.inst ? um->clip_inst[g.idx ? 1 : 0] : g.idx ? um->clip_idx : um->clip;
         (void)hipModuleLaunchKernel(geom, nblocks, 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
         if (g.use_clipq) (void)hipModuleLaunchKernel(clip, std::min<uint32_t>(kClipGrid, nblocks * 4u), 1, 1, GEOM_BLOCK, 1, 1, 0, st, args, nullptr);
         return;
@@ -832,10 +858,16 @@ int settle(frr_ctx *c)
 int exec_geometry(frr_ctx *c, Cmd &cmd)
 {
     FrameState &f = c->fs;
-    const Mesh &m = c->meshes[cmd.mesh];
+    // A list pass (cmd.list >= 0) is that loop over objects with a mesh of its own per object: its inputs are the items'
+    // triangles one after the other, and it reads the list's snapshot, never frr_ctx::meshes.
+    const DrawList *const dl = cmd.list >= 0 ? &c->lists[cmd.list] : nullptr;
+    static const Mesh no_mesh;
+    const Mesh &m = dl ? no_mesh : c->meshes[cmd.mesh];
     const Instances *const it = cmd.inst >= 0 ? &c->instances[cmd.inst] : nullptr;
-    const int K = frr_vs_num_varyings(m.vs);
-    const uint64_t nt = it ? m.ntris * it->n : m.ntris;   // (below 2^27: frr_geometry_instanced)
+    const int vs = dl ? dl->vs : m.vs;
+    const int K = frr_vs_num_varyings(vs);
+    const uint64_t nt = dl ? dl->total : it ? m.ntris * it->n : m.ntris;   // (below 2^27: frr_geometry_instanced, frr_drawlist_upload)
+    const uint64_t nmat = dl ? dl->n : it ? it->n : 0;   // rows of the pass's matrix table
     const int par = f.gpar() ^ 1;
     // Beside the previous pass's tile kernel (second stream, the other workspace set) or after it (the targets' stream,
     // set 0: one set stays hot in the 256 MB Infinity Cache -- two sets of the 1M-triangle frame do not, which costs its
@@ -847,7 +879,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     GeomSet &S = c->gset[si];
     int rc;
     const UserModule *um = nullptr;
-    if (m.vs >= FRR_SHADER_USER_BASE && (rc = user_module(c, m.vs, &um)) != FRR_OK) return rc;
+    if (vs >= FRR_SHADER_USER_BASE && (rc = user_module(c, vs, &um)) != FRR_OK) return rc;
     // fan space: clipped inputs are the ones that straddle a frustum plane, usually few; room for as many fan triangles
     // as there are inputs (+ 4096) to start with, grown on demand (the pass then fails on the device and finish() replays
     // it with more) up to the worst case of 19 per input (small meshes get their worst case outright: 2^20 slots are cheap) ...
@@ -873,7 +905,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if (K > 0 && (rc = ensure(c, S.vary, S.recs.cap() * 3 * std::max(K, 8) /* (K <= 8 in the shader table) */)) != FRR_OK) return rc;
     const bool use_clipq = nt > 0 && (c->clip_queue > 0 || (c->clip_queue < 0 && c->clip_queue_auto));
     if (use_clipq && (rc = ensure(c, S.clipq, (size_t)nt)) != FRR_OK) return rc;
-    if (it && nt > 0 && (rc = ensure(c, S.inst_tab, (size_t)it->n * 32)) != FRR_OK) return rc;
+    if (nmat && nt > 0 && (rc = ensure(c, S.inst_tab, (size_t)nmat * 32)) != FRR_OK) return rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // the previous pass's n_emit feeds this pass's tri_base
     if (on_g && !c->gstream) {
         // created on first use: a process maps its HIP streams onto a handful of hardware queues, and two streams that
@@ -905,7 +937,8 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.recs = S.recs; g.vary = S.vary; g.pbox = S.pbox; g.cnt = c->cnt;
     g.clipq = S.clipq; g.use_clipq = use_clipq ? 1 : 0;
     g.bcount = S.bcount;
-    g.inst = it && nt > 0 ? S.inst_tab.get() : nullptr; g.ntris_mesh = (uint32_t)m.ntris; g.ninst = it ? (uint32_t)it->n : 1u;
+    g.inst = nmat && nt > 0 ? S.inst_tab.get() : nullptr; g.ntris_mesh = (uint32_t)m.ntris; g.ninst = dl || it ? (uint32_t)nmat : 1u;
+    g.items = dl && nt > 0 ? dl->rows.get() : nullptr; g.item_first = dl ? dl->first.get() : nullptr; g.item_ntris = dl ? dl->first.get() + dl->n : nullptr;
     g.cull = cmd.cull;
     // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it)
     f.geom_filter = GeomFilter{cmd.filter, cmd.fy0, cmd.fy1, f.rank, f.world, f.part_blocked};
@@ -913,8 +946,10 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     f.geom_fan_cap = (uint32_t)fan_cap;
     f.geom_nblocks = nblocks;
     f.geom_seq = cmd.seq;
-    f.geom_vs = m.vs; f.geom_ntris = nt;
+    f.geom_vs = vs; f.geom_ntris = nt;
     f.geom_mesh = m.dev; f.geom_mesh_gen = m.gen;
+    f.geom_list = cmd.list; f.geom_list_gen = dl ? dl->gen : 0;
+    f.geom_nitems = dl || it ? nmat : 1; f.geom_stride = m.ntris;
     {   // (field ranges without padding: the struct has some in front of its texture pointer)
         const DevUniforms &du = cmd.duni;
         uint64_t h = fnv1a(&du, offsetof(DevUniforms, flat_color) + sizeof du.flat_color);
@@ -925,12 +960,12 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     }
     f.geom_tex_epoch = c->tex_epoch; f.geom_cull = cmd.cull;
     f.geom_inst = it ? it->dev : nullptr; f.geom_inst_gen = it ? it->gen : 0; f.geom_ninst = it ? it->n : 0;
-    f.geom_sync_epoch = m.own_dev && (!it || it->own || !it->n) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
+    f.geom_sync_epoch = (dl ? !dl->any_dev : m.own_dev && (!it || it->own || !it->n)) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
     f.tris_in += nt; f.draws += 1;
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
     } else {
-        launch_geometry_vs(c, g, nblocks, m.vs, cmd.duni, um, it ? it->dev : nullptr, cmd.pv);
+        launch_geometry_vs(c, g, nblocks, vs, cmd.duni, um, dl ? dl->models.get() : it ? it->dev : nullptr, cmd.pv);
         f.scan_pending = true;
     }
     HIP_TRY(c, hipGetLastError());
@@ -1071,6 +1106,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         DrawSig sig;
         memset(&sig, 0, sizeof sig);
         sig.inst = f.geom_inst; sig.inst_gen = f.geom_inst_gen; sig.ninst = f.geom_ninst;
+        sig.list = f.geom_list; sig.list_gen = f.geom_list_gen;
         sig.mesh = f.geom_mesh; sig.mesh_gen = f.geom_mesh_gen; sig.ntris = f.geom_ntris; sig.duni_hash = f.geom_duni_hash; sig.join_epoch = c->join_epoch;
         sig.tex_epoch = f.geom_tex_epoch; sig.sync_epoch = f.geom_sync_epoch;
         sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
@@ -1739,6 +1775,9 @@ int frr_mesh_free(frr_ctx *c, int mesh)
 {
     if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a draw of it
+    for (DrawList &l : c->lists)   // a list that names it holds its pointers: dead from now on, whoever gets the id next
+        for (size_t i = 0; l.used && !l.dead && i < l.mesh.size(); ++i)
+            if (l.mesh[i] == mesh && l.mesh_gen[i] == c->meshes[mesh].gen) l.dead = true;
     c->meshes[mesh] = Mesh();   // (frees the library's copies)
     return FRR_OK;
 }
@@ -1904,6 +1943,9 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
         (void)hiprtcAddNameExpression(prog, geom_inst_expr[idx].c_str());
         (void)hiprtcAddNameExpression(prog, clip_inst_expr[idx].c_str());
     }
+    const std::string geom_list_expr = "frr::k_geom_single<" + U + ", false, true, true>", clip_list_expr = "frr::k_geom_clip<" + U + ", false, true, true>";   // list passes
+    (void)hiprtcAddNameExpression(prog, geom_list_expr.c_str());
+    (void)hiprtcAddNameExpression(prog, clip_list_expr.c_str());
     const std::string sweep_expr = "frr::k_raster<" + Ks + ", " + U + ">";   // the brute-force tile kernel (option raster_sweep)
     (void)hiprtcAddNameExpression(prog, sweep_expr.c_str());
     const std::string entries_expr = "frr::k_raster_entries<" + Ks + ", " + U + ">";   // windows whose rows share depth entries (x0 < 0)
@@ -1931,6 +1973,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     auto lowered = [&](const std::string &e) { const char *n = nullptr; ok = ok && hiprtcGetLoweredName(prog, e.c_str(), &n) == HIPRTC_SUCCESS && n; return std::string(n ? n : ""); };
     us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->geom_idx = lowered(geom_idx_expr); us->clip_idx = lowered(clip_idx_expr); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
     for (int idx = 0; idx < 2; ++idx) { us->geom_inst[idx] = lowered(geom_inst_expr[idx]); us->clip_inst[idx] = lowered(clip_inst_expr[idx]); }
+    us->geom_list = lowered(geom_list_expr); us->clip_list = lowered(clip_list_expr);
     for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) us->shade[vec] = lowered(shade_expr[vec]);
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
@@ -2082,6 +2125,115 @@ void frr_host_instance_mvp(const float proj[16], const float view[16], const flo
     h_mat4_mul(pv, model, out);
 }
 
+// ---- draw lists: many meshes under their own matrices in one pass (the whole setup loop of phong.rs:319-359) ---------
+int frr_drawlist_upload(frr_ctx *c, const frr_draw_item *items, uint64_t nitems, int *list_out)
+{
+    if (!c || !list_out || (nitems && !items)) return fail(c, FRR_ERR_INVALID, "bad draw list");
+    if (nitems >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 items or more in one draw list");
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < nitems; ++i) {
+        const std::string who = "draw list: item " + std::to_string(i);
+        if (items[i].reserved != 0) return fail(c, FRR_ERR_INVALID, who + ": reserved must be 0");
+        if (!slot_ok(c->meshes, items[i].mesh)) return fail(c, FRR_ERR_INVALID, who + ": bad mesh id");
+        if (c->meshes[items[i].mesh].vs != c->meshes[items[0].mesh].vs)
+            return fail(c, FRR_ERR_INVALID, who + ": its mesh's vertex shader is not item 0's (one vertex shader per list)");
+        total += c->meshes[items[i].mesh].ntris;   // (each below 2^27, fewer than 2^27 of them: no wrap)
+    }
+    if (total >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 triangles or more in one draw list (order keys: 32 per input triangle of a pass)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DrawList l;
+    std::vector<ListRow> rows(nitems);
+    std::vector<uint32_t> first(2 * nitems);
+    std::vector<float> models(16 * nitems);
+    l.mesh.resize(nitems); l.mesh_gen.resize(nitems);
+    uint32_t at = 0;
+    for (uint64_t i = 0; i < nitems; ++i) {
+        const Mesh &m = c->meshes[items[i].mesh];
+        rows[i] = ListRow{m.dev, m.idx, (uint32_t)m.nverts, (uint32_t)m.ntris, at, 0u};
+        first[i] = at; first[nitems + i] = (uint32_t)m.ntris;
+        at += (uint32_t)m.ntris;
+        memcpy(&models[16 * i], items[i].model, sizeof items[i].model);
+        l.mesh[i] = items[i].mesh; l.mesh_gen[i] = m.gen;
+        l.any_dev = l.any_dev || !m.own_dev;
+    }
+    if (nitems) {
+        l.vs = c->meshes[items[0].mesh].vs;
+        int rc = upload(c, l.rows, rows.data(), rows.size() * sizeof(ListRow), "draw list", false);
+        if (rc == FRR_OK) rc = upload(c, l.first, first.data(), first.size() * sizeof(uint32_t), "draw list", false);
+        // (the last one waits for all three; should one fail, the frees in l's destructor wait for the device)
+        if (rc == FRR_OK) rc = upload(c, l.models, models.data(), models.size() * sizeof(float), "draw list");
+        if (rc != FRR_OK) return rc;
+    }
+    l.n = nitems; l.total = total; l.used = true; l.gen = ++c->list_gen;
+    *list_out = slot_put(c->lists, std::move(l));
+    return FRR_OK;
+}
+int frr_drawlist_free(frr_ctx *c, int list)
+{
+    if (!c || !slot_ok(c->lists, list)) return fail(c, FRR_ERR_INVALID, "bad draw list id");
+    { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a pass over it
+    c->lists[list] = DrawList();
+    return FRR_OK;
+}
+// the GEOM command of a list pass, checked
+static int list_cmd(frr_ctx *c, int list, Cmd *cmd)
+{
+    if (!c || !slot_ok(c->lists, list)) return fail(c, FRR_ERR_INVALID, "bad draw list id");
+    if (c->lists[list].dead) return fail(c, FRR_ERR_INVALID, "a mesh the draw list names was freed: the list is dead (frr_drawlist_free still takes it)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    cmd->kind = Cmd::GEOM; cmd->list = list; cmd->list_gen = c->lists[list].gen; cmd->duni = c->duni; cmd->cull = c->cull;
+    h_mat4_mul(c->uni.proj, c->uni.view, cmd->pv);   // as refresh_dev_uniforms builds u.mvp
+    return FRR_OK;
+}
+int frr_geometry_list(frr_ctx *c, int list, uint64_t *ntris_setup)
+{
+    Cmd cmd;
+    int rc = list_cmd(c, list, &cmd);
+    if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
+    if (ntris_setup) {
+        if ((rc = finish(c)) != FRR_OK) return rc;
+        *ntris_setup = c->fs.geom_ntris ? c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit : 0;
+    }
+    return FRR_OK;
+}
+int frr_geometry_item_ranges(frr_ctx *c, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems)
+{
+    if (!c || !nitems || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry pass to take item ranges from");
+    if (c->fs.geom_filter.active)
+        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; use frr_geometry* + frr_raster for item ranges");
+    { int rcs = finish(c); if (rcs != FRR_OK) return rcs; }
+    const FrameState &f = c->fs;
+    const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
+    const GeomSet &S = c->gset[f.gset];
+    const uint64_t n = f.geom_nitems, w = std::min(cap, n);
+    const uint32_t *item_first = nullptr;
+    if (f.geom_list >= 0) {
+        if (!slot_ok(c->lists, f.geom_list) || c->lists[f.geom_list].gen != f.geom_list_gen) return fail(c, FRR_ERR_INVALID, "the draw list of the latest geometry pass was freed");
+        item_first = c->lists[f.geom_list].first;
+    }
+    *nitems = n;
+    if (!w || (!id_first && !id_count)) return FRR_OK;
+    const uint32_t nt = (uint32_t)f.geom_ntris, n_emit = nt ? gt.n_emit : 0u;
+    { int rc = ensure(c, c->item_tmp, (size_t)n + 1); if (rc != FRR_OK) return rc; }
+    hipLaunchKernelGGL(k_item_firsts, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, c->stream, item_first, (uint32_t)f.geom_stride, (uint32_t)n, nt,
+                       S.tinfo.get(), S.block_prefix.get(), n_emit, c->item_tmp.get());
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> e(w + 1);
+    HIP_TRY(c, hipMemcpyAsync(e.data(), c->item_tmp.get(), (w + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < w; ++i) {
+        if (id_first) id_first[i] = gt.tri_base + e[i];
+        if (id_count) id_count[i] = e[i + 1] - e[i];
+    }
+    return FRR_OK;
+}
+int64_t frr_host_list_item(const uint32_t *first, const uint32_t *ntris, uint64_t nitems, uint32_t t)
+{
+    if (!first || !ntris || nitems > 0xFFFFFFFFull) return -1;
+    const uint32_t i = list_item_search(first, ntris, 0u, (uint32_t)nitems, t);
+    return i < nitems && first[i] <= t ? (int64_t)i : -1;
+}
+
 // argument checks of frr_raster; *nothing: the call is valid and draws nothing
 static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, bool *nothing)
 {
@@ -2149,6 +2301,17 @@ int frr_draw_instanced(frr_ctx *c, int mesh, int inst, int ps_id, int32_t x0, in
     if (rc != FRR_OK) return rc;
     cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;   // as frr_draw
     if ((rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
+    return frr_raster(c, ps_id, x0, x1, y0, y1);
+}
+
+int frr_draw_list(frr_ctx *c, int list, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
+{
+    Cmd cmd;
+    int rc = list_cmd(c, list, &cmd);
+    if (rc != FRR_OK) return rc;
+    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;   // as frr_draw
+    if ((rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
+    if (!c->lists[list].n) return FRR_OK;   // no items: no vertex shader either, so nothing a pixel shader could fail to match
     return frr_raster(c, ps_id, x0, x1, y0, y1);
 }
 

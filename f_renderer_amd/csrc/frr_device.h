@@ -160,6 +160,28 @@ struct DevUniforms {
     uint32_t slot_w[FRR_MAX_TEXTURES], slot_h[FRR_MAX_TEXTURES];
 };
 
+// One item of a draw list on the device (frr_drawlist_upload: a snapshot of its mesh): 32 bytes, two 16-byte loads.
+struct ListRow {
+    const float *verts;     // [ntris][3][NF], or with idx: the vertex array [nverts][NF]
+    const uint32_t *idx;    // indexed mesh: [ntris][3]; else null (a per-item run-time branch in the LIST kernels)
+    uint32_t nverts;        // indexed mesh: the index clamp
+    uint32_t ntris, first;  // the item's inputs are [first, first + ntris) of the pass
+    uint32_t pad;
+};
+// The item that owns input t of a list pass: the first i in [lo, n) with first[i] + ntris[i] > t, or n if there is none.
+// The ends are non-decreasing, so this is a binary search; an empty item ends where it starts and is never the answer, which
+// "the first (or last) item with first[i] <= t" gets wrong where empty items repeat a value of `first`.  For the host:
+// frr_host_list_item.
+FRR_HD uint32_t list_item_search(const uint32_t *first, const uint32_t *ntris, uint32_t lo, uint32_t n, uint32_t t)
+{
+    uint32_t hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((unsigned long long)first[mid] + ntris[mid] > t) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
 struct GeomArgs {
     const float *in;        // [ntris][3][NF]; indexed mesh: [nverts][NF]
     const uint32_t *idx;    // indexed mesh: [ntris][3] vertex numbers (corner j of triangle t = in + idx[3t + j] * NF); else null
@@ -196,6 +218,13 @@ struct GeomArgs {
     uint32_t ntris_mesh;    // the mesh's own triangle count
     uint32_t ninst;
     int32_t cull;           // frr_set_cull as of the call (wave-uniform): an input the mode drops emits n = 0, like one with a w == 0
+    // A list pass (frr_geometry_list; the LIST instantiations of the geometry kernels): input t' of the pass is triangle
+    // t' - first[i] of item i, the one item with first[i] <= t' < first[i] + ntris[i] (list_item_search) -- dense, like an
+    // instanced pass -- under row i of `inst` (ninst = the number of items); `in`, `idx`, `nverts` and `ntris_mesh` are
+    // unused, each item brings its own.  Else null.
+    const ListRow *items;       // [ninst]
+    const uint32_t *item_first; // [ninst] exclusive prefix of the items' triangle counts (repeats where items are empty)
+    const uint32_t *item_ntris; // [ninst]
 };
 
 // tile-row ownership over a range of tile rows: ty % world == rank (interleaved), or, blocked != 0, the rows [brow0, brow1); world <= 1: all

@@ -328,9 +328,47 @@ constexpr int CLIP_INBLOCK = GEOM_BLOCK / 64;   // clipped inputs a geometry blo
 // whatever an index buffer that was rewritten in place without a re-bind holds.
 // With INST (an instanced pass, GeomArgs::inst) t is the pass's input t' and the corners are those of mesh triangle
 // t' % ntris_mesh; *inst: the matrices of instance t' / ntris_mesh.
-template <int NF, bool IDX, bool INST = false>
+// With LIST (a list pass, GeomArgs::items; instantiated with INST, without IDX) t is the pass's input t' too, and the
+// corners are those of triangle t' - first[i] of item i's mesh, plain or indexed by a run-time branch on the item's row;
+// *inst: row i of the matrix table.  The item and the triangle within it are clamped before any load: a guard for the
+// machine, no defined result (the table is the library's own and consistent).
+// The item of input t of a list pass.  The search runs once per wave, for the wave's first input and on wave-uniform values
+// (scalar registers, scalar loads where the compiler proves the tables unwritten); a lane whose input lies in the same item
+// -- every lane, where a mesh has more triangles than a wave has lanes, the common case -- takes that answer, and any other
+// lane searches only the side of it its input lies on.  Nobody walks from item 0.
+__device__ __forceinline__ uint32_t list_item_of(const GeomArgs &g, uint32_t t)
+{
+    const uint32_t n = g.ninst, t0 = __builtin_amdgcn_readfirstlane(t);
+    const uint32_t i0 = min(list_item_search(g.item_first, g.item_ntris, 0u, n, t0), n - 1u);
+    const uint32_t f0 = g.item_first[i0], e0 = f0 + g.item_ntris[i0];
+    uint32_t i = i0;
+    if (t >= e0) i = list_item_search(g.item_first, g.item_ntris, i0 + 1u, n, t);
+    else if (t < f0) i = list_item_search(g.item_first, g.item_ntris, 0u, i0, t);
+    return min(i, n - 1u);
+}
+
+template <int NF, bool IDX, bool INST = false, bool LIST = false>
 __device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const float *vp[3], const float **inst = nullptr)
 {
+    if constexpr (LIST) {
+        const uint32_t i = list_item_of(g, t);
+        const ListRow r = g.items[i];
+        const float *verts = r.verts;
+        const uint32_t *idx = r.idx;
+        const uint32_t tl = min(t - r.first, r.ntris ? r.ntris - 1u : 0u);
+        *inst = g.inst + (size_t)i * 32;
+        if (idx) {
+            const uint32_t *ix = idx + (size_t)tl * 3;
+            const uint32_t last = r.nverts - 1u;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) vp[v] = verts + (size_t)min(ix[v], last) * NF;
+        } else {
+            const float *in = verts + (size_t)tl * (3 * NF);
+#pragma unroll
+            for (int v = 0; v < 3; ++v) vp[v] = in + v * NF;
+        }
+        return;
+    }
     if constexpr (INST) {
         const uint32_t i = t / g.ntris_mesh;
         t -= i * g.ntris_mesh;
@@ -373,15 +411,15 @@ __device__ __forceinline__ void run_vs3(const DevUniforms &u, const float *im, c
 
 // Returns the lane's binning record (all zero for lanes that emit no fan triangle).  eoff: the input's emission offset
 // within its geometry block (tinfo[t] >> FAN_BITS).
-template <int VS, bool IDX, bool INST = false>
+template <int VS, bool IDX, bool INST = false, bool LIST = false>
 __device__ __forceinline__ uint4 clip_triangle_wave(const GeomArgs &g, const DevUniforms &u, uint32_t t, uint32_t fbase, uint32_t eoff, int lane,
                                                    float (*s_xy)[2], int32_t *s_key, float (*s_v)[7 + (VSInfo<VS>::K > 0 ? VSInfo<VS>::K : 1)])
 {
     constexpr int NF = VSInfo<VS>::NF, K = VSInfo<VS>::K, KS = K > 0 ? K : 1;
     float pos[3][4], ctx[3][KS];
     const float *in[3], *im = nullptr;
-    if constexpr (INST) t = __builtin_amdgcn_readfirstlane(t);   // (one triangle per wave: its instance's matrices are wave-uniform)
-    tri_inputs<NF, IDX, INST>(g, t, in, &im);
+    if constexpr (INST) t = __builtin_amdgcn_readfirstlane(t);   // (one triangle per wave: its instance's, or item's, matrices are wave-uniform)
+    tri_inputs<NF, IDX, INST, LIST>(g, t, in, &im);
     run_vs3<VS, INST>(u, im, in, pos, ctx);
     // this lane's vertex
     float p[4], c[KS];
@@ -582,7 +620,7 @@ __device__ __forceinline__ void geom_bookkeeping(const GeomArgs &g)
     me.tinfo = g.tinfo; me.fanbase = g.fanbase; me.fan_okey = g.fan_okey; me.block_prefix = g.block_prefix;
 }
 
-template <int VS, bool IDX, bool INST = false>
+template <int VS, bool IDX, bool INST = false, bool LIST = false>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUniforms u)
 {
     __shared__ uint32_t s_w[4];
@@ -607,7 +645,7 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
     bool clipped = false;
     if (t < g.ntris) {
         const float *in[3], *im = nullptr;
-        tri_inputs<NF, IDX, INST>(g, t, in, &im);
+        tri_inputs<NF, IDX, INST, LIST>(g, t, in, &im);
         run_vs3<VS, INST>(u, im, in, pos, ctx);
         n = classify(pos, clipped);
         // frr_set_cull: an input the mode drops emits nothing, like one with a w == 0 -- decided before the block scan, so
@@ -760,13 +798,13 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         for (uint32_t e = (uint32_t)w; e < nin; e += GEOM_BLOCK / 64) {
             const uint32_t en = s_cl[e];
-            (void)clip_triangle_wave<VS, IDX, INST>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
+            (void)clip_triangle_wave<VS, IDX, INST, LIST>(g, u, bid * GEOM_BLOCK + (en & 255u), fbase + (en >> 8), s_ce[en & 255u], lane, s_cxy[w], s_ckey[w], s_cv[w]);
         }
     }
 }
 
 // the clipped inputs the geometry blocks queued (GeomArgs::use_clipq), one wavefront per triangle over the whole chip
-template <int VS, bool IDX, bool INST = false>
+template <int VS, bool IDX, bool INST = false, bool LIST = false>
 __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniforms u)
 {
     __shared__ float s_cxy[GEOM_BLOCK / 64][CLIP_MAXV][2];
@@ -778,7 +816,7 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_clip(GeomArgs g, DevUniform
     const uint32_t stride = gridDim.x * (GEOM_BLOCK / 64);
     for (uint32_t e = blockIdx.x * (GEOM_BLOCK / 64) + (uint32_t)w; e < n; e += stride) {
         const uint2 q = g.clipq[e];
-        (void)clip_triangle_wave<VS, IDX, INST>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
+        (void)clip_triangle_wave<VS, IDX, INST, LIST>(g, u, q.x, q.y, g.tinfo[q.x] >> FAN_BITS, lane, s_cxy[w], s_ckey[w], s_cv[w]);
     }
 }
 
@@ -798,6 +836,18 @@ __global__ __launch_bounds__(256) void k_instance_mvp(const float *__restrict__ 
     float4 *dst = reinterpret_cast<float4 *>(out + (size_t)i * 32);
     dst[c] = make_float4(o[0], o[1], o[2], o[3]);
     dst[4 + c] = b;
+}
+
+// frr_geometry_item_ranges: out[i], i in 0..nitems, = the emission index within the pass of the first input of item i (a
+// list pass: item_first; else the items are `stride` inputs each) -- from the pass's own tables, as the tile kernel's
+// resolve numbers a triangle -- and out[nitems] = n_emit.  An item that starts behind the last input starts there as well.
+__global__ __launch_bounds__(256) void k_item_firsts(const uint32_t *__restrict__ item_first, uint32_t stride, uint32_t nitems, uint32_t ntris,
+                                                     const uint32_t *__restrict__ tinfo, const uint32_t *__restrict__ block_prefix, uint32_t n_emit, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > nitems) return;
+    const unsigned long long f = i == nitems ? ntris : item_first ? item_first[i] : (unsigned long long)i * stride;
+    out[i] = f >= ntris ? n_emit : block_prefix[(uint32_t)f / GEOM_BLOCK] + (tinfo[(uint32_t)f] >> FAN_BITS);
 }
 
 // An empty mesh launches no geometry kernel proper: the per-draw bookkeeping alone.

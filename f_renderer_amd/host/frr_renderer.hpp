@@ -305,6 +305,7 @@ inline Model::Indexed Model::indexed_inputs() const
 struct Mesh { int id = -1; uint64_t ntris = 0; int vs = 0; };
 struct Lines { int id = -1; uint64_t nlines = 0; };   // a list of draw_line calls on the device
 struct Instances { int id = -1; uint64_t ninst = 0; };   // a table of model matrices on the device: one per instance of an instanced pass
+struct DrawList { int id = -1; uint64_t nitems = 0; };   // (mesh, model matrix) items on the device: one list pass draws them all
 struct LineSegment { uint32_t x1, y1, x2, y2; };
 static_assert(sizeof(LineSegment) == 16, "LineSegment must be 4 packed u32");
 
@@ -381,6 +382,21 @@ public:
         return t;
     }
     void free_instances(Instances &t) { if (t.id >= 0) { check(frr_instances_free(ctx_, t.id)); t.id = -1; } }
+    // The objects of a frame that do not share a mesh (phong.rs:319-359: body, face, hair), each under its own model matrix
+    // (column-major like uniforms.model).  A snapshot of the meshes: freeing one of them kills the list.
+    DrawList upload_draw_list(const std::vector<Mesh> &meshes, const std::vector<Mat4> &models)
+    {
+        if (meshes.size() != models.size()) throw Error(FRR_ERR_INVALID, "one model matrix per mesh");
+        std::vector<frr_draw_item> items(meshes.size());
+        for (size_t i = 0; i < items.size(); ++i) {
+            items[i].mesh = meshes[i].id; items[i].reserved = 0;
+            std::memcpy(items[i].model, models[i].data(), sizeof items[i].model);
+        }
+        DrawList l; l.nitems = items.size();
+        check(frr_drawlist_upload(ctx_, items.empty() ? nullptr : items.data(), l.nitems, &l.id));
+        return l;
+    }
+    void free_draw_list(DrawList &l) { if (l.id >= 0) { check(frr_drawlist_free(ctx_, l.id)); l.id = -1; } }
     Lines upload_lines(const std::vector<LineSegment> &segments, const std::vector<std::array<uint8_t, 4>> &colors)
     {
         if (segments.size() != colors.size()) throw Error(FRR_ERR_INVALID, "one colour per segment");
@@ -444,6 +460,27 @@ public:
     // Face culling of the geometry passes issued from now on (frr_set_cull): FRR_CULL_NONE, FRR_CULL_NEG (drop the inputs whose
     // clip-space determinant is < 0) or FRR_CULL_POS (> 0).  The reference has no such switch: the default draws everything.
     void set_cull(int mode) { check(frr_set_cull(ctx_, mode)); }
+    // Loop A over every item's mesh under that item's matrix into ONE setup list in (item, triangle) order -- the whole setup
+    // loop of phong.rs:319-359; draw_list: that and one rasterization over the list.  Bit for bit what one draw(mesh_i) per
+    // item gives with uniforms.model = model_i.
+    void geometry_list(const DrawList &l) { check(frr_geometry_list(ctx_, l.id, nullptr)); }
+    void draw_list(const DrawList &l, int pixel_shader)
+    {
+        check(frr_draw_list(ctx_, l.id, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
+    }
+    // per item of the latest geometry pass (list items, instances, or one for a plain pass): the triangle id of its first setup
+    // triangle and how many it emitted -- body_offset / face_offset of phong.rs:333-359 without a read-back per draw
+    void item_ranges(std::vector<uint32_t> &first, std::vector<uint32_t> &count)
+    {
+        uint64_t n = 0;
+        check(frr_geometry_item_ranges(ctx_, nullptr, nullptr, 0, &n));
+        first.assign((size_t)n, 0u); count.assign((size_t)n, 0u);
+        if (n) check(frr_geometry_item_ranges(ctx_, first.data(), count.data(), n, &n));
+    }
+    static int64_t host_list_item(const std::vector<uint32_t> &first, const std::vector<uint32_t> &ntris, uint32_t t)
+    {
+        return first.size() == ntris.size() ? frr_host_list_item(first.data(), ntris.data(), first.size(), t) : -1;
+    }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream
     // waits for every frame issued so far; frame_wait -- the next write of the frame targets waits for what the stream holds now

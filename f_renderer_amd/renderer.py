@@ -181,6 +181,27 @@ class Instances:
             self.id = None
 
 
+class DrawList:
+    """A list of (mesh, model matrix) items on the device (Renderer.upload_draw_list): a snapshot of the meshes it names."""
+
+    def __init__(self, renderer, list_id, nitems, ntris, keepalive=None):
+        self.renderer, self.id, self.nitems, self.ntris, self._keep = renderer, list_id, nitems, ntris, keepalive
+
+    def free(self):
+        if self.id is not None:
+            self.renderer._check(N.lib().frr_drawlist_free(self.renderer._ctx, self.id))
+            self.id = None
+
+
+def host_list_item(first, ntris, t):
+    """The item of a list pass that owns input t as the geometry kernels find it (frr_host_list_item): the i with
+    first[i] <= t < first[i] + ntris[i], or -1."""
+    f, n = np.ascontiguousarray(first, np.uint32), np.ascontiguousarray(ntris, np.uint32)
+    if f.shape != n.shape or f.ndim != 1:
+        raise FrrError(N.FRR_ERR_INVALID, "host_list_item: first and ntris must be 1-D and of one length")
+    return int(N.lib().frr_host_list_item(f.ctypes.data, n.ctypes.data, f.size, int(t)))
+
+
 def host_instance_mvp(proj, view, model):
     """(proj * view) * model as the device computes it per instance (frr_host_instance_mvp): float32 [16], column-major."""
     p, v, m = (np.ascontiguousarray(x, np.float32).reshape(16) for x in (proj, view, model))
@@ -457,6 +478,50 @@ class Renderer:
         wr = width_range or (0, self.width)
         hr = height_range or (0, self.height)
         self._check(self._lib.frr_draw_instanced(self._ctx, mesh.id, instances.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
+
+    def upload_draw_list(self, meshes, models, reserved=0):
+        """(mesh, model matrix) items -> device (frr_drawlist_upload): meshes, a sequence of Mesh; models, float32
+        [nitems, 16] (or [nitems, 4, 4] in memory order), column-major like uniforms.model.  The list is a snapshot: freeing
+        a mesh it names kills it."""
+        a = np.ascontiguousarray(models, np.float32).reshape(-1)
+        if a.size != 16 * len(meshes):
+            raise FrrError(N.FRR_ERR_INVALID, "one 4x4 model matrix per mesh")
+        items = (N.DrawItem * max(len(meshes), 1))()
+        for i, m in enumerate(meshes):
+            items[i].mesh, items[i].reserved = -1 if m.id is None else m.id, reserved
+            items[i].model[:] = a[16 * i:16 * i + 16].tolist()
+        lid = C.c_int()
+        self._check(self._lib.frr_drawlist_upload(self._ctx, C.cast(items, C.c_void_p) if meshes else None, len(meshes), C.byref(lid)))
+        return DrawList(self, lid.value, len(meshes), sum(m.ntris for m in meshes), keepalive=list(meshes))
+
+    def free_draw_list(self, draw_list):
+        draw_list.free()
+
+    def geometry_list(self, draw_list, count=False):
+        """Loop A over every item's mesh under that item's model matrix, into ONE setup list in (item, triangle) order: the
+        whole setup loop of phong.rs:319-359 (frr_geometry_list)."""
+        n = C.c_uint64()
+        self._check(self._lib.frr_geometry_list(self._ctx, draw_list.id, C.byref(n) if count else None))
+        return int(n.value) if count else None
+
+    def draw_list(self, draw_list, pixel_shader, width_range=None, height_range=None):
+        """geometry_list + rasterization: what one set_uniforms(model=...) + draw(mesh) per item gives, bit for bit, in one
+        pass (frr_draw_list)."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        self._check(self._lib.frr_draw_list(self._ctx, draw_list.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
+
+    def item_ranges(self, cap=None):
+        """(first, count), uint32 arrays: per item of the latest geometry pass -- the items of a list pass, the instances of
+        an instanced pass, one item for a plain pass -- the triangle id of its first setup triangle and how many it emitted
+        (frr_geometry_item_ranges; a synchronisation point).  cap: at most that many entries."""
+        n = C.c_uint64()
+        self._check(self._lib.frr_geometry_item_ranges(self._ctx, None, None, 0, C.byref(n)))
+        w = int(n.value) if cap is None else min(int(cap), int(n.value))
+        first, count = np.zeros(w, np.uint32), np.zeros(w, np.uint32)
+        if w:
+            self._check(self._lib.frr_geometry_item_ranges(self._ctx, first.ctypes.data, count.ctypes.data, w, C.byref(n)))
+        return first, count
 
     def draw_lines(self, lines):
         """for each segment of the list, in order: frame_buffer.draw_line(x1, y1, x2, y2, color) on the colour target (depth

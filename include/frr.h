@@ -326,6 +326,56 @@ int frr_instances_free(frr_ctx *ctx, int inst);
 int frr_geometry_instanced(frr_ctx *ctx, int mesh, int inst, uint64_t *ntris_setup);
 int frr_draw_instanced(frr_ctx *ctx, int mesh, int inst, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
 
+/* ---- draw lists --------------------------------------------------------------------------- */
+
+/* Many meshes, each under its own model matrix, in ONE geometry pass: the reference's whole setup loop (phong.rs:319-359
+ * builds one setup list from three different meshes) as one call, and its rasterization loop (:361-381) as one tile kernel.
+ * A draw list is nitems (mesh, model matrix) items; the matrix is 16 f32, column-major like frr_uniforms.model.
+ * frr_geometry_list(list) is BY DEFINITION this loop, concatenated into one setup list in that order:
+ *     for i in 0..nitems:
+ *         vs_uniform.model = items[i].model
+ *         for t in 0..ntris(mesh_i): geometry_processing(mesh_i[t])   (renderer.rs:96-267)
+ * and frr_draw_list is that loop followed by one Loop B over the list (renderer.rs:269-384).  Hence:
+ * - Depth bits, ids, RGBA8, the setup list and tris_setup / frag_covered / frag_nan are, bit for bit, those of nitems
+ *   plain frr_draw calls of mesh_i, each after an frr_set_uniforms that differs only in model = items[i].model.
+ * - Emission order is (item, input triangle, fan triangle).  The ids of one item are one contiguous range
+ *   (frr_geometry_item_ranges below; ranged frr_shade_varyings: per-object pixel uniforms, the `place` rule of
+ *   phong.rs:147-151); the ids of later draws of the frame continue behind the whole pass.  Where fragments tie in depth
+ *   the later item wins (renderer.rs:363).
+ * - Statistics: tris_in grows by the sum of the items' triangle counts, draws by 1.
+ * - mvp_i = (proj * view) * items[i].model with the arithmetic of an instanced pass (frr_host_instance_mvp).  Only the
+ *   vertex shader sees an item's matrices; the pixel shader runs with the call's uniforms.
+ * - The cull mode of the call (frr_set_cull) is evaluated per (item, triangle) under that item's matrices.
+ * - A list whose items all name one mesh is frr_draw_instanced of that mesh under the same matrices, bit for bit.
+ * - Items may mix plain and indexed meshes, host-uploaded and device-bound ones; a device-bound mesh follows the rule
+ *   for in-place rewrites unchanged (frr_frame_fence, rewrite, bind again -- and upload the list again: see below).
+ * - All items must carry the same vs_id, built-in or user: otherwise the upload fails with FRR_ERR_INVALID and
+ *   frr_last_error names the first offending item.
+ * - nitems == 0 is a pass that emits nothing (draws still counts it); an item whose mesh has no triangles is valid at
+ *   any position, several in a row too.
+ * - The list is a SNAPSHOT taken at upload: the matrices, and per mesh its pointers, counts and registration.  Freeing a
+ *   mesh that a live list names kills the list: frr_geometry_list / frr_draw_list of it return FRR_ERR_INVALID,
+ *   frr_drawlist_free still takes it, and a later mesh that gets the freed id does not revive it.
+ * - frr_debug_mvp is unaffected.
+ * Errors: the sum of the items' triangle counts >= 2^27: FRR_ERR_UNSUPPORTED at upload, before anything is allocated;
+ * reserved != 0, a NULL array with nitems > 0, an unknown or freed mesh or list id: FRR_ERR_INVALID.
+ * The calls are logged, verified and replayed like frr_geometry / frr_draw (a replay fills the matrix table again and runs
+ * under the cull mode and uniforms of the call), and everything downstream of a geometry pass takes the list's setup list
+ * as it is: frr_raster with any window, frr_readback_setup, frr_draw_wireframe, frr_resolve_varyings,
+ * frr_shade_varyings, the partition filter of a draw. */
+typedef struct frr_draw_item { int32_t mesh; int32_t reserved; float model[16]; } frr_draw_item; /* reserved = 0 */
+int frr_drawlist_upload(frr_ctx *ctx, const frr_draw_item *items, uint64_t nitems, int *list_out);
+int frr_drawlist_free(frr_ctx *ctx, int list);
+int frr_geometry_list(frr_ctx *ctx, int list, uint64_t *ntris_setup);
+int frr_draw_list(frr_ctx *ctx, int list, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1);
+/* Per item of the LATEST geometry pass: the frame-global emission index (= triangle id) of its first setup triangle, and
+ * how many it emitted.  The items of a list pass, the instances of an instanced pass, one item for a plain pass.  An item
+ * that emitted nothing has count 0 and first = where it would have started.  The numbers come from the pass's device
+ * tables at the item boundaries (the setup list is not read back).  A synchronisation point like frr_readback_setup,
+ * and FRR_ERR_INVALID where that fails: before any geometry pass, and after a frr_draw* that filtered the list on a
+ * partitioned ctx.  With cap < *nitems it writes cap entries and still returns *nitems; either array may be NULL. */
+int frr_geometry_item_ranges(frr_ctx *ctx, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems);
+
 /* ---- face culling ------------------------------------------------------------------------- */
 
 /* The reference draws every input triangle, whichever way it faces; frr_set_cull lets a geometry pass drop those that face
@@ -592,6 +642,9 @@ int64_t frr_host_line_pixels(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2,
 /* host build of the device's per-instance matrix product (cf. frr_host_atan2f, frr_host_line_pixels):
  * out = (proj * view) * model, column-major, every element ((a0*b0 + a1*b1) + a2*b2) + a3*b3 */
 void frr_host_instance_mvp(const float proj[16], const float view[16], const float model[16], float out[16]);
+/* host build of the device's item search of a list pass (cf. frr_host_line_pixels): the item i with
+ * first[i] <= t < first[i] + ntris[i], or -1; first is the exclusive prefix of ntris (it repeats where items are empty) */
+int64_t frr_host_list_item(const uint32_t *first, const uint32_t *ntris, uint64_t nitems, uint32_t t);
 /* host build of the device's facing determinant (frr_set_cull; cf. frr_host_atan2f): d of the three clip positions
  * clip[0..3], clip[4..7], clip[8..11] (x, y, z, w each) */
 float frr_host_cull_det(const float clip[12]);

@@ -36,6 +36,15 @@ pub mod ffi {
         pub texture_slot: i32, // PSUniform.place
     }
 
+    /// one item of a draw list (frr_drawlist_upload): a mesh id and its model matrix, column-major; reserved = 0
+    #[repr(C)]
+    #[derive(Clone, Copy, Default, Debug)]
+    pub struct frr_draw_item {
+        pub mesh: i32,
+        pub reserved: i32,
+        pub model: [f32; 16],
+    }
+
     #[repr(C)]
     #[derive(Clone, Copy, Default, Debug)]
     pub struct frr_stats {
@@ -92,6 +101,13 @@ pub mod ffi {
         pub fn frr_geometry_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ntris_setup: *mut u64) -> c_int;
         pub fn frr_draw_instanced(ctx: *mut frr_ctx, mesh: c_int, inst: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
         pub fn frr_host_instance_mvp(proj: *const f32, view: *const f32, model: *const f32, out: *mut f32);
+        // draw lists: many meshes, each under its own model matrix, in one pass (the whole setup loop of phong.rs:319-359)
+        pub fn frr_drawlist_upload(ctx: *mut frr_ctx, items: *const frr_draw_item, nitems: u64, list_out: *mut c_int) -> c_int;
+        pub fn frr_drawlist_free(ctx: *mut frr_ctx, list: c_int) -> c_int;
+        pub fn frr_geometry_list(ctx: *mut frr_ctx, list: c_int, ntris_setup: *mut u64) -> c_int;
+        pub fn frr_draw_list(ctx: *mut frr_ctx, list: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
+        pub fn frr_geometry_item_ranges(ctx: *mut frr_ctx, id_first: *mut u32, id_count: *mut u32, cap: u64, nitems: *mut u64) -> c_int;
+        pub fn frr_host_list_item(first: *const u32, ntris: *const u32, nitems: u64, t: u32) -> i64;
         // face culling of the geometry passes issued from now on (0 none, 1 drop d < 0, 2 drop d > 0): set beside the uniforms
         pub fn frr_set_cull(ctx: *mut frr_ctx, mode: c_int) -> c_int;
         pub fn frr_host_cull_det(clip: *const f32) -> f32;
