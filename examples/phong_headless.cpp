@@ -17,6 +17,9 @@
 //       the loop over objects of phong.rs:319-331 as one instanced pass (draw_instanced)
 //   --list anywhere among them draws the objects -- the N copies of --instances, else the one mesh -- as (mesh, model matrix) items
 //       of ONE list pass (draw_list): the setup loop of phong.rs:319-359, where every object may name a mesh of its own
+//   --visible with --list or --instances N prints, after the draw, one line per item -- its first triangle id, the triangles
+//       it emitted and the pixels it owns on screen (visible_pixels: counted on the device, the frame is not read back for
+//       it) -- and the number of items that own no pixel; the frame written is the same
 //   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
 //       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
@@ -39,10 +42,10 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false, list = false;
+    bool wireframe = false, deferred = false, list = false, visible = false;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list") {
-            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : deferred) = true;
+        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible") {
+            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -62,6 +65,7 @@ int main(int argc, char **argv)
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
             argc -= 2; --i;
         }
+    if (visible && !list && instances < 0) { std::cerr << "--visible goes with --list or --instances N\n"; return 2; }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -81,7 +85,8 @@ int main(int argc, char **argv)
                      "       phong_headless --assets model.obj diffuse.tga W H out.rgba [out.ppm]\n"
                      "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade;\n"
                      "        --instances N: N copies on a grid in one instanced pass; --list: the objects as one list pass;\n"
-                     "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign)\n";
+                     "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign;\n"
+                     "        --visible (with --list or --instances N): print the pixels every item owns on screen)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -158,6 +163,19 @@ int main(int argc, char **argv)
             std::vector<float> varyings;
             const int num_varyings = renderer.readback_varyings(varyings);                      // ... its `input` (:368-378) per pixel ...
             renderer.shade_varyings_host(FRR_PS_PHONG, varyings, num_varyings);                 // ... and :380-381 over that buffer
+        }
+        if (visible) {
+            // which objects ended up on screen: the id target counted per item on the device (the wireframe and the shade pass
+            // write colour only, so the place behind the raster pass is as good as any)
+            const std::vector<uint32_t> pixels = renderer.visible_pixels(FRR_PER_ITEM);
+            std::vector<uint32_t> first, count;
+            renderer.item_ranges(first, count);
+            size_t hidden = 0;
+            for (size_t k = 0; k < pixels.size(); ++k) {
+                std::printf("item %zu: first id %u, triangles %u, visible pixels %u\n", k, first[k], count[k], pixels[k]);
+                hidden += pixels[k] == 0u;
+            }
+            std::printf("items that own no pixel: %zu of %zu\n", hidden, pixels.size());
         }
         if (wireframe) renderer.draw_wireframe({255, 255, 255, 255});                           // the edges over the shaded frame
         renderer.read_frame_buffer(frame_buffer);                                               // phong.rs:386

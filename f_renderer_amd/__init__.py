@@ -4,6 +4,7 @@ path is hand-written HIP in f_renderer_amd/csrc.  No CPU fallback exists."""
 from . import scenes  # noqa: F401
 from ._native import (FRR_ERR_CAPACITY, FRR_ERR_HIP, FRR_ERR_INVALID, FRR_ERR_NOMEM, FRR_ERR_UNSUPPORTED,  # noqa: F401
                       FRR_OK, FrrError, build, lib)
+from ._native import PER_ITEM, PER_TRIANGLE, VISIBLE_LDS_BINS  # noqa: F401
 from .renderer import (CULL_NEG, CULL_NONE, CULL_POS, PS_BLINN, PS_COLOR, PS_DEPTH, PS_FLAT, PS_PHONG, VS_CLIP,  # noqa: F401
                        VS_CLIP_COLOR, VS_GOURAUD, VS_PHONG, Camera, DrawList, FrameBuffer, Instances, Lines, Mesh, Renderer, host_cull_det,
-                       host_instance_mvp, host_list_item, set_identity, set_look_at, set_perspective)
+                       host_instance_mvp, host_list_item, host_visible_counts, set_identity, set_look_at, set_perspective)

@@ -5,6 +5,7 @@
 #include "frr_lines.h"
 #include "frr_varyings.h"
 #include "frr_shade.h"
+#include "frr_visible.h"
 #include "frr_own.h"
 
 #include <math.h>
@@ -41,10 +42,10 @@ using namespace frr;
 namespace {
 
 enum KernelId { KID_CLEAR, KID_GEOM, KID_GEOM_SCAN, KID_BIN_COUNT,
-                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_LINES_MARK, KID_LINES_PAINT, KID_COUNT };
+                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_LINES_MARK, KID_LINES_PAINT, KID_VISIBLE, KID_COUNT };
 const char *const kKernelNames[KID_COUNT] = {"k_clear", "k_geom", "k_geom_scan",
                                              "k_bin_count", "k_tile_scan", "k_bin_fill",
-                                             "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint"};
+                                             "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint", "k_visible"};
 
 struct Mesh {
     DevBuf<float> own_dev; DevBuf<uint32_t> own_idx;   // a host upload: the library's copies (dev / idx point at them); else empty, and dev AND idx are the caller's
@@ -235,7 +236,7 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER, LINES, VARY, SHADE } kind;
+    enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE } kind;
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -253,6 +254,8 @@ struct Cmd {
     // SHADE (frr_shade_varyings): the window in x0 .. y1, the shader in ps, the buffer ([shade_entries][shade_K]: the caller's,
     // or one of frr_ctx::shade_tmp) and the range of triangle ids
     const float *shade_in = nullptr; uint64_t shade_entries = 0; int shade_K = 0; uint32_t id_first = 0, id_count = 0;
+    // VISIBLE (frr_visible_pixels): the window in x0 .. y1, the unit and the caller's buffer
+    int vis_unit = 0; uint32_t *vis_out = nullptr; uint64_t vis_entries = 0;
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
@@ -375,6 +378,9 @@ struct frr_ctx {
     // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
     DevBuf<uint32_t> line_owner[3];
     uint32_t lines_chunk = 0;       // option lines_chunk (0: LINES_CHUNK)
+    // frr_visible_pixels: the item boundaries of a count in flight, one table per stream that can carry one (as line_owner)
+    DevBuf<uint32_t> vis_bounds[3];
+    uint32_t visible_lds_bins = 0;  // option visible_lds_bins (0: VIS_LDS_BINS)
     // per lane of device tables: the latest wireframe reads its geometry pass's fan cursors, which the next pass IN THAT LANE
     // zeroes (geom_bookkeeping), whatever workspace set it writes; the other lane's frame shares nothing with it
     ReaderFence wire_reader[2];
@@ -1295,6 +1301,75 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_visible_pixels: the triangle-id target of a window as counts per item of the latest geometry pass, or per triangle of
+// the frame (frr_visible.h).  Ordered like frr_resolve_varyings: on the targets' stream behind the pass's geometry, it reads
+// the pass's tables on the device (no host wait), cannot fail there and owns no device table, so a replay runs it again in
+// its place -- behind a failed command it writes nothing, not even the zeros (seq_cancelled).
+int exec_visible(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    int rc;
+    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass
+    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    const bool item = cmd.vis_unit == FRR_PER_ITEM;
+    const bool cleared = f.draws == 0;   // frr_clear since the pass: the id target holds nothing of it, and its tables are gone
+    const uint32_t *item_first = nullptr;
+    if (item && !cleared && f.geom_list >= 0) {
+        if (!slot_ok(c->lists, f.geom_list) || c->lists[f.geom_list].gen != f.geom_list_gen) return fail(c, FRR_ERR_INVALID, "the draw list of the latest geometry pass was freed");
+        item_first = c->lists[f.geom_list].first;
+    }
+    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
+    hipStream_t ts = tstream_of(c);
+    // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
+    if (ts != c->stream) c->tstream[f.tset].dirty = c->tstream[f.tset].xdirty = true;
+    // the units the histogram can meet: decides the path, and whether there is anything to count at all
+    const uint64_t bound = cleared ? 0 : item ? std::min<uint64_t>(f.geom_nitems, cmd.vis_entries) : cmd.vis_entries;
+    const GeomSet &S = c->gset[f.gset];
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    VisibleArgs a;
+    memset(&a, 0, sizeof a);
+    a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
+    a.unit = cmd.vis_unit;
+    a.ntris = cleared ? 0u : (uint32_t)f.geom_ntris;
+    a.tinfo = S.tinfo; a.block_prefix = S.block_prefix;
+    if (item && bound > 0) {
+        DevBuf<uint32_t> &tab = c->vis_bounds[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
+        if ((rc = ensure(c, tab, (size_t)f.geom_nitems + 1)) != FRR_OK) return rc;
+        a.nitems = (uint32_t)f.geom_nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom_stride; a.bounds = tab;
+    }
+    a.gpar = f.gpar(); a.lane = f.lane;
+    a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    a.tri_id = f.tri_id; a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
+    const uint32_t cap = c->visible_lds_bins ? c->visible_lds_bins : VIS_LDS_BINS;
+    const bool lds = bound <= cap;
+    // rows per workgroup: a span is a chain of dependent loads, so what counts is waves in flight -- as many workgroups as
+    // the window has rows, up to 2,048 -- but no fewer than 16 spans (four per wave) for a workgroup's set-up and flush
+    const uint64_t spr = ((uint64_t)ww + VIS_SPAN - 1) / VIS_SPAN;
+    a.rows = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(std::max<uint64_t>((16 + spr - 1) / spr, (uint64_t)(wh + 2047) / 2048), (uint64_t)wh), 1);
+    {
+        ProfScope p(c, KID_VISIBLE, ts);
+        const uint64_t pn = std::max<uint64_t>(cmd.vis_entries, (uint64_t)a.nitems + 1);
+        hipLaunchKernelGGL(k_visible_prep, dim3((uint32_t)std::min<uint64_t>((pn + VIS_WG - 1) / VIS_WG, 2048)), dim3(VIS_WG), 0, ts, a);
+        if (bound > 0) {
+            const dim3 grid((uint32_t)((wh + a.rows - 1) / a.rows)), block(VIS_WG);
+            const bool blds = item && a.nitems <= VIS_LDS_BINS;   // the boundaries fit LDS too
+            if (item && lds && blds) hipLaunchKernelGGL((k_visible<true, true, true>), grid, block, 0, ts, a);
+            else if (item && lds) hipLaunchKernelGGL((k_visible<true, true, false>), grid, block, 0, ts, a);
+            else if (item && blds) hipLaunchKernelGGL((k_visible<true, false, true>), grid, block, 0, ts, a);
+            else if (item) hipLaunchKernelGGL((k_visible<true, false, false>), grid, block, 0, ts, a);
+            else if (lds) hipLaunchKernelGGL((k_visible<false, true, false>), grid, block, 0, ts, a);
+            else hipLaunchKernelGGL((k_visible<false, false, false>), grid, block, 0, ts, a);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    // like a resolve it reads the pass's tables, which a later pass of this lane overwrites
+    ReaderFence &wr = c->wire_reader[f.lane];
+    wr.pending = true; wr.stream = ts; wr.recorded = false;
+    cmd.par = f.gpar(); cmd.set = f.gset; cmd.lane = f.lane;
+    return FRR_OK;
+}
+
 // frr_shade_varyings: a pixel shader over a buffer of varyings into the colour target (frr_shade.h).  It writes a target, so it
 // is ordered like a line list: on the targets' stream, behind a pending frr_clear and the streams of pending frr_frame_wait
 // calls (the caller's writes of the buffer).  It reads nothing of a geometry pass, cannot fail on the device and owns no
@@ -1351,7 +1426,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : exec_shade(c, cmd);
+    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : cmd.kind == Cmd::VISIBLE ? exec_visible(c, cmd) : exec_shade(c, cmd);
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1419,10 +1494,10 @@ int finish(frr_ctx *c)
         // the device tables as they were before the failed command: it has used its own parity's cursors (and, when its
         // block sums were scanned inside the next raster pass's binning launch, that pass has reserved bin space)
         h.first_bad = SEQ_NONE; h.overflow = 0u;
-        // (line, varyings and shade commands in between own no table: the "next" command is the next geometry or raster pass)
+        // (line, varyings, count and shade commands in between own no table: the "next" command is the next geometry or raster pass)
         for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
-            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE) continue;
+            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE || m.kind == Cmd::VISIBLE) continue;
             ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
@@ -1579,6 +1654,7 @@ int frr_set_option(frr_ctx *c, const char *name, int64_t v)
     else if (n == "overlap") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "overlap: 0, 1 or 2"); c->overlap = (int)v; }
     else if (n == "bound_targets_in_flight") c->bound_in_flight = v != 0;
     else if (n == "tile_order") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "tile_order: 0, 1 or 2"); c->tile_order = (int)v; }
+    else if (n == "visible_lds_bins") { if (v < 0 || v > (int64_t)VIS_LDS_BINS) return fail(c, FRR_ERR_INVALID, "visible_lds_bins: 0 .. VIS_LDS_BINS"); c->visible_lds_bins = (uint32_t)v; }
     else if (n == "lines_chunk") { if (v < 0 || v > (int64_t)LINES_CHUNK) return fail(c, FRR_ERR_INVALID, "lines_chunk: 0 .. 2^24"); c->lines_chunk = (uint32_t)v; }
     else if (n == "frames_in_flight") { if (v != 1 && v != 2) return fail(c, FRR_ERR_INVALID, "frames_in_flight: 1 or 2"); c->frames_in_flight = (int)v; }
     else return fail(c, FRR_ERR_INVALID, "unknown option");
@@ -2415,12 +2491,9 @@ int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uin
     return FRR_OK;
 }
 
-// argument checks of frr_resolve_varyings / frr_readback_varyings; *K: varyings per vertex, *nothing: valid, writes nothing
-static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries, int *K, bool *nothing)
+// the window rules of the commands that address the targets entry by entry (frr_resolve_varyings, frr_visible_pixels)
+static int entry_window_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
-    if (!c) return FRR_ERR_INVALID;
-    const FrameState &f = c->fs;
-    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
     if (x1 <= x0 || y1 <= y0) return fail(c, FRR_ERR_INVALID, "empty or inverted window");
     if (x0 < 0) return fail(c, FRR_ERR_UNSUPPORTED, "x0 < 0: pixels of neighbouring rows share depth entries, an entry has no single pixel");
     const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
@@ -2428,6 +2501,17 @@ static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1
     if (y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_INVALID, "window coordinates outside the i16 range");
     if ((wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H)
         return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
+    return FRR_OK;
+}
+
+// argument checks of frr_resolve_varyings / frr_readback_varyings; *K: varyings per vertex, *nothing: valid, writes nothing
+static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries, int *K, bool *nothing)
+{
+    if (!c) return FRR_ERR_INVALID;
+    const FrameState &f = c->fs;
+    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
+    { const int rcw = entry_window_check(c, x0, x1, y0, y1); if (rcw != FRR_OK) return rcw; }
+    const int64_t wh = (int64_t)y1 - y0;
     if (f.geom_filter.active)
         return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry (unfiltered) and frr_raster before frr_resolve_varyings");
     if (!buf || ((uintptr_t)buf & 3u)) return fail(c, FRR_ERR_INVALID, "output buffer is NULL or not 4-byte aligned");
@@ -2479,6 +2563,68 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     if (rc != FRR_OK) return rc;
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy varyings: ") + hipGetErrorString(e));
     return FRR_OK;
+}
+
+// argument checks of frr_visible_pixels / frr_visible_pixels_host
+static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
+{
+    if (!c) return FRR_ERR_INVALID;
+    const FrameState &f = c->fs;
+    if (unit != FRR_PER_ITEM && unit != FRR_PER_TRIANGLE) return fail(c, FRR_ERR_INVALID, "unknown frr_visible_unit");
+    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
+    { const int rcw = entry_window_check(c, x0, x1, y0, y1); if (rcw != FRR_OK) return rcw; }
+    if (f.geom_filter.active)
+        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; use frr_geometry* + frr_raster before frr_visible_pixels");
+    if (out_entries > 0 && (!buf || ((uintptr_t)buf & 3u))) return fail(c, FRR_ERR_INVALID, "output buffer is NULL or not 4-byte aligned");
+    return FRR_OK;
+}
+static Cmd visible_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
+{
+    Cmd cmd;
+    cmd.kind = Cmd::VISIBLE; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.duni = c->duni;
+    cmd.vis_unit = unit; cmd.vis_out = dev_out; cmd.vis_entries = out_entries;
+    return cmd;
+}
+
+int frr_visible_pixels(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_u32, uint64_t out_entries)
+{
+    const int rc = visible_check(c, unit, x0, x1, y0, y1, dev_out_u32, out_entries);
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return exec_cmd(c, visible_cmd(c, unit, x0, x1, y0, y1, (uint32_t *)dev_out_u32, out_entries));
+}
+
+int frr_visible_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *host_out, uint64_t out_entries, uint64_t *nunits)
+{
+    int rc = visible_check(c, unit, x0, x1, y0, y1, host_out, out_entries);
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint32_t> tmp;
+    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
+    rc = exec_cmd(c, visible_cmd(c, unit, x0, x1, y0, y1, tmp, out_entries));
+    const int rf = finish(c);   // synchronisation point (and, if a list was too small, the replay -- the command included); the log is empty afterwards
+    if (rc == FRR_OK) rc = rf;
+    hipError_t e = hipSuccess;
+    if (rc == FRR_OK) e = hipMemcpy(host_out, tmp, (size_t)out_entries * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    // (a finish() that failed may have left the command in the log: nothing may replay it into the freed buffer)
+    for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == Cmd::VISIBLE && c->log[k].vis_out == tmp) c->log.erase(c->log.begin() + (ptrdiff_t)k);
+    if (rc != FRR_OK) return rc;
+    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy counts: ") + hipGetErrorString(e));
+    if (nunits) {
+        const FrameState &f = c->fs;
+        const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
+        *nunits = unit == FRR_PER_ITEM ? f.geom_nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom_ntris ? gt.n_emit : 0u);
+    }
+    return FRR_OK;
+}
+
+int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                                const uint32_t *bounds, uint64_t nunits, uint32_t *out, uint64_t out_entries)
+{
+    if (!ids || (out_entries && !out) || x0 < 0 || x1 <= x0 || y1 <= y0 || nunits > 0xFFFFFFFFull) return -1;
+    if ((uint64_t)((int64_t)y1 - y0 - 1) * (uint64_t)x1 + (uint64_t)((int64_t)x1 - x0) > id_entries) return -1;   // the last entry the window reads
+    if (bounds) for (uint64_t k = 0; k < nunits; ++k) if (bounds[k] > bounds[k + 1]) return -1;
+    return (int64_t)visible_counts_host(ids, x0, x1, y0, y1, bounds, nunits, out, out_entries);
 }
 
 // argument checks of frr_shade_varyings / frr_shade_varyings_host; *nothing: the call is valid and writes nothing

@@ -841,13 +841,19 @@ __global__ __launch_bounds__(256) void k_instance_mvp(const float *__restrict__ 
 // frr_geometry_item_ranges: out[i], i in 0..nitems, = the emission index within the pass of the first input of item i (a
 // list pass: item_first; else the items are `stride` inputs each) -- from the pass's own tables, as the tile kernel's
 // resolve numbers a triangle -- and out[nitems] = n_emit.  An item that starts behind the last input starts there as well.
+// (item_first_emission: one boundary, i <= nitems; k_visible_prep builds the same table on the device, from the device's n_emit)
+__device__ __forceinline__ uint32_t item_first_emission(const uint32_t *item_first, uint32_t stride, uint32_t nitems, uint32_t ntris,
+                                                        const uint32_t *tinfo, const uint32_t *block_prefix, uint32_t n_emit, uint32_t i)
+{
+    const unsigned long long f = i == nitems ? ntris : item_first ? item_first[i] : (unsigned long long)i * stride;
+    return f >= ntris ? n_emit : block_prefix[(uint32_t)f / GEOM_BLOCK] + (tinfo[(uint32_t)f] >> FAN_BITS);
+}
 __global__ __launch_bounds__(256) void k_item_firsts(const uint32_t *__restrict__ item_first, uint32_t stride, uint32_t nitems, uint32_t ntris,
                                                      const uint32_t *__restrict__ tinfo, const uint32_t *__restrict__ block_prefix, uint32_t n_emit, uint32_t *__restrict__ out)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i > nitems) return;
-    const unsigned long long f = i == nitems ? ntris : item_first ? item_first[i] : (unsigned long long)i * stride;
-    out[i] = f >= ntris ? n_emit : block_prefix[(uint32_t)f / GEOM_BLOCK] + (tinfo[(uint32_t)f] >> FAN_BITS);
+    out[i] = item_first_emission(item_first, stride, nitems, ntris, tinfo, block_prefix, n_emit, i);
 }
 
 // An empty mesh launches no geometry kernel proper: the per-draw bookkeeping alone.

@@ -481,6 +481,27 @@ public:
     {
         return first.size() == ntris.size() ? frr_host_list_item(first.data(), ntris.data(), first.size(), t) : -1;
     }
+    // How many entries of the window each unit owns in the triangle-id target (include/frr.h: frr_visible_pixels): FRR_PER_ITEM,
+    // the items of the latest geometry pass as item_ranges reports them, or FRR_PER_TRIANGLE, the triangle ids of the frame so
+    // far -- which objects of a list ended up on screen, with no read-back of the frame.  Device memory of `entries` u32, every
+    // one written; a command on the frame's stream, no host wait: order the reads with frame_fence on a created stream or with
+    // sync, and keep the buffer until then.
+    void visible_pixels(int unit, void *dev_out_u32, uint64_t entries, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        check(frr_visible_pixels(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, dev_out_u32, entries));
+    }
+    void visible_pixels(int unit, void *dev_out_u32, uint64_t entries) { visible_pixels(unit, dev_out_u32, entries, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // the same on the host (a synchronisation point): the counts of all n units
+    std::vector<uint32_t> visible_pixels(int unit, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        uint64_t n = 0;
+        uint32_t probe = 0;   // (one entry is enough to ask for n)
+        check(frr_visible_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, &probe, 1, &n));
+        std::vector<uint32_t> out((size_t)n, probe);
+        if (n > 1) check(frr_visible_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, out.data(), n, &n));
+        return out;
+    }
+    std::vector<uint32_t> visible_pixels(int unit) { return visible_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream
     // waits for every frame issued so far; frame_wait -- the next write of the frame targets waits for what the stream holds now

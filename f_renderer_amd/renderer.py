@@ -202,6 +202,24 @@ def host_list_item(first, ntris, t):
     return int(N.lib().frr_host_list_item(f.ctypes.data, n.ctypes.data, f.size, int(t)))
 
 
+def host_visible_counts(ids, width_range, height_range, bounds=None, units=None, entries=None):
+    """The counts of frr_visible_pixels over a host id array, by the host build of the kernel's span logic
+    (frr_host_visible_counts): `ids` uint32, entry (cy - y0) * x1 + (cx - x0).  bounds: the nitems + 1 item boundaries
+    (first ids, then the end of the last) for per-item counts; None: per triangle over the ids 0 .. units.  Returns
+    (counts uint32 [entries, default: the number of units], adds: the run heads that counted)."""
+    a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    b = None if bounds is None else np.ascontiguousarray(bounds, np.uint32).reshape(-1)
+    if b is not None and b.size < 1:
+        raise FrrError(N.FRR_ERR_INVALID, "host_visible_counts: nitems + 1 boundaries")
+    n = b.size - 1 if b is not None else int(units)
+    out = np.empty(n if entries is None else int(entries), np.uint32)
+    adds = N.lib().frr_host_visible_counts(a.ctypes.data, a.size, int(width_range[0]), int(width_range[1]), int(height_range[0]), int(height_range[1]),
+                                           None if b is None else b.ctypes.data, n, out.ctypes.data if out.size else None, out.size)
+    if adds < 0:
+        raise FrrError(N.FRR_ERR_INVALID, "host_visible_counts: bad window, array or boundaries")
+    return out, int(adds)
+
+
 def host_instance_mvp(proj, view, model):
     """(proj * view) * model as the device computes it per instance (frr_host_instance_mvp): float32 [16], column-major."""
     p, v, m = (np.ascontiguousarray(x, np.float32).reshape(16) for x in (proj, view, model))
@@ -596,6 +614,35 @@ class Renderer:
         self._check(fn(self._ctx, int(pixel_shader), int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), C.c_void_p(ptr), int(entries), int(K),
                        int(ids[0]) & 0xFFFFFFFF, int(ids[1]) & 0xFFFFFFFF))
 
+    def visible_pixels(self, unit="item", out_ptr=None, entries=None, width_range=None, height_range=None):
+        """How many entries of the window each unit owns in the triangle-id target (frr_visible_pixels): unit="item", the
+        items of the latest geometry pass as item_ranges() reports them, or "triangle", the triangle ids of the frame so far.
+        With `out_ptr` -- device memory of `entries` uint32, e.g. a torch int32 / uint32 tensor's data_ptr() -- it is a
+        command on the frame's stream with no host wait and returns nothing: every entry is written, units at and beyond
+        `entries` are counted nowhere; order the reads with frame_fence(a created stream) or sync(), and keep the buffer
+        until then.  Without `out_ptr` it is the host form (a synchronisation point) and returns a uint32 array of the n
+        counts, or of `entries` of them."""
+        u = {"item": N.PER_ITEM, "triangle": N.PER_TRIANGLE}.get(unit, unit)
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        win = (int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]))
+        if out_ptr is not None:
+            if entries is None:
+                raise FrrError(N.FRR_ERR_INVALID, "visible_pixels: the device form needs the buffer's entries")
+            self._check(self._lib.frr_visible_pixels(self._ctx, int(u), *win, C.c_void_p(out_ptr), int(entries)))
+            return None
+        n = C.c_uint64()
+        if entries is None:   # n first (one entry is enough to ask), then the counts
+            probe = np.zeros(1, np.uint32)
+            self._check(self._lib.frr_visible_pixels_host(self._ctx, int(u), *win, probe.ctypes.data, 1, C.byref(n)))
+            entries = int(n.value)
+            if entries <= 1:
+                return probe[:entries]
+        out = np.zeros(int(entries), np.uint32)
+        if out.size:
+            self._check(self._lib.frr_visible_pixels_host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
     def frame_fence(self, stream=None):
         """`stream` (a hipStream_t handle, e.g. torch's stream.cuda_stream; None = the ctx's stream) waits for every frame
         issued so far -- no host wait (frr_frame_fence; option bound_targets_in_flight)."""
@@ -650,10 +697,13 @@ class Renderer:
     KERNELS = ("k_clear", "k_geom", "k_geom_scan", "k_bin_count",
                "k_tile_scan", "k_bin_fill", "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint")
 
+    # the order of the profile's mask bits: KERNELS, the kernels of a frame, then what was appended since
+    PROFILE_ORDER = KERNELS + ("k_visible",)
+
     def profile_enable(self, on=True, kernels=None, period=1):
         """Bracket launches with HIP events: all kernels (on=True), none (False) or the named ones; only every
         `period`-th launch of each (an event pair costs the stream ~4 us)."""
-        mask = (-1 if on else 0) if kernels is None else sum(1 << self.KERNELS.index(k) for k in kernels)
+        mask = (-1 if on else 0) if kernels is None else sum(1 << self.PROFILE_ORDER.index(k) for k in kernels)
         self._check(self._lib.frr_profile_set_period(self._ctx, period))
         self._check(self._lib.frr_profile_enable(self._ctx, mask))
 

@@ -536,6 +536,52 @@ int frr_shade_varyings_host(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int
                             const float *host_in, uint64_t in_entries, int K,
                             uint32_t id_first, uint32_t id_count);
 
+/* ---- visible pixel counts --------------------------------------------------------------------- */
+/* Which objects of a pass ended up on screen, and with how many pixels, without reading the frame back: the triangle-id
+ * target of a window as counts, on the device.  (The reference has no such query; every renderer with a batched draw has:
+ * occlusion queries, picking, choosing a level of detail, visible-triangle sets for baking.)
+ *   window  (x0, x1) x (y0, y1), addressed as everywhere else: pixel (cx, cy) has the depth index
+ *           i = (cy - y0) * x1 + (cx - x0) (renderer.rs:362).  The entries of the window are those i with
+ *           0 <= cx - x0 < x1 - x0 and 0 <= cy - y0 < y1 - y0.
+ *   id      id[i]: the current frame's triangle-id target at the command's place in the stream.
+ * FRR_PER_ITEM      The units are the items of the LATEST geometry pass, exactly the ones frr_geometry_item_ranges reports:
+ *                   the items of a list pass, the instances of an instanced pass, one item for a plain pass.  out[k] = the
+ *                   number of window entries with id[i] != 0xFFFFFFFF and id[i] - id_first[k] < id_count[k] (unsigned), with
+ *                   id_first and id_count as frr_geometry_item_ranges would return them.  Pixels owned by earlier passes of
+ *                   the frame count for nobody.
+ * FRR_PER_TRIANGLE  The units are the frame-global emission indices 0 .. T, T = the frame's running triangle count behind
+ *                   the latest geometry pass (its first id plus what it emitted).  out[t] = the number of window entries with
+ *                   id[i] == t.  This covers every pass of the frame so far: a caller who wants per-item counts over several
+ *                   passes sums the ranges it got from frr_geometry_item_ranges after each pass.
+ * With n units, EVERY one of the out_entries entries is written: unit k < min(n, out_entries) gets its count, entries at and
+ * beyond n get 0; a unit >= out_entries is counted nowhere.  Colour, depth, ids and every field of frr_stats are untouched.
+ * The counts are sums of integers: two runs give the same bytes.
+ * After a frr_clear since the geometry pass the id target holds nothing of it: FRR_OK, all zeros; n is still the pass's item
+ * count for FRR_PER_ITEM, and 0 for FRR_PER_TRIANGLE.  An empty list, an empty mesh, ninst == 0 and items that emit nothing
+ * are valid and count 0.
+ * frr_visible_pixels: dev_out_u32 is device memory, 4-byte aligned, of out_entries u32.  It is a command like
+ * frr_resolve_varyings: it runs on the current frame's stream behind the draws issued so far and before those issued after
+ * it -- a later draw that occludes an item does not change a count queued before it --, settles a pending frr_clear first,
+ * reads the current target set (own or caller-bound, one or two frames in flight) and the pass's tables on the device, and
+ * waits for nothing on the host.  The caller orders its reads of dev_out_u32 with frr_frame_fence (on a created stream, see
+ * frr_resolve_varyings) or frr_sync.  It is logged and replayed: behind a command that found a work list too small it writes
+ * nothing, not even the zeros, and is replayed with that command -- so dev_out_u32 stays allocated until the next
+ * synchronisation point or frr_clear.
+ * On a partitioned ctx only entries in tile rows this rank owns are counted, so the ranks' counts add up to the unpartitioned
+ * ones; after a frr_draw* that filtered the setup list the call fails with FRR_ERR_INVALID, where
+ * frr_geometry_item_ranges fails.
+ * frr_visible_pixels_host: the same through a temporary device buffer into host memory; a synchronisation point.  *nunits
+ * (optional) receives n.
+ * Errors.  The window rules of frr_resolve_varyings: FRR_ERR_UNSUPPORTED for x0 < 0; FRR_ERR_INVALID for x1 <= x0, y1 <= y0, a
+ * window larger than the FrameBuffer, coordinates outside the i16 range, a depth index that leaves the buffer.
+ * FRR_ERR_INVALID also: an unknown unit, a NULL or not 4-byte-aligned buffer with out_entries > 0, a call before any geometry
+ * pass.  out_entries == 0 (after these checks): FRR_OK, and nothing happens (*nunits is not written either). */
+typedef enum frr_visible_unit { FRR_PER_ITEM = 0, FRR_PER_TRIANGLE = 1 } frr_visible_unit;
+int frr_visible_pixels(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                       void *dev_out_u32, uint64_t out_entries);
+int frr_visible_pixels_host(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                            uint32_t *host_out, uint64_t out_entries, uint64_t *nunits);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to
@@ -605,6 +651,10 @@ int frr_event_elapsed_ms(frr_ctx *ctx, int a, int b, float *ms);
  *                             line kernels (0 = default 2^24, the bound that keeps a wavefront's prefix sums in 32 bits).  Only a
  *                             segment nearly as long as a 2^24-pixel buffer takes a second round at the default; a small value
  *                             lets the tests walk that path on a 96 x 70 frame
+ *   "visible_lds_bins"        a test hook like lines_chunk: v > 0: a frr_visible_pixels whose histogram can meet more than v units (the
+ *                             pass's items, or out_entries if that is fewer; per triangle: out_entries) adds to global memory
+ *                             directly instead of through the LDS histogram; 0 = default, the 4,096 units the LDS path takes.
+ *                             The small test frames can then walk both paths
  *   "tile_order"              which workgroup of the tile kernel takes which tile (segmented binning): 0 (default) the fixed order
  *                             by position; 1 heaviest first -- each XCD's run of neighbouring tiles by descending records in the
  *                             latest pass over the same grid on the same workspace (the fixed order on a first pass, after a new
@@ -614,7 +664,8 @@ int frr_set_option(frr_ctx *ctx, const char *name, int64_t value);
 /* per-kernel accumulated device time (ms) and launch count since frr_profile_reset.  `mask`:
  * 0 = off, -1 = every kernel, else OR of (1 << index) with index in the order k_clear,
  * k_geom, k_geom_scan, k_bin_count, k_tile_scan, k_bin_fill, k_raster,
- * k_bin_seg, k_lines_mark, k_lines_paint (k_geom covers the clip kernel too when the clip queue is in use, and the kernel that fills an instanced pass's matrices).  A profiled launch is bracketed by two
+ * k_bin_seg, k_lines_mark, k_lines_paint, k_visible (k_visible covers the launch that zeroes the counts and builds the item
+ * boundaries too; k_geom covers the clip kernel too when the clip queue is in use, and the kernel that fills an instanced pass's matrices).  A profiled launch is bracketed by two
  * HIP events on the ctx stream. */
 int frr_profile_enable(frr_ctx *ctx, int mask);
 /* bracket only every `period`-th launch of each selected kernel (default 1): an event pair costs the
@@ -645,6 +696,14 @@ void frr_host_instance_mvp(const float proj[16], const float view[16], const flo
 /* host build of the device's item search of a list pass (cf. frr_host_line_pixels): the item i with
  * first[i] <= t < first[i] + ntris[i], or -1; first is the exclusive prefix of ntris (it repeats where items are empty) */
 int64_t frr_host_list_item(const uint32_t *first, const uint32_t *ntris, uint64_t nitems, uint32_t t);
+/* host build of the span logic of frr_visible_pixels (cf. frr_host_list_item): the unit search, the run heads and the run
+ * lengths, span by span and lane by lane as the kernel takes them, over an id array of id_entries u32 and a window
+ * (x0 >= 0; the window's last index (y1 - y0 - 1) * x1 + (x1 - x0) - 1 lies inside the array).  bounds: the nunits + 1
+ * non-decreasing boundaries of the items (the ids of item k are [bounds[k], bounds[k + 1])), or NULL: per triangle, the units
+ * are the ids 0 .. nunits.  Every one of the out_entries entries of out is written, as by frr_visible_pixels.  Returns the
+ * number of adds -- run heads that counted for a unit --, or -1 for a bad argument. */
+int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                                const uint32_t *bounds, uint64_t nunits, uint32_t *out, uint64_t out_entries);
 /* host build of the device's facing determinant (frr_set_cull; cf. frr_host_atan2f): d of the three clip positions
  * clip[0..3], clip[4..7], clip[8..11] (x, y, z, w each) */
 float frr_host_cull_det(const float clip[12]);

@@ -107,6 +107,9 @@ pub mod ffi {
         pub fn frr_geometry_list(ctx: *mut frr_ctx, list: c_int, ntris_setup: *mut u64) -> c_int;
         pub fn frr_draw_list(ctx: *mut frr_ctx, list: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
         pub fn frr_geometry_item_ranges(ctx: *mut frr_ctx, id_first: *mut u32, id_count: *mut u32, cap: u64, nitems: *mut u64) -> c_int;
+        // unit: 0 = FRR_PER_ITEM, 1 = FRR_PER_TRIANGLE
+        pub fn frr_visible_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
+        pub fn frr_visible_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
         pub fn frr_host_list_item(first: *const u32, ntris: *const u32, nitems: u64, t: u32) -> i64;
         // face culling of the geometry passes issued from now on (0 none, 1 drop d < 0, 2 drop d > 0): set beside the uniforms
         pub fn frr_set_cull(ctx: *mut frr_ctx, mode: c_int) -> c_int;
@@ -205,6 +208,24 @@ impl Renderer {
         }
         let message = unsafe { CStr::from_ptr(ffi::frr_last_error(self.ctx)) }.to_string_lossy().into_owned();
         Err(Error { code: rc, message })
+    }
+
+    /// frr_visible_pixels_host: how many entries of the window each unit owns in the triangle-id target -- the items of the latest
+    /// geometry pass (`per_triangle = false`) or the triangle ids of the frame so far -- with no read-back of the frame.  Every
+    /// entry of `out` is written; returns the number of units n.  A synchronisation point.
+    pub fn visible_pixels(&mut self, per_triangle: bool, width_range: (i32, i32), height_range: (i32, i32), out: &mut [u32]) -> Result<u64, Error> {
+        let mut n = 0u64;
+        self.check(unsafe {
+            ffi::frr_visible_pixels_host(self.ctx, per_triangle as c_int, width_range.0, width_range.1, height_range.0, height_range.1,
+                                         out.as_mut_ptr(), out.len() as u64, &mut n)
+        })?;
+        Ok(n)
+    }
+    /// frr_visible_pixels: the same into device memory, as a command on the frame's stream with no host wait.
+    /// # Safety
+    /// `dev_out` is device memory of `entries` u32 that stays allocated until the next synchronisation point or `clear`.
+    pub unsafe fn visible_pixels_device(&mut self, per_triangle: bool, width_range: (i32, i32), height_range: (i32, i32), dev_out: *mut c_void, entries: u64) -> Result<(), Error> {
+        self.check(ffi::frr_visible_pixels(self.ctx, per_triangle as c_int, width_range.0, width_range.1, height_range.0, height_range.1, dev_out, entries))
     }
 
     /// `Vec<[VSInput;3]>` (phong.rs:187-205) -> device
