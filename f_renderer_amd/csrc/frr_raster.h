@@ -614,6 +614,7 @@ template <int NW, int B> struct SpanLds {
     static constexpr int bytes(bool textured) { return U8 + (textured ? 256 * 4 : 0); }
     static_assert(B <= 32, "staging slots are five bits of a span descriptor, first rows ten bits of SpanTri::misc");
     static_assert(U1 - U0 >= TILE_PX * 4, "the NaN pass keeps one u32 per pixel in the staging region");
+    static_assert(HZ % 16 == 0 && HZ_QUAD % 4 == 0, "the four quad minima are read as one uint4");
     // The typed view of it: what lies where in the kernel's buffer `lds` (per-wave arrays: [wave][slot]).  The pointers are formed
     // where a phase uses them: held in a struct they would reach the phases through memory, and the code generated changes.
     template <class T> static __device__ __forceinline__ T *at(unsigned char *lds, int off) { return reinterpret_cast<T *>(lds + off); }
@@ -639,7 +640,7 @@ template <int NW, int B> struct SpanLds {
     static __device__ __forceinline__ float *u8(unsigned char *lds) { return at<float>(lds, U8); }                     // (float)i / 255.0f for the texture taps of the resolve
 };
 // FRR_DEBUG_COUNTERS builds (tools/debug_counters.py, tools/tile_timeline.py): the funnel counters, the wave-cycles per
-// phase and the workgroup's timeline, added to Counters::dbg (slots 0..10, 12..19, 20) and written to RasterArgs::dbg_tiles.
+// phase and the workgroup's timeline, added to Counters::dbg (slots 0..11, 12..19, 20) and written to RasterArgs::dbg_tiles.
 // Every other build gets the empty twin below: the kernel calls the same methods and nothing is left of them.
 #ifdef FRR_DEBUG_COUNTERS
 struct SpanDbg {
@@ -651,6 +652,11 @@ struct SpanDbg {
     uint32_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t tri = 0, alive = 0, rows = 0, spans = 0, spans_live = 0, frags = 0, fwin = 0, rwin = 0;
     uint32_t pre = 0, win = 0, rebuilds = 0; // fragments a per-pixel zub test would skip; fragments that took the pixel; hi-z rebuilds
+    // cull steps of a heavy tile that no wave fetched (the early exit of step 1): wave 0 puts in the tile's steps, every wave takes out
+    // the ones it ran -- summed over the tile's waves (they share a copy of Counters::dbg) that is the steps left, once per tile
+    int32_t notf = 0;
+    __device__ __forceinline__ void heavy_tile(uint32_t nent, int cull, int w) { if (w == 0) notf += (int32_t)((nent + (uint32_t)cull - 1u) / (uint32_t)cull); }
+    __device__ __forceinline__ void step_fetched() { --notf; }
     __device__ __forceinline__ void T(int i) { const unsigned long long now = __builtin_amdgcn_s_memtime(); t[i] += (uint32_t)(now - tlast); tlast = now; }
     __device__ __forceinline__ void main_loop_begins() { rt1 = __builtin_amdgcn_s_memrealtime(); }
     __device__ __forceinline__ void rebuilt() { ++rebuilds; }
@@ -671,6 +677,7 @@ struct SpanDbg {
         const uint32_t v[11] = {tri, alive, rows, spans, spans_live, frags, fwin, rwin, pre, win, rebuilds};
 #pragma unroll
         for (int i = 0; i < 11; ++i) atomicAdd(d + i, (unsigned long long)v[i]);
+        if (notf != 0) atomicAdd(d + 11, (unsigned long long)(long long)notf);   // (wraps; the sum over a tile's waves is >= 0)
     }
     __device__ __forceinline__ void kernel_ends(const RasterArgs &a, const TileCtx &c, int lane, int w)
     {
@@ -692,6 +699,8 @@ struct SpanDbg {
 };
 #else
 struct SpanDbg {
+    __device__ __forceinline__ void heavy_tile(uint32_t, int, int) {}
+    __device__ __forceinline__ void step_fetched() {}
     __device__ __forceinline__ void T(int) {}
     __device__ __forceinline__ void main_loop_begins() {}
     __device__ __forceinline__ void rebuilt() {}
@@ -756,13 +765,37 @@ __device__ __forceinline__ DirectRecs span_order_direct(const RasterArgs &a, con
     return d;
 }
 // More records: copied in that order into the tile's own range [c.beg, c.beg + nent) of `ents` (bins2).
-template <bool COUNT, class L>
-__device__ __forceinline__ void span_order_bins2(const RasterArgs &a, const TileCtx &c, unsigned char *lds, uint4 *ents, uint32_t nent, int lane, int w)
+//
+// The same walk prepares the main loop's early exit (draws that do not count fragments): cull step g of the main loop takes the records
+// at sorted positions [g CULL, (g + 1) CULL), and the loop may stop at the first step from which on EVERY record's depth bound lies below
+// the smallest depth in the tile -- none of them could change a pixel.  So each record's bound is folded into the maximum of its step
+// (steps from 63 on share the last one), in 64 words of the pre-pass half of the union that this path does not use otherwise (the
+// exchange buffer), and wave 0 leaves the SUFFIX maxima -- entry g: the largest bound at any step >= g -- in the bucket counters, which
+// are dead once the records are scattered.  The real keys are folded, not the buckets (z_bucket sees six bits of the key and is not
+// monotone over all keys), so the exit is exact whatever the order.  A record that span_cull would never z-cull (outside the span
+// algebra's safe range, or any record when the window is: it is swept) counts as all-ones, like the records with NaN vertices (cull_zub).
+__device__ __forceinline__ uint32_t exit_bound(const uint4 &en, int win_safe)
+{
+    const int mnx = (int)(short)(en.z & 0xFFFFu), mny = (int)(short)(en.z >> 16);
+    const int mxx = (int)(short)(en.w & 0xFFFFu), mxy = (int)(short)(en.w >> 16);
+    const int amax = max(max(abs(mnx), abs(mxx)), max(abs(mny), abs(mxy)));
+    return win_safe && amax <= SPAN_SAFE ? en.y : 0xFFFFFFFFu;
+}
+template <bool COUNT, int CULL, class L>
+__device__ __forceinline__ void span_order_bins2(const RasterArgs &a, const TileCtx &c, unsigned char *lds, uint4 *ents, uint32_t nent, int lane, int w, int win_safe)
 {
     constexpr int NW = L::WAVES, B = L::BATCH;
+    static_assert(BKT_N >= 64 && DIRECT_MAX * 16 >= 64 * 4, "64 suffix maxima in the bucket counters, 64 step maxima in the exchange buffer");
     const TileSource source = {a, c, a.nseg != 0, L::segpre(lds), L::segsrc(lds)};
     const bool sorted = !COUNT && nent > 2u * B;
     auto bucket_of = [&](const uint4 &e) { return sorted ? z_bucket(e.y) : 0u; };
+    uint32_t *gmax = reinterpret_cast<uint32_t *>(L::exch(lds));
+    if (!COUNT && threadIdx.x < 64) gmax[threadIdx.x] = 0u;   // (two barriers before the first atomicMax below)
+    auto scatter = [&](const uint4 &en) {
+        const uint32_t pos = atomicAdd(&L::bkt(lds)[bucket_of(en)], 1u);
+        ents[pos] = en;
+        if (!COUNT) atomicMax(&gmax[min((pos - c.beg) / (uint32_t)CULL, 63u)], exit_bound(en, win_safe));
+    };
     uint4 ce[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -777,15 +810,21 @@ __device__ __forceinline__ void span_order_bins2(const RasterArgs &a, const Tile
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t e = threadIdx.x + (uint32_t)(NW * 64) * k;
-        if (e < nent) ents[atomicAdd(&L::bkt(lds)[bucket_of(ce[k])], 1u)] = ce[k];
+        if (e < nent) scatter(ce[k]);
     }
-    for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) {
-        const uint4 en = source(e);
-        ents[atomicAdd(&L::bkt(lds)[bucket_of(en)], 1u)] = en;
-    }
+    for (uint32_t e = threadIdx.x + 4u * NW * 64; e < nent; e += NW * 64) scatter(source(e));
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (!COUNT) {
+        if (w == 0) {
+            uint32_t v = gmax[lane];
+#pragma unroll
+            for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o = (uint32_t)__shfl_down((int)v, dd, 64); if (lane + dd < 64) v = max(v, o); }
+            L::bkt(lds)[lane] = v;
+        }
+        __syncthreads(); // the main loop reads the suffix maxima, and its staging overwrites the step maxima
+    }
 }
 
 // ---- step 1a, the cull half of one cull step: lane = bin entry `en` (where `valid`).  bbox-in-tile + whole-triangle early-z on
@@ -1000,26 +1039,27 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
     for (int i = threadIdx.x; i < HZ_SIZE; i += NW * 64) L::hz(lds)[i] = i >= HZ_C4 ? hz0 >> 1 : hz0;
     __syncthreads();
 
+    // bin entries culled per step: every survivor of a step gets a staging slot (<= B per wave), and its fragments are
+    // resolved before the next step culls (fresh z minima: the early-z of the later, farther records lives on them)
+    constexpr int CULL = SPAN_CULL < B ? SPAN_CULL : B;
     // ---- step 0b: near-first order, into registers (few records) or into the tile's range of bins2 ----
     uint4 *__restrict__ ents = a.bins2;
     const uint32_t nent = c.end - c.beg;
     const bool direct = nent <= (uint32_t)(DIRECT_MAX < NW * 64 ? DIRECT_MAX : NW * 64);
     DirectRecs d = {make_uint4(0, 0, 0, 0), false, 0, 0, 64};
     if (direct) d = span_order_direct<COUNT, L>(a, c, lds, nent, lane, w);                              // step 0b
-    else span_order_bins2<COUNT, L>(a, c, lds, ents, nent, lane, w);
+    else span_order_bins2<COUNT, CULL, L>(a, c, lds, ents, nent, lane, w, win_safe);
 
     __builtin_amdgcn_s_setprio(0);
     const uint32_t le_lo = lane < 32 ? (2u << lane) - 1u : 0xFFFFFFFFu;
     const uint32_t le_hi = lane < 32 ? 0u : (2u << (lane - 32)) - 1u;
     uint32_t n_cov = 0, n_nan = 0;
 
-    // bin entries culled per step: every survivor of a step gets a staging slot (<= B per wave), and its fragments are
-    // resolved before the next step culls (fresh z minima: the early-z of the later, farther records lives on them)
-    constexpr int CULL = SPAN_CULL < B ? SPAN_CULL : B;
     if (direct) { // (B can be smaller than half a wave)
         const int nsteps = max(DIRECT_STEPS, (d.count + B - 1) / B);
         d.step = max(min(DIRECT_MIN, B), (d.count + nsteps - 1) / nsteps);
     }
+    if (!COUNT && !direct) dbg.heavy_tile(nent, CULL, w);
     dbg.T(0);
     dbg.main_loop_begins();
     for (;;) {
@@ -1036,6 +1076,16 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_raster_span(RasterArgs a, DevU
             b = __builtin_amdgcn_readfirstlane(b);
             e0 = c.beg + b * (uint32_t)CULL;
             if (e0 >= c.end) break;
+            if constexpr (!COUNT) {
+                // the early exit (span_order_bins2): every record of this and all later steps has its bound below the smallest depth of
+                // the tile, so span_cull would reject each one -- the other waves leave at their next fetch by the same test.  (The minimum
+                // may be read stale: a stale one is lower.  Pixels of a partial tile beyond the window hold all-ones keys and do not lower it.)
+                const uint4 qm = *reinterpret_cast<const uint4 *>(&L::hz(lds)[HZ_QUAD]);
+                const uint32_t tmin = __builtin_amdgcn_readfirstlane(min(min(qm.x, qm.y), min(qm.z, qm.w)));
+                const uint32_t rest = __builtin_amdgcn_readfirstlane(L::bkt(lds)[min(b, 63u)]);
+                if (rest < tmin) break;
+                dbg.step_fetched();
+            }
         }
         // the minima are rebuilt only if some wave has resolved fragments since the last rebuild
         // (a stale minimum is a lower one: still conservative)

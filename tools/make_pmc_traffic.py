@@ -52,7 +52,7 @@ def main():
     fetch, write = mean_counter(fd, "FETCH_SIZE"), mean_counter(wd, "WRITE_SIZE")
     res = json.load(open(out)) if os.path.exists(out) else {}
     entry = {"_source_sha": source_sha()}
-    calib = [v for k, v in fetch.items() if "k_geom_single<0>" in k or "k_geom_single<(int)0>" in k]
+    calib = [v for k, v in fetch.items() if "k_geom_single<0>" in k or "k_geom_single<(int)0>" in k or "k_geom_single<0, false, false, false>" in k]
     if calib and "1M" in workload:
         entry["_calibration"] = {"kernel": "k_geom_single<0>", "fetch_size_kib": calib[0], "true_bytes": 48_000_000,
                                  "ratio": calib[0] * 1024 / 48_000_000}

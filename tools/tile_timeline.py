@@ -47,6 +47,10 @@ print("  main loop      ", q(main1 - main0))
 print("  barrier+resolve", q(end - main1))
 print("records per tile ", q(nent))
 print("corr(duration, records) = %.3f" % np.corrcoef(end - start, nent)[0, 1])
+# heavy tiles (more than 256 records: the near-first copy) and their cull steps of 32 records; the twelfth number of the `frr dbg:` line
+# below (slot 11, all frames since the last clear count) is the steps of them no wave fetched: the early exit of step 1
+heavy = nent[nent > 256]
+print(f"heavy tiles {len(heavy)}; their cull steps of 32 records: {int(((heavy + 31) // 32).sum())} per frame (set slot 11 of the dbg line against it)")
 edges = np.arange(0, end.max() + 5, 5.0)
 act = [(int(((start <= t) & (end > t)).sum())) for t in edges]
 print("active workgroups every 5 us:", act)
