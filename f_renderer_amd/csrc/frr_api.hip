@@ -2,6 +2,7 @@
 // frr_kernels.h.  gfx950 only; no CPU fallback (every compute entry point needs the device).
 #include "frr_kernels.h"
 #include "frr_tile_order.h"
+#include "frr_rules.h"
 #include "frr_lines.h"
 #include "frr_varyings.h"
 #include "frr_shade.h"
@@ -38,6 +39,7 @@ FRR_EMBED(frr_src_frr_h, "../../include/frr.h");
 extern "C" const char frr_src_device_h[], frr_src_exact_h[], frr_src_kernels_h[], frr_src_raster_h[], frr_src_shade_h[], frr_src_frr_h[];
 
 using namespace frr;
+static_assert(PASS_FAN_BITS == FAN_BITS && MAX_PASS_INPUTS << FAN_BITS == 1ull << PASS_ORDER_KEY_BITS, "frr_rules.h: an input's order keys are 32 * input + (0 .. 31), in 32 bits (frr_device.h)");
 
 namespace {
 
@@ -793,6 +795,23 @@ template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const Ra
     }
 }
 
+// `ts` (tstream_of) has been given work: a frame stream is dirty until fence_stream joins it
+void frame_stream_dirty(frr_ctx *c, hipStream_t ts)
+{
+    if (ts != c->stream) c->tstream[c->fs.tset].dirty = c->tstream[c->fs.tset].xdirty = true;
+}
+// which of the buffers kept per stream that can carry target work (frr_ctx::line_owner, vis_bounds) goes with `ts`
+int stream_slot(const frr_ctx *c, hipStream_t ts) { return ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2; }
+// the command has read the tables of the latest geometry pass on `ts`: the next pass in this lane, which zeroes the fan
+// cursors and may overwrite the workspace, waits for it (frr_ctx::wire_reader); finish() finds the tables it read in cmd
+void tables_read(frr_ctx *c, Cmd &cmd, hipStream_t ts)
+{
+    const FrameState &f = c->fs;
+    ReaderFence &wr = c->wire_reader[f.lane];
+    wr.pending = true; wr.stream = ts; wr.recorded = false;
+    cmd.par = f.gpar(); cmd.set = f.gset; cmd.lane = f.lane;
+}
+
 // Every launch that writes the frame targets goes on the stream this returns (*ts, the targets' stream).  The write follows
 // every stream of a pending frr_frame_wait, and its stream, if a frame stream, is dirty until fence_stream joins it.
 // `consume`: the write was issued after the latest frr_frame_wait (the one the waits are for), so later writes follow it
@@ -800,7 +819,7 @@ template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const Ra
 int target_write(frr_ctx *c, bool consume, hipStream_t *ts)
 {
     *ts = tstream_of(c);
-    if (*ts != c->stream) c->tstream[c->fs.tset].dirty = c->tstream[c->fs.tset].xdirty = true;
+    frame_stream_dirty(c, *ts);
     for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(*ts, w.ev, 0));
     if (consume) {
         for (frr_ctx::FrameWait &w : c->waits) c->wait_pool.push_back(std::move(w.ev));
@@ -1210,7 +1229,7 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
     if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
     // (a device-bound list needs no join of `ts` with the caller's stream: frr_lines_bind_device has waited on the host for
     // that stream, behind whatever wrote the list)
-    DevBuf<uint32_t> &owner = c->line_owner[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
+    DevBuf<uint32_t> &owner = c->line_owner[stream_slot(c, ts)];
     if (!owner) {
         const size_t npx = (size_t)c->W * c->H;
         if (owner.reset(npx) != hipSuccess) return nomem(c, "owner plane");
@@ -1234,12 +1253,7 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
         else hipLaunchKernelGGL(k_lines_paint<false>, grid, block, 0, ts, a);
     }
     HIP_TRY(c, hipGetLastError());
-    if (wire) {
-        ReaderFence &wr = c->wire_reader[f.lane];
-        wr.pending = true; wr.stream = ts; wr.recorded = false;
-        cmd.par = f.gpar(); cmd.set = f.gset;
-    }
-    cmd.lane = f.lane;
+    if (wire) tables_read(c, cmd, ts); else cmd.lane = f.lane;
     return FRR_OK;
 }
 
@@ -1261,7 +1275,7 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     hipStream_t ts = tstream_of(c);
     // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
-    if (ts != c->stream) c->tstream[f.tset].dirty = c->tstream[f.tset].xdirty = true;
+    frame_stream_dirty(c, ts);
     if (S.vslot_stream[par] && S.vslot_stream[par] != ts) {   // the table's previous resolve ran on another stream: after it
         HIP_TRY(c, hipEventRecord(c->ev_join, S.vslot_stream[par]));
         HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_join, 0));
@@ -1294,10 +1308,7 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     else if (vec) hipLaunchKernelGGL((k_vary_resolve<0, true>), grid, block, 0, ts, a);   // user shaders: K at run time
     else hipLaunchKernelGGL((k_vary_resolve<0, false>), grid, block, 0, ts, a);
     HIP_TRY(c, hipGetLastError());
-    // like a wireframe it reads the pass's fan cursors, which the next pass in this lane zeroes, and its workspace
-    ReaderFence &wr = c->wire_reader[f.lane];
-    wr.pending = true; wr.stream = ts; wr.recorded = false;
-    cmd.par = par; cmd.set = f.gset; cmd.lane = f.lane;
+    tables_read(c, cmd, ts);   // like a wireframe: the pass's fan cursors and its workspace
     return FRR_OK;
 }
 
@@ -1321,7 +1332,7 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     hipStream_t ts = tstream_of(c);
     // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
-    if (ts != c->stream) c->tstream[f.tset].dirty = c->tstream[f.tset].xdirty = true;
+    frame_stream_dirty(c, ts);
     // the units the histogram can meet: decides the path, and whether there is anything to count at all
     const uint64_t bound = cleared ? 0 : item ? std::min<uint64_t>(f.geom_nitems, cmd.vis_entries) : cmd.vis_entries;
     const GeomSet &S = c->gset[f.gset];
@@ -1333,7 +1344,7 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
     a.ntris = cleared ? 0u : (uint32_t)f.geom_ntris;
     a.tinfo = S.tinfo; a.block_prefix = S.block_prefix;
     if (item && bound > 0) {
-        DevBuf<uint32_t> &tab = c->vis_bounds[ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2];
+        DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
         if ((rc = ensure(c, tab, (size_t)f.geom_nitems + 1)) != FRR_OK) return rc;
         a.nitems = (uint32_t)f.geom_nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom_stride; a.bounds = tab;
     }
@@ -1363,10 +1374,7 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
         }
     }
     HIP_TRY(c, hipGetLastError());
-    // like a resolve it reads the pass's tables, which a later pass of this lane overwrites
-    ReaderFence &wr = c->wire_reader[f.lane];
-    wr.pending = true; wr.stream = ts; wr.recorded = false;
-    cmd.par = f.gpar(); cmd.set = f.gset; cmd.lane = f.lane;
+    tables_read(c, cmd, ts);   // like a resolve
     return FRR_OK;
 }
 
@@ -1535,6 +1543,58 @@ int finish(frr_ctx *c)
         HIP_TRY(c, hipMemcpy(&c->cnt.get()->first_bad, &none, sizeof none, hipMemcpyHostToDevice));
         c->next_seq = c->epoch = 1;
     }
+    return FRR_OK;
+}
+
+// ---- what the entry points share ------------------------------------------------------------------------------------
+// a rule of frr_rules.h, answered through the ctx
+int rule_rc(frr_ctx *c, const Rule &r) { return r.code == FRR_OK ? FRR_OK : fail(c, r.code, r.msg); }
+// pixel_shader_rule with the K a user pixel shader was registered with looked up
+int ps_check(frr_ctx *c, VaryingsFrom from, int ps_id, int K)
+{
+    const UserShader *us = ps_id >= FRR_SHADER_USER_BASE ? user_shader(ps_id) : nullptr;
+    return rule_rc(c, pixel_shader_rule(from, ps_id, K, us ? us->K : USER_K_UNKNOWN, c->duni.tex != nullptr));
+}
+// `who` needs the whole setup list of the latest geometry pass: a frr_draw* on a partitioned ctx keeps only the triangles
+// that touch the rank's tile rows of its window (frr_raster of that window and partition alone takes such a list: raster_check)
+int need_unfiltered_list(frr_ctx *c, const char *who)
+{
+    if (!c->fs.geom_filter.active) return FRR_OK;
+    return fail(c, FRR_ERR_INVALID, std::string("the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry* (unfiltered) and frr_raster before ") + who);
+}
+// the common part of a command: its kind, the uniforms and the cull mode at the time of the call, its window
+Cmd new_cmd(const frr_ctx *c, Cmd::Kind kind, int32_t x0 = 0, int32_t x1 = 0, int32_t y0 = 0, int32_t y1 = 0)
+{
+    Cmd cmd;
+    cmd.kind = kind; cmd.duni = c->duni; cmd.cull = c->cull;
+    cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1;
+    return cmd;
+}
+// the tail of frr_geometry*: a caller that wants the pass's emission count waits for it (a synchronisation point).  (A pass
+// without inputs launches k_geom_empty, whose geom_bookkeeping leaves n_emit = 0: the guard reads the same value.)
+int geometry_count(frr_ctx *c, uint64_t *ntris_setup)
+{
+    if (!ntris_setup) return FRR_OK;
+    const int rc = finish(c);
+    if (rc != FRR_OK) return rc;
+    *ntris_setup = c->fs.geom_ntris ? c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit : 0;
+    return FRR_OK;
+}
+// The host form of a command that writes a caller's buffer (`out`: which field of the command names it): the command runs
+// on the temporary device buffer `tmp`, the host waits -- a synchronisation point and, if a list was too small, the replay,
+// the command included; the log is empty afterwards -- and `bytes` of `tmp` come back to `host`.  A finish() that failed may
+// have left the command in the log: it is purged, so that nothing replays it into the freed buffer.
+template <typename T> int host_round_trip(frr_ctx *c, Cmd cmd, T *Cmd::*out, DevBuf<T> &tmp, T *host, size_t bytes, const char *what)
+{
+    cmd.*out = tmp;
+    int rc = exec_cmd(c, cmd);
+    const int rf = finish(c);
+    if (rc == FRR_OK) rc = rf;
+    hipError_t e = hipSuccess;
+    if (rc == FRR_OK) e = hipMemcpy(host, tmp, bytes, hipMemcpyDeviceToHost);
+    for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == cmd.kind && c->log[k].*out == tmp.get()) c->log.erase(c->log.begin() + (ptrdiff_t)k);
+    if (rc != FRR_OK) return rc;
+    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy ") + what + ": " + hipGetErrorString(e));
     return FRR_OK;
 }
 
@@ -1789,7 +1849,7 @@ static int mesh_register(frr_ctx *c, Mesh &&m, uint64_t ntris, int vs, int *mesh
 int frr_mesh_upload(frr_ctx *c, const float *vs_inputs, uint64_t ntris, int vs_id, int *mesh_out)
 {
     if (!c || !mesh_out || frr_vs_input_floats(vs_id) < 0 || (ntris && !vs_inputs)) return fail(c, FRR_ERR_INVALID, "bad mesh");
-    if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
+    if (ntris >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
     HIP_TRY(c, hipSetDevice(c->device));
     Mesh m;
     const int rc = upload(c, m.own_dev, vs_inputs, (size_t)ntris * 3 * frr_vs_input_floats(vs_id) * sizeof(float), "mesh");
@@ -1798,7 +1858,7 @@ int frr_mesh_upload(frr_ctx *c, const float *vs_inputs, uint64_t ntris, int vs_i
 int frr_mesh_bind_device(frr_ctx *c, const void *dev, uint64_t ntris, int vs_id, int *mesh_out)
 {
     if (!c || !mesh_out || frr_vs_input_floats(vs_id) < 0 || (ntris && !dev)) return fail(c, FRR_ERR_INVALID, "bad mesh");
-    if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
+    if (ntris >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
     if (((uintptr_t)dev & 15u) != 0) return fail(c, FRR_ERR_INVALID, "mesh pointer must be 16-byte aligned");
     c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
     Mesh m; m.dev = (const float *)dev;
@@ -1809,7 +1869,7 @@ static int indexed_args(frr_ctx *c, const void *verts, uint64_t nverts, const vo
 {
     if (!c || !mesh_out || frr_vs_input_floats(vs_id) < 0 || (nverts && !verts) || (ntris && !idx)) return fail(c, FRR_ERR_INVALID, "bad mesh");
     if (ntris && !nverts) return fail(c, FRR_ERR_INVALID, "indexed mesh: triangles but no vertices");
-    if (ntris >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
+    if (ntris >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^27 triangles per mesh (order keys: 32 per input triangle)");
     if (nverts > 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "more than 2^32 - 1 vertices per mesh (u32 indices)");
     return FRR_OK;
 }
@@ -1917,8 +1977,8 @@ int frr_draw_lines(frr_ctx *c, int lines)
     if (!c || !slot_ok(c->lines, lines)) return fail(c, FRR_ERR_INVALID, "bad line list id");
     if (c->lines[lines].n == 0) return FRR_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    Cmd cmd;
-    cmd.kind = Cmd::LINES; cmd.lines = lines; cmd.duni = c->duni;
+    Cmd cmd = new_cmd(c, Cmd::LINES);
+    cmd.lines = lines;
     return exec_cmd(c, cmd);
 }
 int frr_draw_wireframe(frr_ctx *c, const uint8_t rgba[4])
@@ -1926,14 +1986,13 @@ int frr_draw_wireframe(frr_ctx *c, const uint8_t rgba[4])
     if (!c || !rgba) return fail(c, FRR_ERR_INVALID, "bad arguments");
     const FrameState &f = c->fs;
     if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_draw_wireframe before frr_geometry");
-    if (f.geom_filter.active)
-        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry (unfiltered) before frr_draw_wireframe");
+    { const int rc = need_unfiltered_list(c, "frr_draw_wireframe"); if (rc != FRR_OK) return rc; }
     if (f.geom_ntris == 0) return FRR_OK;
     // (segment numbers + 1 are u32, and a wave's last batch of 64 must not wrap either)
     if (3ull * (f.geom_ntris + f.geom_fan_cap) + 64ull >= 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "wireframe: more than 2^32 / 3 setup slots (owner numbers are u32)");
     HIP_TRY(c, hipSetDevice(c->device));
-    Cmd cmd;
-    cmd.kind = Cmd::LINES; cmd.lines = -1; cmd.duni = c->duni;
+    Cmd cmd = new_cmd(c, Cmd::LINES);
+    cmd.lines = -1;
     memcpy(&cmd.wire_rgba, rgba, 4);
     return exec_cmd(c, cmd);
 }
@@ -2126,15 +2185,10 @@ int frr_geometry(frr_ctx *c, int mesh, uint64_t *ntris_setup)
 {
     if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     HIP_TRY(c, hipSetDevice(c->device));
-    Cmd cmd;
-    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni; cmd.cull = c->cull;
-    int rc = exec_cmd(c, cmd);
-    if (rc != FRR_OK) return rc;
-    if (ntris_setup) {
-        if ((rc = finish(c)) != FRR_OK) return rc;
-        *ntris_setup = c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit;
-    }
-    return FRR_OK;
+    Cmd cmd = new_cmd(c, Cmd::GEOM);
+    cmd.mesh = mesh;
+    const int rc = exec_cmd(c, cmd);
+    return rc != FRR_OK ? rc : geometry_count(c, ntris_setup);
 }
 
 // ---- instanced passes: one mesh under a table of model matrices (the loop over objects of phong.rs:319-331) ----------
@@ -2148,7 +2202,7 @@ static int instances_register(frr_ctx *c, Instances &&t, uint64_t ninst, int *in
 int frr_instances_upload(frr_ctx *c, const float *models, uint64_t ninst, int *inst_out)
 {
     if (!c || !inst_out || (ninst && !models)) return fail(c, FRR_ERR_INVALID, "bad instance table");
-    if (ninst >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
+    if (ninst >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
     HIP_TRY(c, hipSetDevice(c->device));
     Instances t;
     if (ninst) { const int rc = upload(c, t.own, models, (size_t)ninst * 16 * sizeof(float), "instance table"); if (rc != FRR_OK) return rc; }
@@ -2157,7 +2211,7 @@ int frr_instances_upload(frr_ctx *c, const float *models, uint64_t ninst, int *i
 int frr_instances_bind_device(frr_ctx *c, const void *dev_models, uint64_t ninst, int *inst_out)
 {
     if (!c || !inst_out || (ninst && !dev_models)) return fail(c, FRR_ERR_INVALID, "bad instance table");
-    if (ninst >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
+    if (ninst >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 instances or more (order keys: 32 per input triangle of a pass)");
     if (((uintptr_t)dev_models & 15u) != 0) return fail(c, FRR_ERR_INVALID, "instance table pointer must be 16-byte aligned");
     c->join_epoch += 1;    // the ctx's private streams have to see what the caller's stream wrote into that memory up to now
     Instances t; t.dev = (const float *)dev_models;
@@ -2176,10 +2230,11 @@ static int instanced_cmd(frr_ctx *c, int mesh, int inst, Cmd *cmd)
     if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     if (!slot_ok(c->instances, inst)) return fail(c, FRR_ERR_INVALID, "bad instance table id");
     const uint64_t ntris = c->meshes[mesh].ntris, ninst = c->instances[inst].n;
-    if (ntris && ninst && ntris * ninst >= (1ull << 27))   // (both factors are below 2^27: no wrap)
+    if (ntris && ninst && ntris * ninst >= MAX_PASS_INPUTS)   // (both factors are below 2^27: no wrap)
         return fail(c, FRR_ERR_UNSUPPORTED, "2^27 (instance, triangle) pairs or more in one pass (order keys: 32 per input triangle)");
     HIP_TRY(c, hipSetDevice(c->device));
-    cmd->kind = Cmd::GEOM; cmd->mesh = mesh; cmd->inst = inst; cmd->duni = c->duni; cmd->cull = c->cull;
+    *cmd = new_cmd(c, Cmd::GEOM);
+    cmd->mesh = mesh; cmd->inst = inst;
     h_mat4_mul(c->uni.proj, c->uni.view, cmd->pv);   // as refresh_dev_uniforms builds u.mvp
     return FRR_OK;
 }
@@ -2188,11 +2243,7 @@ int frr_geometry_instanced(frr_ctx *c, int mesh, int inst, uint64_t *ntris_setup
     Cmd cmd;
     int rc = instanced_cmd(c, mesh, inst, &cmd);
     if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
-    if (ntris_setup) {
-        if ((rc = finish(c)) != FRR_OK) return rc;
-        *ntris_setup = c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit;
-    }
-    return FRR_OK;
+    return geometry_count(c, ntris_setup);
 }
 void frr_host_instance_mvp(const float proj[16], const float view[16], const float model[16], float out[16])
 {
@@ -2205,7 +2256,7 @@ void frr_host_instance_mvp(const float proj[16], const float view[16], const flo
 int frr_drawlist_upload(frr_ctx *c, const frr_draw_item *items, uint64_t nitems, int *list_out)
 {
     if (!c || !list_out || (nitems && !items)) return fail(c, FRR_ERR_INVALID, "bad draw list");
-    if (nitems >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 items or more in one draw list");
+    if (nitems >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 items or more in one draw list");
     uint64_t total = 0;
     for (uint64_t i = 0; i < nitems; ++i) {
         const std::string who = "draw list: item " + std::to_string(i);
@@ -2215,7 +2266,7 @@ int frr_drawlist_upload(frr_ctx *c, const frr_draw_item *items, uint64_t nitems,
             return fail(c, FRR_ERR_INVALID, who + ": its mesh's vertex shader is not item 0's (one vertex shader per list)");
         total += c->meshes[items[i].mesh].ntris;   // (each below 2^27, fewer than 2^27 of them: no wrap)
     }
-    if (total >= (1ull << 27)) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 triangles or more in one draw list (order keys: 32 per input triangle of a pass)");
+    if (total >= MAX_PASS_INPUTS) return fail(c, FRR_ERR_UNSUPPORTED, "2^27 triangles or more in one draw list (order keys: 32 per input triangle of a pass)");
     HIP_TRY(c, hipSetDevice(c->device));
     DrawList l;
     std::vector<ListRow> rows(nitems);
@@ -2257,7 +2308,8 @@ static int list_cmd(frr_ctx *c, int list, Cmd *cmd)
     if (!c || !slot_ok(c->lists, list)) return fail(c, FRR_ERR_INVALID, "bad draw list id");
     if (c->lists[list].dead) return fail(c, FRR_ERR_INVALID, "a mesh the draw list names was freed: the list is dead (frr_drawlist_free still takes it)");
     HIP_TRY(c, hipSetDevice(c->device));
-    cmd->kind = Cmd::GEOM; cmd->list = list; cmd->list_gen = c->lists[list].gen; cmd->duni = c->duni; cmd->cull = c->cull;
+    *cmd = new_cmd(c, Cmd::GEOM);
+    cmd->list = list; cmd->list_gen = c->lists[list].gen;
     h_mat4_mul(c->uni.proj, c->uni.view, cmd->pv);   // as refresh_dev_uniforms builds u.mvp
     return FRR_OK;
 }
@@ -2266,17 +2318,12 @@ int frr_geometry_list(frr_ctx *c, int list, uint64_t *ntris_setup)
     Cmd cmd;
     int rc = list_cmd(c, list, &cmd);
     if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
-    if (ntris_setup) {
-        if ((rc = finish(c)) != FRR_OK) return rc;
-        *ntris_setup = c->fs.geom_ntris ? c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit : 0;
-    }
-    return FRR_OK;
+    return geometry_count(c, ntris_setup);
 }
 int frr_geometry_item_ranges(frr_ctx *c, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems)
 {
     if (!c || !nitems || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry pass to take item ranges from");
-    if (c->fs.geom_filter.active)
-        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; use frr_geometry* + frr_raster for item ranges");
+    { const int rc = need_unfiltered_list(c, "frr_geometry_item_ranges"); if (rc != FRR_OK) return rc; }
     { int rcs = finish(c); if (rcs != FRR_OK) return rcs; }
     const FrameState &f = c->fs;
     const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
@@ -2315,22 +2362,10 @@ static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y
 {
     const FrameState &f = c->fs;
     if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_raster before frr_geometry");
-    if (x0 > x1 || y0 > y1) return fail(c, FRR_ERR_INVALID, "range min > max (i32::clamp would panic, renderer.rs:285)");
-    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
-    if (ww > (int64_t)c->W || wh > (int64_t)c->H) return fail(c, FRR_ERR_INVALID, "window larger than the FrameBuffer");
-    if (x0 < -32768 || y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_UNSUPPORTED, "window coordinates outside the i16 range");
-    if (ww > 0 && wh > 0 && (x1 <= 0 || (wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H))
-        return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
-    const int K = frr_vs_num_varyings(f.geom_vs);
-    if (ps_id >= FRR_SHADER_USER_BASE) {
-        // a user pixel shader: the mesh's vertex shader -- the same user shader, another one, or a built-in -- has to hand it
-        // the varyings it was registered with (the reference's two closures share one ShaderContext type, renderer.rs:97-110)
-        const UserShader *us = user_shader(ps_id);
-        if (!us) return fail(c, FRR_ERR_INVALID, "unknown shader id");
-        if (us->K != K) return fail(c, FRR_ERR_INVALID, "the user pixel shader's varyings do not match the vertex shader's");
-    } else if ((ps_id == FRR_PS_COLOR && K != 3) || ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && K != 8) || ps_id < 0 || ps_id > FRR_PS_BLINN)
-        return fail(c, FRR_ERR_INVALID, "pixel shader does not match the vertex shader's varyings");
-    if ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && !c->duni.tex) return fail(c, FRR_ERR_INVALID, "no texture bound to uniforms.texture_slot");
+    int rc = rule_rc(c, window_rule(WINDOW_RASTER, c->W, c->H, x0, x1, y0, y1));
+    // the mesh's vertex shader -- the same user shader, another one, or a built-in -- has to hand the pixel shader its varyings
+    if (rc == FRR_OK) rc = ps_check(c, K_OF_GEOMETRY, ps_id, frr_vs_num_varyings(f.geom_vs));
+    if (rc != FRR_OK) return rc;
     {
         // frr_draw on a partitioned ctx keeps only the triangles that touch the rank's tile rows of ITS window; that
         // list serves no other window or partition (the reference may reuse one geometry for several ranges,
@@ -2339,7 +2374,7 @@ static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y
         if (gf.active && (gf.y0 != y0 || gf.y1 != y1 || gf.rank != f.rank || gf.world != f.world || gf.blocked != f.part_blocked))
             return fail(c, FRR_ERR_INVALID, "the setup list was filtered by frr_draw for another window/partition; re-run frr_geometry (unfiltered) before frr_raster");
     }
-    *nothing = ww == 0 || wh == 0 || f.geom_ntris == 0;
+    *nothing = x0 == x1 || y0 == y1 || f.geom_ntris == 0;
     return FRR_OK;
 }
 
@@ -2350,45 +2385,43 @@ int frr_raster(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_
     const int rc = raster_check(c, ps_id, x0, x1, y0, y1, &nothing);
     if (rc != FRR_OK || nothing) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    Cmd cmd;
-    cmd.kind = Cmd::RASTER; cmd.ps = ps_id; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1;
-    cmd.count_frags = c->count_frags; cmd.duni = c->duni;
+    Cmd cmd = new_cmd(c, Cmd::RASTER, x0, x1, y0, y1);
+    cmd.ps = ps_id; cmd.count_frags = c->count_frags;
     return exec_cmd(c, cmd);
+}
+
+// frr_draw*: the geometry pass `cmd`, then frr_raster of its setup list.  The raster window is known here, so a partitioned
+// ctx can skip the setup records of triangles that touch none of its tile rows (frr_geometry* alone cannot: the window comes
+// later).  raster: false for a list without items -- no vertex shader either, so nothing a pixel shader could fail to match.
+static int draw_pass(frr_ctx *c, Cmd &cmd, bool raster, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
+{
+    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
+    const int rc = exec_cmd(c, cmd);
+    if (rc != FRR_OK || !raster) return rc;
+    return frr_raster(c, ps_id, x0, x1, y0, y1);
 }
 
 int frr_draw(frr_ctx *c, int mesh, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
     if (!c || !slot_ok(c->meshes, mesh)) return fail(c, FRR_ERR_INVALID, "bad mesh id");
     HIP_TRY(c, hipSetDevice(c->device));
-    // frr_draw knows the raster window, so a partitioned ctx can skip the setup records of triangles
-    // that touch none of its tile rows (frr_geometry alone cannot: the window comes later)
-    Cmd cmd;
-    cmd.kind = Cmd::GEOM; cmd.mesh = mesh; cmd.duni = c->duni; cmd.cull = c->cull;
-    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
-    const int rc = exec_cmd(c, cmd);
-    if (rc != FRR_OK) return rc;
-    return frr_raster(c, ps_id, x0, x1, y0, y1);
+    Cmd cmd = new_cmd(c, Cmd::GEOM);
+    cmd.mesh = mesh;
+    return draw_pass(c, cmd, true, ps_id, x0, x1, y0, y1);
 }
 
 int frr_draw_instanced(frr_ctx *c, int mesh, int inst, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
     Cmd cmd;
-    int rc = instanced_cmd(c, mesh, inst, &cmd);
-    if (rc != FRR_OK) return rc;
-    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;   // as frr_draw
-    if ((rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
-    return frr_raster(c, ps_id, x0, x1, y0, y1);
+    const int rc = instanced_cmd(c, mesh, inst, &cmd);
+    return rc != FRR_OK ? rc : draw_pass(c, cmd, true, ps_id, x0, x1, y0, y1);
 }
 
 int frr_draw_list(frr_ctx *c, int list, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
     Cmd cmd;
-    int rc = list_cmd(c, list, &cmd);
-    if (rc != FRR_OK) return rc;
-    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;   // as frr_draw
-    if ((rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
-    if (!c->lists[list].n) return FRR_OK;   // no items: no vertex shader either, so nothing a pixel shader could fail to match
-    return frr_raster(c, ps_id, x0, x1, y0, y1);
+    const int rc = list_cmd(c, list, &cmd);
+    return rc != FRR_OK ? rc : draw_pass(c, cmd, c->lists[list].n != 0, ps_id, x0, x1, y0, y1);
 }
 
 int frr_frame_fence(frr_ctx *c, void *stream)
@@ -2442,8 +2475,7 @@ int frr_readback(frr_ctx *c, uint8_t *rgba, float *depth, uint32_t *tri_id)
 int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uint64_t *ntris)
 {
     if (!c || !ntris || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry to read back");
-    if (c->fs.geom_filter.active)
-        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; use frr_geometry to read back the full Vec<[Vertex;3]>");
+    { const int rc = need_unfiltered_list(c, "frr_readback_setup (the full Vec<[Vertex;3]>)"); if (rc != FRR_OK) return rc; }
     { int rcs = finish(c); if (rcs != FRR_OK) return rcs; }
     const FrameState &f = c->fs;
     const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
@@ -2491,31 +2523,16 @@ int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uin
     return FRR_OK;
 }
 
-// the window rules of the commands that address the targets entry by entry (frr_resolve_varyings, frr_visible_pixels)
-static int entry_window_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
-{
-    if (x1 <= x0 || y1 <= y0) return fail(c, FRR_ERR_INVALID, "empty or inverted window");
-    if (x0 < 0) return fail(c, FRR_ERR_UNSUPPORTED, "x0 < 0: pixels of neighbouring rows share depth entries, an entry has no single pixel");
-    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
-    if (ww > (int64_t)c->W || wh > (int64_t)c->H) return fail(c, FRR_ERR_INVALID, "window larger than the FrameBuffer");
-    if (y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_INVALID, "window coordinates outside the i16 range");
-    if ((wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H)
-        return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
-    return FRR_OK;
-}
-
 // argument checks of frr_resolve_varyings / frr_readback_varyings; *K: varyings per vertex, *nothing: valid, writes nothing
 static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries, int *K, bool *nothing)
 {
     if (!c) return FRR_ERR_INVALID;
     const FrameState &f = c->fs;
     if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
-    { const int rcw = entry_window_check(c, x0, x1, y0, y1); if (rcw != FRR_OK) return rcw; }
-    const int64_t wh = (int64_t)y1 - y0;
-    if (f.geom_filter.active)
-        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry (unfiltered) and frr_raster before frr_resolve_varyings");
-    if (!buf || ((uintptr_t)buf & 3u)) return fail(c, FRR_ERR_INVALID, "output buffer is NULL or not 4-byte aligned");
-    if (out_entries < (uint64_t)wh * (uint64_t)x1) return fail(c, FRR_ERR_INVALID, "out_entries < (y1 - y0) * x1");
+    int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
+    if (rc == FRR_OK) rc = need_unfiltered_list(c, "frr_resolve_varyings");
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_VARYINGS_OUT, buf, out_entries, 0, x1, y0, y1));
+    if (rc != FRR_OK) return rc;
     *K = frr_vs_num_varyings(f.geom_vs);
     *nothing = *K <= 0 || f.geom_ntris == 0;   // (geom_ntris == 0: an empty mesh, or frr_clear since -- the setup list is gone)
     return FRR_OK;
@@ -2533,15 +2550,15 @@ int frr_resolve_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t
     const int rc = vary_check(c, x0, x1, y0, y1, dev_out_f32, out_entries, &K, &nothing);
     if (rc != FRR_OK || nothing) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    Cmd cmd;
-    cmd.kind = Cmd::VARY; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.vary_out = (float *)dev_out_f32; cmd.duni = c->duni;
+    Cmd cmd = new_cmd(c, Cmd::VARY, x0, x1, y0, y1);
+    cmd.vary_out = (float *)dev_out_f32;
     return exec_cmd(c, cmd);
 }
 
 int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, float *host_inout, uint64_t out_entries)
 {
     int K = 0; bool nothing = false;
-    int rc = vary_check(c, x0, x1, y0, y1, host_inout, out_entries, &K, &nothing);
+    const int rc = vary_check(c, x0, x1, y0, y1, host_inout, out_entries, &K, &nothing);
     if (rc != FRR_OK || nothing) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // a temporary device buffer that starts as the caller's: what the command leaves untouched comes back as it went in
@@ -2549,39 +2566,25 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     const size_t bytes = (size_t)entries * (size_t)K * sizeof(float);
     DevBuf<float> tmp;
     if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
-    hipError_t e = hipMemcpy(tmp, host_inout, bytes, hipMemcpyHostToDevice);   // (returns when the copy is done: in front of the command on any stream)
-    if (e == hipSuccess) {
-        Cmd cmd;
-        cmd.kind = Cmd::VARY; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.vary_out = tmp; cmd.duni = c->duni;
-        rc = exec_cmd(c, cmd);
-        const int rf = finish(c);   // synchronisation point (and, if a list was too small, the replay -- the command included); the log is empty afterwards
-        if (rc == FRR_OK) rc = rf;
-        if (rc == FRR_OK) e = hipMemcpy(host_inout, tmp, bytes, hipMemcpyDeviceToHost);
-        // (a finish() that failed may have left the command in the log: nothing may replay it into the freed buffer)
-        for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == Cmd::VARY && c->log[k].vary_out == tmp) c->log.erase(c->log.begin() + (ptrdiff_t)k);
-    }
-    if (rc != FRR_OK) return rc;
+    const hipError_t e = hipMemcpy(tmp, host_inout, bytes, hipMemcpyHostToDevice);   // (returns when the copy is done: in front of the command on any stream)
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy varyings: ") + hipGetErrorString(e));
-    return FRR_OK;
+    return host_round_trip(c, new_cmd(c, Cmd::VARY, x0, x1, y0, y1), &Cmd::vary_out, tmp, host_inout, bytes, "varyings");
 }
 
 // argument checks of frr_visible_pixels / frr_visible_pixels_host
 static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
 {
     if (!c) return FRR_ERR_INVALID;
-    const FrameState &f = c->fs;
     if (unit != FRR_PER_ITEM && unit != FRR_PER_TRIANGLE) return fail(c, FRR_ERR_INVALID, "unknown frr_visible_unit");
-    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
-    { const int rcw = entry_window_check(c, x0, x1, y0, y1); if (rcw != FRR_OK) return rcw; }
-    if (f.geom_filter.active)
-        return fail(c, FRR_ERR_INVALID, "the setup list of a partitioned frr_draw holds only this rank's triangles; use frr_geometry* + frr_raster before frr_visible_pixels");
-    if (out_entries > 0 && (!buf || ((uintptr_t)buf & 3u))) return fail(c, FRR_ERR_INVALID, "output buffer is NULL or not 4-byte aligned");
-    return FRR_OK;
+    if (c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
+    int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
+    if (rc == FRR_OK) rc = need_unfiltered_list(c, "frr_visible_pixels");
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, buf, out_entries, 0, x1, y0, y1));
+    return rc;
 }
 static Cmd visible_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
 {
-    Cmd cmd;
-    cmd.kind = Cmd::VISIBLE; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.duni = c->duni;
+    Cmd cmd = new_cmd(c, Cmd::VISIBLE, x0, x1, y0, y1);
     cmd.vis_unit = unit; cmd.vis_out = dev_out; cmd.vis_entries = out_entries;
     return cmd;
 }
@@ -2601,15 +2604,8 @@ int frr_visible_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf<uint32_t> tmp;
     if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
-    rc = exec_cmd(c, visible_cmd(c, unit, x0, x1, y0, y1, tmp, out_entries));
-    const int rf = finish(c);   // synchronisation point (and, if a list was too small, the replay -- the command included); the log is empty afterwards
-    if (rc == FRR_OK) rc = rf;
-    hipError_t e = hipSuccess;
-    if (rc == FRR_OK) e = hipMemcpy(host_out, tmp, (size_t)out_entries * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    // (a finish() that failed may have left the command in the log: nothing may replay it into the freed buffer)
-    for (size_t k = c->log.size(); k-- > 0;) if (c->log[k].kind == Cmd::VISIBLE && c->log[k].vis_out == tmp) c->log.erase(c->log.begin() + (ptrdiff_t)k);
+    rc = host_round_trip(c, visible_cmd(c, unit, x0, x1, y0, y1, nullptr, out_entries), &Cmd::vis_out, tmp, host_out, (size_t)out_entries * sizeof(uint32_t), "counts");
     if (rc != FRR_OK) return rc;
-    if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy counts: ") + hipGetErrorString(e));
     if (nunits) {
         const FrameState &f = c->fs;
         const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
@@ -2631,34 +2627,16 @@ int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_
 static int shade_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t in_entries, int K, uint32_t id_count, bool *nothing)
 {
     if (!c) return FRR_ERR_INVALID;
-    if (x1 <= x0 || y1 <= y0) return fail(c, FRR_ERR_INVALID, "empty or inverted window");
-    if (x0 < 0) return fail(c, FRR_ERR_UNSUPPORTED, "x0 < 0: pixels of neighbouring rows share depth entries, an entry has no single pixel");
-    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
-    if (ww > (int64_t)c->W || wh > (int64_t)c->H) return fail(c, FRR_ERR_INVALID, "window larger than the FrameBuffer");
-    if (y0 < -32768 || x1 > 32767 || y1 > 32767) return fail(c, FRR_ERR_INVALID, "window coordinates outside the i16 range");
-    if ((wh - 1) * (int64_t)x1 + ww > (int64_t)c->W * c->H)
-        return fail(c, FRR_ERR_INVALID, "depth index (cy-y0)*x1+(cx-x0) would leave the depth buffer (renderer.rs:362)");
-    // the rule frr_raster applies between a pixel shader and the geometry's K (raster_check), with the buffer's K
-    if (ps_id >= FRR_SHADER_USER_BASE) {
-        const UserShader *us = user_shader(ps_id);
-        if (!us) return fail(c, FRR_ERR_INVALID, "unknown shader id");
-        if (us->K != K) return fail(c, FRR_ERR_INVALID, "the user pixel shader's varyings do not match the buffer's K");
-    } else if (ps_id == FRR_PS_DEPTH) {
-        return fail(c, FRR_ERR_INVALID, "FRR_PS_DEPTH: nothing to shade");
-    } else if (ps_id < 0 || ps_id > FRR_PS_BLINN || K < 0 || K > FRR_MAX_VARYINGS || (ps_id == FRR_PS_COLOR && K != 3) || ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && K != 8)) {
-        return fail(c, FRR_ERR_INVALID, "pixel shader does not match the buffer's K");
-    }
-    if ((ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN) && !c->duni.tex) return fail(c, FRR_ERR_INVALID, "no texture bound to uniforms.texture_slot");
-    if ((K > 0 && !buf) || ((uintptr_t)buf & 3u)) return fail(c, FRR_ERR_INVALID, "varyings buffer is NULL or not 4-byte aligned");
-    if (in_entries < (uint64_t)wh * (uint64_t)x1) return fail(c, FRR_ERR_INVALID, "in_entries < (y1 - y0) * x1");
+    int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
+    if (rc == FRR_OK) rc = ps_check(c, K_OF_BUFFER, ps_id, K);   // the rule frr_raster applies, with the buffer's K for the geometry's
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_VARYINGS_IN, buf, in_entries, K, x1, y0, y1));
     *nothing = id_count == 0u;
-    return FRR_OK;
+    return rc;
 }
 static Cmd shade_cmd(const frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *dev_in, uint64_t in_entries, int K, uint32_t id_first, uint32_t id_count)
 {
-    Cmd cmd;
-    cmd.kind = Cmd::SHADE; cmd.ps = ps_id; cmd.x0 = x0; cmd.x1 = x1; cmd.y0 = y0; cmd.y1 = y1; cmd.duni = c->duni;
-    cmd.shade_in = dev_in; cmd.shade_entries = in_entries; cmd.shade_K = K; cmd.id_first = id_first; cmd.id_count = id_count;
+    Cmd cmd = new_cmd(c, Cmd::SHADE, x0, x1, y0, y1);
+    cmd.ps = ps_id; cmd.shade_in = dev_in; cmd.shade_entries = in_entries; cmd.shade_K = K; cmd.id_first = id_first; cmd.id_count = id_count;
     return cmd;
 }
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_np as onp
+from . import arg_rules
 from . import limit_scenes as ls
 
 
@@ -102,7 +103,7 @@ def test_far_window_scenes_meet_their_conditions(oracle, name, variant):
     if variant == "fans":
         assert c["spi"].shape[0] > c["tris"].shape[0] + 100, (c["spi"].shape[0], c["tris"].shape[0], got)
     W, H, (x0, x1, y0, y1) = ls.FAR_WINDOWS[name]
-    assert x1 > 0 and (y1 - y0 - 1) * x1 + (x1 - x0) <= W * H and x1 - x0 <= W and y1 - y0 <= H   # raster_check accepts it
+    assert x1 > x0 and y1 > y0 and arg_rules.ask([arg_rules.window(arg_rules.RASTER, W, H, x0, x1, y0, y1)]) == [(arg_rules.OK, "")]   # frr_raster accepts it, and it is not empty
     for axis, (lo, hi) in enumerate(((x0, x1), (y0, y1))):
         for v in ls.BOUNDARY_VALUES:
             if lo - 3 <= v <= hi + 3:
