@@ -518,6 +518,16 @@ __device__ __forceinline__ ScreenVtx to_screen(const float pos[4], float fw, flo
     v.ndcy = pos[1] * v.rhw;
     v.sx = (v.ndcx + 1.0f) * fw * 0.5f;
     v.sy = (1.0f - v.ndcy) * fh * 0.5f;
+    if (v.sx != v.sx || v.sy != v.sy) {
+        // a NaN screen position is a word of the setup record: sign and payload are the reference machine's (frr_exact.h: x86_nan)
+        const float nx = x86_nan(pos[0], v.rhw, v.ndcx), ny = x86_nan(pos[1], v.rhw, v.ndcy);
+        float t = x86_nan(nx, 1.0f, nx + 1.0f);
+        t = x86_nan(t, fw, t * fw);
+        v.sx = x86_nan(t, 0.5f, t * 0.5f);
+        t = x86_nan(1.0f, ny, 1.0f - ny);
+        t = x86_nan(t, fh, t * fh);
+        v.sy = x86_nan(t, 0.5f, t * 0.5f);
+    }
     v.ix = spi_of(v.sx); v.iy = spi_of(v.sy);
     return v;
 }
@@ -575,12 +585,19 @@ __device__ __forceinline__ uint2 pack_pbox(int x0, int y0, int x1, int y1, int x
 }
 
 // Whole-triangle early-z bound: rhw = (r0*a + r1*b) + r2*c with a+b+c = 1 up to a few roundings, so
-// |rhw| <= max|r_i| * (1 + 2^-18); the z key of that bound, or all-ones (never culled) for NaN vertices.
-__device__ __forceinline__ uint32_t cull_zub(float r0, float r1, float r2)
+// |rhw| <= max|r_i| * (1 + 2^-18); the z key of that bound, or all-ones (never culled) for a triangle that can have a NaN
+// fragment, which passes every z-test (renderer.rs:363) whatever lies in front of it: a NaN or infinite rhw at a vertex
+// (inf * 0, inf - inf), or screen positions (sx, sy of the three vertices) that are not finite or so large that a
+// product of frag_eval could overflow (below 1e18 every product stays under 1e37: that, and no more, is what the
+// threshold rests on; the bound itself still assumes, as before, that 1 / (a + b + c) is finite).
+__device__ __forceinline__ uint32_t cull_zub(float r0, float r1, float r2, float s0x, float s0y, float s1x, float s1y, float s2x, float s2y)
 {
     const float ar0 = fabsf(r0), ar1 = fabsf(r1), ar2 = fabsf(r2);
     const float ub = fmaxf(fmaxf(ar0, ar1), ar2) * 1.000003814697265625f;
-    return (ar0 == ar0 && ar1 == ar1 && ar2 == ar2) ? zkey(ub) : 0xFFFFFFFFu;
+    const float big = fmaxf(fmaxf(fmaxf(fabsf(s0x), fabsf(s0y)), fmaxf(fabsf(s1x), fabsf(s1y))), fmaxf(fabsf(s2x), fabsf(s2y)));
+    const bool pos_ok = big < 1.0e18f && s0x == s0x && s0y == s0y && s1x == s1x && s1y == s1y && s2x == s2x && s2y == s2y;   // (fmaxf drops a NaN operand)
+    const float inf = __builtin_huge_valf();
+    return (ar0 < inf && ar1 < inf && ar2 < inf && pos_ok) ? zkey(ub) : 0xFFFFFFFFu;
 }
 
 // ---- fragment arithmetic (renderer.rs:343-360), shared by the coverage loop and the resolve --

@@ -336,4 +336,30 @@ FRR_HD float sort_angle(float fy, float fx)
     return a;
 }
 
+// The sort of renderer.rs:205-218 compares the angles by f32::total_cmp, which orders NaNs too: by sign, then by payload.
+// Which NaN an angle is, is the arithmetic of the machine the reference runs on (x86-64, SSE), not IEEE 754's:
+//   - an operation with a NaN operand returns that operand (quieted) with its sign -- also a subtraction's second
+//     operand -- and the first one where both are NaN;
+//   - an operation that makes a NaN of other values (inf - inf, 0 * inf) returns the negative one, 0xFFC00000.
+// gfx950 gives +NaN for the latter and flips the sign of a NaN it subtracts, so `x - cx` with a NaN centroid sorts the
+// finite vertices BEFORE the NaN ones here and among them there.  x86_nan restates the rule for one operation: r is
+// `a op b` as this machine computed it, returned unchanged unless it is a NaN.
+// NOT a general guarantee: it is the reference's NaN only while at most one NaN reaches each operation (one NaN source per
+// chain).  Where two different NaNs meet, SSE returns the one in its first operand, and which operand of a commutative
+// addss / mulss that is, is the compiler's choice -- it may differ between the Rust build and any restatement of it.
+FRR_HD float x86_nan(float a, float b, float r)
+{
+    if (r == r) return r;
+    if (a != a) return u2f(f2u(a) | 0x00400000u);
+    if (b != b) return u2f(f2u(b) | 0x00400000u);
+    return u2f(0xFFC00000u);
+}
+// sort_angle(py - cy, px - cx) with the reference's NaNs (e_atan2f.c returns x + y for a NaN operand)
+FRR_HD float sort_angle_x86(float py, float cy, float px, float cx)
+{
+    const float fy = x86_nan(py, cy, py - cy), fx = x86_nan(px, cx, px - cx);
+    if (fx != fx || fy != fy) return x86_nan(fx, fy, fx + fy);
+    return sort_angle(fy, fx);
+}
+
 } // namespace frr

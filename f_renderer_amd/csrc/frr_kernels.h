@@ -457,7 +457,37 @@ __device__ __forceinline__ uint4 clip_triangle_wave(const GeomArgs &g, const Dev
     for (int k = 0; k < n; ++k) { cx += s_xy[k][0]; cy += s_xy[k][1]; }
     const float inv_n = 1.0f / (float)n;
     cx *= inv_n; cy *= inv_n;
-    const int32_t key = total_order_key(sort_angle(p[1] - cy, p[0] - cx));
+    float ang = sort_angle(p[1] - cy, p[0] - cx);
+    if (__ballot(keep && ang != ang)) {
+        // A NaN angle (an x or y that is NaN or infinite in the list): total_cmp orders NaNs by sign and payload, and
+        // those are the reference machine's, not this one's (frr_exact.h: x86_nan).  The whole wave takes this triangle's
+        // x, y (:89), centroid and angles again by that rule; whatever is not a NaN comes out as before.
+        float nx = p[0], ny = p[1];
+        // (the vertex shader once more, by the whole wave: the clip positions need not stay in registers for a branch almost nobody takes)
+        float q[3][4], qc[3][KS];
+        const float *qin[3], *qim = nullptr;
+        tri_inputs<NF, IDX, INST, LIST>(g, t, qin, &qim);
+        run_vs3<VS, INST>(u, qim, qin, q, qc);
+        if (lane < 18) {
+            const int pi = lane / 6, plane = lane - pi * 6;
+            float a[4], b[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { a[k] = pi == 2 ? q[1][k] : q[0][k]; b[k] = pi == 0 ? q[1][k] : q[2][k]; }
+            const float r = intersect_ratio(plane, a, b);      // (not a NaN on a kept lane: its w is not)
+            const float dx = x86_nan(b[0], a[0], b[0] - a[0]), dy = x86_nan(b[1], a[1], b[1] - a[1]);
+            const float rx = x86_nan(r, dx, r * dx), ry = x86_nan(r, dy, r * dy);
+            nx = x86_nan(a[0], rx, a[0] + rx); ny = x86_nan(a[1], ry, a[1] + ry);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (keep) { s_xy[li][0] = nx; s_xy[li][1] = ny; }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        float ex = 0.0f, ey = 0.0f;
+        for (int k = 0; k < n; ++k) { ex = x86_nan(ex, s_xy[k][0], ex + s_xy[k][0]); ey = x86_nan(ey, s_xy[k][1], ey + s_xy[k][1]); }
+        ex = x86_nan(ex, inv_n, ex * inv_n); ey = x86_nan(ey, inv_n, ey * inv_n);
+        ang = sort_angle_x86(ny, ey, nx, ex);
+        p[0] = nx; p[1] = ny;          // (to_screen below: a NaN of these is a word of the record)
+    }
+    const int32_t key = total_order_key(ang);
     if (keep) s_key[li] = key;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     int rank = 0;                                                                          // stable sort position (:205-218)
@@ -489,7 +519,7 @@ __device__ __forceinline__ uint4 clip_triangle_wave(const GeomArgs &g, const Dev
         const uint32_t fslot = fbase + (uint32_t)q;             // fan triangle q of input t: emission order is q order
         const uint32_t idx = g.ntris + fslot;
         g.fan_okey[fslot] = (t << FAN_BITS) + 1u + (uint32_t)q;
-        { const uint2 pb = pack_pbox(p0x, p0y, p1x, p1y, p2x, p2y); mine = make_uint4(pb.x, pb.y, cull_zub(v0[0], v1[0], v2[0]), idx); g.pbox[idx] = mine; }
+        { const uint2 pb = pack_pbox(p0x, p0y, p1x, p1y, p2x, p2y); mine = make_uint4(pb.x, pb.y, cull_zub(v0[0], v1[0], v2[0], v0[3], v0[4], v1[3], v1[4], v2[3], v2[4]), idx); g.pbox[idx] = mine; }
         const EdgeWords e01 = edge_words(p0x, p0y, p1x, p1y, (flags >> 1) & 1u);
         const EdgeWords e12 = edge_words(p1x, p1y, p2x, p2y, (flags >> 2) & 1u);
         const EdgeWords e20 = edge_words(p2x, p2y, p0x, p0y, (flags >> 3) & 1u);
@@ -547,9 +577,14 @@ __device__ __forceinline__ SetupOut setup_unclipped(const float pos[3][4], const
         };
         lt10 = less(1, 0); lt20 = less(2, 0); lt21 = less(2, 1); le01 = !lt10;
         if (!safe) {
+            // (a NaN angle is the reference machine's NaN, sign and payload: frr_exact.h, x86_nan -- the centroid again by that rule)
             int32_t key[3];
+            float ex = 0.0f, ey = 0.0f;
 #pragma unroll
-            for (int v = 0; v < 3; ++v) key[v] = total_order_key(sort_angle(dy[v], dx[v]));
+            for (int v = 0; v < 3; ++v) { ex = x86_nan(ex, pos[v][0], ex + pos[v][0]); ey = x86_nan(ey, pos[v][1], ey + pos[v][1]); }
+            ex = x86_nan(ex, inv_n, ex * inv_n); ey = x86_nan(ey, inv_n, ey * inv_n);
+#pragma unroll
+            for (int v = 0; v < 3; ++v) key[v] = total_order_key(sort_angle_x86(pos[v][1], ey, pos[v][0], ex));
             lt10 = key[1] < key[0]; lt20 = key[2] < key[0]; lt21 = key[2] < key[1]; le01 = key[0] <= key[1];
         }
     }
@@ -588,7 +623,7 @@ __device__ __forceinline__ SetupOut setup_unclipped(const float pos[3][4], const
     const EdgeWords e20 = edge_words(px[2], py[2], px[0], py[0], (flags >> 3) & 1u);
     flags |= (e01.pos | (e12.pos << 1) | (e20.pos << 2)) << REC_POS_SHIFT;
     flags |= eoff << REC_EOFF_SHIFT;
-    { const uint2 pb = pack_pbox(px[0], py[0], px[1], py[1], px[2], py[2]); o.pbox = make_uint4(pb.x, pb.y, cull_zub(rw[0], rw[1], rw[2]), 0u); }
+    { const uint2 pb = pack_pbox(px[0], py[0], px[1], py[1], px[2], py[2]); o.pbox = make_uint4(pb.x, pb.y, cull_zub(rw[0], rw[1], rw[2], sx[0], sy[0], sx[1], sy[1], sx[2], sy[2]), 0u); }
     o.q0 = make_uint4(e01.kd, e01.c, e12.kd, e12.c);
     o.q1 = make_uint4(e20.kd, e20.c, f2u(sx[0]), f2u(sy[0]));
     o.q2 = make_uint4(f2u(sx[1]), f2u(sy[1]), f2u(sx[2]), f2u(sy[2]));

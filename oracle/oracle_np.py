@@ -235,7 +235,9 @@ def _ratio(plane, a, b):
     return (aw - a[2]) / (aw - bw - a[2] + b[2])                 # Z_FAR
 
 
-def geometry_processing(width, height, vs_inputs, vs_id, u):
+def geometry_processing(width, height, vs_inputs, vs_id, u, debug=None):
+    """debug: a dict that receives `keys`, the sort keys of the vertex list in list order (kept intersections, then the
+    three originals), and `kept`, the number of intersections kept."""
     nf = VS_NF[vs_id]
     vin = np.asarray(vs_inputs, F).reshape(3, nf)
     verts = []
@@ -272,6 +274,8 @@ def geometry_processing(width, height, vs_inputs, vs_id, u):
         if at < 0.0:
             at = F(at + PI * F(2.0))
         keys.append(total_key(at))
+    if debug is not None:
+        debug.update(keys=list(keys), kept=len(lst) - 3)
     order = sorted(range(len(lst)), key=lambda i: keys[i])      # Python's sort is stable
     lst = [lst[i] for i in order]
     with np.errstate(all="ignore"):
