@@ -20,6 +20,11 @@
 //   --visible with --list or --instances N prints, after the draw, one line per item -- its first triangle id, the triangles
 //       it emitted and the pixels it owns on screen (visible_pixels: counted on the device, the frame is not read back for
 //       it) -- and the number of items that own no pixel; the frame written is the same
+//   --reuse with --list --visible draws a SECOND frame from the first one's counts: the counts go to device memory
+//       (visible_pixels), and after clear the list is drawn again with draw_list_if on that buffer -- an item that owned no
+//       pixel is dropped -- with no host wait between the count and the draw; it prints how many items the second frame dropped
+//       and whether its colour equals the first frame's.  (The mechanism only: an item that was hidden stays dropped until the
+//       caller's own policy sets its entry again.)
 //   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
 //       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
@@ -33,6 +38,11 @@
 
 #include "../f_renderer_amd/host/frr_renderer.hpp"
 
+// --reuse: one device buffer of the HIP runtime libfrr_hip.so itself runs on (no HIP header is needed for three calls)
+extern "C" int hipMalloc(void **ptr, size_t size);
+extern "C" int hipFree(void *ptr);
+extern "C" int hipMemcpy(void *dst, const void *src, size_t size, int kind);
+
 static std::vector<char> slurp(const char *path)
 {
     std::ifstream f(path, std::ios::binary);
@@ -42,10 +52,10 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false, list = false, visible = false;
+    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible") {
-            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : deferred) = true;
+        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible" || std::string(argv[i]) == "--reuse") {
+            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : std::string(argv[i]) == "--reuse" ? reuse : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -66,6 +76,7 @@ int main(int argc, char **argv)
             argc -= 2; --i;
         }
     if (visible && !list && instances < 0) { std::cerr << "--visible goes with --list or --instances N\n"; return 2; }
+    if (reuse && (!list || !visible || wireframe || deferred)) { std::cerr << "--reuse goes with --list --visible (and without --wireframe / --deferred)\n"; return 2; }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -86,7 +97,8 @@ int main(int argc, char **argv)
                      "       (--wireframe: overlay the mesh's edges; --deferred: depth pre-pass, varyings, shade;\n"
                      "        --instances N: N copies on a grid in one instanced pass; --list: the objects as one list pass;\n"
                      "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign;\n"
-                     "        --visible (with --list or --instances N): print the pixels every item owns on screen)\n";
+                     "        --visible (with --list or --instances N): print the pixels every item owns on screen;\n"
+                     "        --reuse (with --list --visible): a second frame by draw_list_if on the first one's counts)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -144,8 +156,9 @@ int main(int argc, char **argv)
                 m[14] = -0.25f * (float)(i % 3);
             }
         } else if (list) models.assign(1, model);
+        frr::DrawList items;
         if (list) {
-            const frr::DrawList items = renderer.upload_draw_list(std::vector<frr::Mesh>(models.size(), mesh), models);
+            items = renderer.upload_draw_list(std::vector<frr::Mesh>(models.size(), mesh), models);
             renderer.geometry_list(items);                                                      // loop A for every item, one pass
             std::vector<uint32_t> first, count;
             renderer.item_ranges(first, count);                                                 // body_offset, face_offset, ... (phong.rs:333-359)
@@ -188,6 +201,28 @@ int main(int argc, char **argv)
             std::ofstream ppm(out_ppm, std::ios::binary);
             ppm << "P6\n" << W << " " << H << "\n255\n";
             for (uint32_t i = 0; i < W * H; ++i) ppm.write(reinterpret_cast<const char *>(&frame_buffer.get_data()[(size_t)i * 4]), 3);
+        }
+        if (reuse) {
+            // draw, count, draw again: the counts of the frame above stay on the device and decide what the next frame draws
+            const uint64_t n = models.size();
+            void *counts = nullptr;
+            if (hipMalloc(&counts, (size_t)(n ? n : 1) * sizeof(uint32_t)) != 0) { std::cerr << "hipMalloc failed\n"; return 1; }
+            renderer.visible_pixels(FRR_PER_ITEM, counts, n);                                   // per item of the list pass above
+            renderer.clear({30, 30, 30, 255}, 0.0f);
+            renderer.draw_list_if(items, counts, n, FRR_PS_PHONG);                              // keep[i] >= 1: the item owned a pixel
+            frr::FrameBuffer second = frr::FrameBuffer::create(W, H);
+            renderer.read_frame_buffer(second);                                                 // (the first host wait since the count)
+            std::vector<uint32_t> host((size_t)n, 0u), first, count;
+            if (n && hipMemcpy(host.data(), counts, (size_t)n * sizeof(uint32_t), 2 /* device to host */) != 0) { std::cerr << "hipMemcpy failed\n"; return 1; }
+            renderer.item_ranges(first, count);
+            size_t dropped = 0;
+            for (size_t k = 0; k < (size_t)n; ++k) {
+                dropped += host[k] == 0u;
+                if ((host[k] == 0u) != (count[k] == 0u)) { std::cerr << "item " << k << ": dropped and emitting disagree\n"; return 3; }
+            }
+            const bool same = second.get_data() == frame_buffer.get_data();
+            std::printf("reuse: dropped %zu of %zu items, colour equal: %s\n", dropped, (size_t)n, same ? "yes" : "no");
+            (void)hipFree(counts);
         }
         // error behaviour: a range with min > max panics in the reference (i32::clamp) -> frr::Error here
         bool threw = false;

@@ -138,6 +138,8 @@ SIGNATURES = {
     "frr_drawlist_free": (C.c_int, [C.c_void_p, C.c_int]),
     "frr_geometry_list": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_uint64)]),
     "frr_draw_list": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frr_geometry_list_if": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, _P(C.c_uint64)]),
+    "frr_draw_list_if": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frr_geometry_item_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "frr_host_list_item": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
     "frr_lines_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),

@@ -179,6 +179,7 @@ struct GeomSet {
     DevBuf<uint32_t> bcount;         // [geometry blocks] dense binning entries per block (GeomArgs::bcount)
     DevBuf<uint2> clipq;             // [input triangles] the clip kernel's queue (GeomArgs::clipq)
     DevBuf<float> inst_tab;          // [instances][32] the matrices of an instanced pass (GeomArgs::inst)
+    DevBuf<uint32_t> keep_tab;       // [items] the keep table of a predicated list pass (GeomArgs::keep), beside its matrices
     // frr_resolve_varyings: emission index within the draw -> slot, one table per parity of the geometry pass (allocated by
     // the first resolve of a pass on this set, at the set's setup capacity); vslot_stream: the stream of its latest user
     DevBuf<uint32_t> vslot[2]; hipStream_t vslot_stream[2] = {nullptr, nullptr};
@@ -234,6 +235,7 @@ struct FrameState {
     int geom_list = -1; uint64_t geom_list_gen = 0;    // ... and, a list pass, its list: DrawSig
     // its items (frr_geometry_item_ranges): the items of a list pass, the instances of an instanced pass (geom_stride inputs each), else one
     uint64_t geom_nitems = 1, geom_stride = 0;
+    bool geom_pred = false;        // it is a predicated list pass: what it needs of the work lists hangs on device data (never proven)
     uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
 };
 
@@ -246,6 +248,8 @@ struct Cmd {
     int mesh = -1; bool filter = false; int32_t fy0 = 0, fy1 = 0;
     int cull = FRR_CULL_NONE;           // frr_set_cull at the time of the call (a replay runs the pass under it again)
     int list = -1; uint64_t list_gen = 0;   // a list pass: its list, and which upload that id meant (mesh is unused then; pv as below)
+    // a predicated list pass (frr_geometry_list_if): the caller's device buffer, read again by a replay, and the threshold
+    bool pred = false; const uint32_t *keep = nullptr; uint64_t keep_entries = 0; uint32_t min_value = 0;
     int inst = -1; float pv[16] = {};   // an instanced pass: its table, and proj * view at the time of the call (the table's mvp = pv * model)
     // RASTER
     int ps = 0; int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0; bool count_frags = true;
@@ -317,6 +321,7 @@ struct frr_ctx {
     // cross-stream ordering: every workspace set has an event that fires when the latest tile kernel reading it is done (the second
     // stream waits for it before it overwrites a workspace that kernel reads), ev_bin[k & 3] when binning k is done
     Event ev_bin[4], ev_join;
+    Event ev_keep[4];               // a predicated pass's stream behind the ctx's other streams, one event per stream (exec_geometry)
     uint64_t bin_serial = 0;
     // inputs the caller wrote on `stream` (a device-bound mesh) must be visible to the ctx's private streams: every bind
     // starts a new epoch, and a private stream waits for `stream` once per epoch before its next geometry pass
@@ -342,6 +347,7 @@ struct frr_ctx {
     uint64_t sync_epoch = 0;        // frr_sync calls so far (DrawSig of a device-bound mesh: rewritten in place behind one?)
     Event ev_verify;
     bool verify_pending = false;
+    bool verify_proves = true;      // the pass being verified enters `proven` (false: a predicated pass, verified every time)
     DrawSig verify_sig;
     // own targets handed out (frr_target_ptrs / frr_frame_fence): the frame that next renders into that set waits for what
     // the stream they were handed to holds by then (the caller's reads), see frr_clear
@@ -717,10 +723,13 @@ template <int VS> void launch_geometry(frr_ctx *c, GeomArgs &g, uint32_t nblocks
 
 // the geometry kernel for the VS of the mesh; models: the table of an instanced pass (or the matrices of a list's items), whose matrices (GeomArgs::inst = pv * model
 // and model, per instance) are filled first -- on the pass's stream and inside the command, so a replay fills them again
-void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const DevUniforms &du, const UserModule *um, const float *models, const float *pv)
+// keep, min_value: a predicated list pass, whose keep table (GeomArgs::keep) is filled the same way, from the caller's buffer
+void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const DevUniforms &du, const UserModule *um, const float *models, const float *pv,
+                        const uint32_t *keep, uint32_t min_value)
 {
     hipStream_t st = gstream_of(c);
     ProfScope p(c, KID_GEOM, st);
+    if (g.keep) hipLaunchKernelGGL(k_item_keep, dim3((g.ninst + 255u) / 256u), dim3(256), 0, st, keep, min_value, const_cast<uint32_t *>(g.keep), g.ninst);
     if (g.inst) {
         Mat4Arg m;
         memcpy(m.m, pv, sizeof m.m);
@@ -931,6 +940,8 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     const bool use_clipq = nt > 0 && (c->clip_queue > 0 || (c->clip_queue < 0 && c->clip_queue_auto));
     if (use_clipq && (rc = ensure(c, S.clipq, (size_t)nt)) != FRR_OK) return rc;
     if (nmat && nt > 0 && (rc = ensure(c, S.inst_tab, (size_t)nmat * 32)) != FRR_OK) return rc;
+    const bool keep_tab = cmd.pred && nmat && nt > 0;
+    if (keep_tab && (rc = ensure(c, S.keep_tab, (size_t)nmat)) != FRR_OK) return rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // the previous pass's n_emit feeds this pass's tri_base
     if (on_g && !c->gstream) {
         // created on first use: a process maps its HIP streams onto a handful of hardware queues, and two streams that
@@ -950,6 +961,20 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if ((rc = gstream_join(c)) != FRR_OK) return rc;
     if ((rc = gstream_wait_readers(c, S.reader)) != FRR_OK) return rc;
     if ((rc = gstream_wait_readers(c, c->wire_reader[f.lane])) != FRR_OK) return rc;
+    if (keep_tab) {
+        // The keep buffer is read on this pass's stream, behind every command issued on this ctx so far -- whichever of its
+        // streams that ran on: the frr_visible_pixels of the previous frame is the intended writer -- and behind the streams
+        // of pending frr_frame_wait calls (a caller that wrote the mask on a stream of its own).  Events only: no host wait.
+        // (The waits stay pending: the pass's target write consumes them.)
+        hipStream_t gs = gstream_of(c);
+        const hipStream_t others[4] = {c->stream, c->tstream[0].st, c->tstream[1].st, c->gstream};
+        for (int k = 0; k < 4; ++k) {
+            if (!others[k] || others[k] == gs) continue;
+            HIP_TRY(c, hipEventRecord(c->ev_keep[k], others[k]));
+            HIP_TRY(c, hipStreamWaitEvent(gs, c->ev_keep[k], 0));
+        }
+        for (const frr_ctx::FrameWait &w : c->waits) HIP_TRY(c, hipStreamWaitEvent(gs, w.ev, 0));
+    }
     GeomArgs g;
     g.in = m.dev; g.idx = m.idx; g.nverts = (uint32_t)m.nverts; g.ntris = (uint32_t)nt; g.width = c->W; g.height = c->H;
     g.fan_cap = (uint32_t)fan_cap;
@@ -965,6 +990,8 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.inst = nmat && nt > 0 ? S.inst_tab.get() : nullptr; g.ntris_mesh = (uint32_t)m.ntris; g.ninst = dl || it ? (uint32_t)nmat : 1u;
     g.items = dl && nt > 0 ? dl->rows.get() : nullptr; g.item_first = dl ? dl->first.get() : nullptr; g.item_ntris = dl ? dl->first.get() + dl->n : nullptr;
     g.cull = cmd.cull;
+    g.keep = keep_tab ? S.keep_tab.get() : nullptr;
+    f.geom_pred = cmd.pred;
     // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it)
     f.geom_filter = GeomFilter{cmd.filter, cmd.fy0, cmd.fy1, f.rank, f.world, f.part_blocked};
     f.gpars[f.lane] = par; cmd.par = par; cmd.lane = f.lane; f.gset = si;
@@ -990,7 +1017,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
     } else {
-        launch_geometry_vs(c, g, nblocks, vs, cmd.duni, um, dl ? dl->models.get() : it ? it->dev : nullptr, cmd.pv);
+        launch_geometry_vs(c, g, nblocks, vs, cmd.duni, um, dl ? dl->models.get() : it ? it->dev : nullptr, cmd.pv, cmd.keep, cmd.min_value);
         f.scan_pending = true;
     }
     HIP_TRY(c, hipGetLastError());
@@ -1137,11 +1164,14 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
         sig.blocked = f.part_blocked ? 1 : 0; sig.filter = f.geom_filter.active ? 1 : 0; sig.fy0 = f.geom_filter.y0; sig.fy1 = f.geom_filter.y1;
         sig.gset = f.gset; sig.bset = bi; sig.cull = f.geom_cull;
+        // (a predicated pass is never known: which items it keeps is device data, so neither its own earlier runs nor the
+        // unpredicated pass over the same list say what it needs -- and it proves nothing for anybody else)
         bool known = false;
-        for (const DrawSig &p : c->proven) known = known || same_sig(p, sig);
+        if (!f.geom_pred) for (const DrawSig &p : c->proven) known = known || same_sig(p, sig);
         if (!known) {
             HIP_TRY(c, hipEventRecord(c->ev_verify, gs));
             c->verify_pending = true;
+            c->verify_proves = !f.geom_pred;
             c->verify_sig = sig;
         }
     }
@@ -1448,6 +1478,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
             failed = *(volatile uint32_t *)c->host_bad != c->seen_bad;
         }
         if (failed) { const int rf = finish(c); if (rf != FRR_OK) return rf; }   // grows the lists and replays, as often as it takes
+        if (!c->verify_proves) return FRR_OK;
         if (c->proven.size() >= 32) c->proven.erase(c->proven.begin());
         c->proven.push_back(sig);
         return FRR_OK;
@@ -1650,7 +1681,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     for (DevBuf<uint32_t> *b : {&c->tile_counts, &c->tile_offsets, &c->tile_cursor}) ok = ok && b->reset((size_t)c->max_tiles + 1) == hipSuccess;
     for (Event *e : {&c->gset[0].reader.ev, &c->gset[1].reader.ev, &c->bset[0].reader.ev, &c->bset[1].reader.ev, &c->tstream[1].ev, &c->tstream[0].ev,
                      &c->ev_bin[0], &c->ev_bin[1], &c->ev_bin[2], &c->ev_bin[3], &c->ev_join, &c->wire_reader[0].ev, &c->wire_reader[1].ev,
-                     &c->ev_verify, &c->ev_export}) ok = ok && e->create() == hipSuccess;
+                     &c->ev_verify, &c->ev_export, &c->ev_keep[0], &c->ev_keep[1], &c->ev_keep[2], &c->ev_keep[3]}) ok = ok && e->create() == hipSuccess;
     if (!ok) { frr_destroy(c); return FRR_ERR_NOMEM; }
     c->fs.color = c->own_color[0]; c->fs.depth = c->own_depth[0]; c->fs.tri_id = c->own_tri_id[0];
     // tables of frame 0 (no frame has that number), no failed command
@@ -2320,6 +2351,22 @@ int frr_geometry_list(frr_ctx *c, int list, uint64_t *ntris_setup)
     if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
     return geometry_count(c, ntris_setup);
 }
+// the GEOM command of a predicated list pass, checked: the list as frr_draw_list checks it, then the keep rule
+static int list_if_cmd(frr_ctx *c, int list, const void *dev_keep_u32, uint64_t keep_entries, uint32_t min_value, Cmd *cmd)
+{
+    int rc = list_cmd(c, list, cmd);
+    if (rc == FRR_OK) rc = rule_rc(c, keep_rule(dev_keep_u32, keep_entries, c->lists[list].n));
+    if (rc != FRR_OK) return rc;
+    cmd->pred = true; cmd->keep = (const uint32_t *)dev_keep_u32; cmd->keep_entries = keep_entries; cmd->min_value = min_value;
+    return FRR_OK;
+}
+int frr_geometry_list_if(frr_ctx *c, int list, const void *dev_keep_u32, uint64_t keep_entries, uint32_t min_value, uint64_t *ntris_setup)
+{
+    Cmd cmd;
+    int rc = list_if_cmd(c, list, dev_keep_u32, keep_entries, min_value, &cmd);
+    if (rc != FRR_OK || (rc = exec_cmd(c, cmd)) != FRR_OK) return rc;
+    return geometry_count(c, ntris_setup);
+}
 int frr_geometry_item_ranges(frr_ctx *c, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems)
 {
     if (!c || !nitems || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry pass to take item ranges from");
@@ -2421,6 +2468,13 @@ int frr_draw_list(frr_ctx *c, int list, int ps_id, int32_t x0, int32_t x1, int32
 {
     Cmd cmd;
     const int rc = list_cmd(c, list, &cmd);
+    return rc != FRR_OK ? rc : draw_pass(c, cmd, c->lists[list].n != 0, ps_id, x0, x1, y0, y1);
+}
+
+int frr_draw_list_if(frr_ctx *c, int list, const void *dev_keep_u32, uint64_t keep_entries, uint32_t min_value, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
+{
+    Cmd cmd;
+    const int rc = list_if_cmd(c, list, dev_keep_u32, keep_entries, min_value, &cmd);
     return rc != FRR_OK ? rc : draw_pass(c, cmd, c->lists[list].n != 0, ps_id, x0, x1, y0, y1);
 }
 

@@ -225,6 +225,9 @@ struct GeomArgs {
     const ListRow *items;       // [ninst]
     const uint32_t *item_first; // [ninst] exclusive prefix of the items' triangle counts (repeats where items are empty)
     const uint32_t *item_ntris; // [ninst]
+    // A predicated list pass (frr_geometry_list_if): per item 1 = kept, 0 = dropped (k_item_keep) -- every input of a dropped
+    // item emits n = 0 and is neither loaded nor shaded.  Null: every item is kept (wave-uniform, tested like `cull`).
+    const uint32_t *keep;       // [ninst]
 };
 
 // tile-row ownership over a range of tile rows: ty % world == rank (interleaved), or, blocked != 0, the rows [brow0, brow1); world <= 1: all

@@ -6,6 +6,7 @@
 #include "frr_device.h"
 #ifndef __HIPCC_RTC__
 #include <type_traits>
+#include "frr_rules.h"   // item_kept (k_item_keep)
 #endif
 
 namespace frr {
@@ -347,26 +348,32 @@ __device__ __forceinline__ uint32_t list_item_of(const GeomArgs &g, uint32_t t)
     return min(i, n - 1u);
 }
 
+// (a list pass's input t, whose item i the caller has found: list_item_of)
+template <int NF>
+__device__ __forceinline__ void tri_inputs_list(const GeomArgs &g, uint32_t t, uint32_t i, const float *vp[3], const float **inst)
+{
+    const ListRow r = g.items[i];
+    const float *verts = r.verts;
+    const uint32_t *idx = r.idx;
+    const uint32_t tl = min(t - r.first, r.ntris ? r.ntris - 1u : 0u);
+    *inst = g.inst + (size_t)i * 32;
+    if (idx) {
+        const uint32_t *ix = idx + (size_t)tl * 3;
+        const uint32_t last = r.nverts - 1u;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) vp[v] = verts + (size_t)min(ix[v], last) * NF;
+    } else {
+        const float *in = verts + (size_t)tl * (3 * NF);
+#pragma unroll
+        for (int v = 0; v < 3; ++v) vp[v] = in + v * NF;
+    }
+}
+
 template <int NF, bool IDX, bool INST = false, bool LIST = false>
 __device__ __forceinline__ void tri_inputs(const GeomArgs &g, uint32_t t, const float *vp[3], const float **inst = nullptr)
 {
     if constexpr (LIST) {
-        const uint32_t i = list_item_of(g, t);
-        const ListRow r = g.items[i];
-        const float *verts = r.verts;
-        const uint32_t *idx = r.idx;
-        const uint32_t tl = min(t - r.first, r.ntris ? r.ntris - 1u : 0u);
-        *inst = g.inst + (size_t)i * 32;
-        if (idx) {
-            const uint32_t *ix = idx + (size_t)tl * 3;
-            const uint32_t last = r.nverts - 1u;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) vp[v] = verts + (size_t)min(ix[v], last) * NF;
-        } else {
-            const float *in = verts + (size_t)tl * (3 * NF);
-#pragma unroll
-            for (int v = 0; v < 3; ++v) vp[v] = in + v * NF;
-        }
+        tri_inputs_list<NF>(g, t, list_item_of(g, t), vp, inst);
         return;
     }
     if constexpr (INST) {
@@ -680,12 +687,24 @@ __global__ __launch_bounds__(GEOM_BLOCK) void k_geom_single(GeomArgs g, DevUnifo
     bool clipped = false;
     if (t < g.ntris) {
         const float *in[3], *im = nullptr;
-        tri_inputs<NF, IDX, INST, LIST>(g, t, in, &im);
-        run_vs3<VS, INST>(u, im, in, pos, ctx);
-        n = classify(pos, clipped);
-        // frr_set_cull: an input the mode drops emits nothing, like one with a w == 0 -- decided before the block scan, so
-        // the fan slots, the clip queue and the partition test below never see it
-        if (g.cull != FRR_CULL_NONE && cull_drops(g.cull, pos)) { n = 0; clipped = false; }
+        // a predicated list pass (GeomArgs::keep): an input of a dropped item emits nothing, like one with a w == 0, and is
+        // decided before anything of it is loaded -- no index or vertex load, no vertex shader; a wave whose inputs are all
+        // dropped branches over the section
+        bool dropped = false;
+        if constexpr (LIST) {
+            const uint32_t i = list_item_of(g, t);
+            dropped = g.keep && !g.keep[i];
+            if (!dropped) tri_inputs_list<NF>(g, t, i, in, &im);
+        } else {
+            tri_inputs<NF, IDX, INST, LIST>(g, t, in, &im);
+        }
+        if (!dropped) {
+            run_vs3<VS, INST>(u, im, in, pos, ctx);
+            n = classify(pos, clipped);
+            // frr_set_cull: an input the mode drops emits nothing, like one with a w == 0 -- decided before the block scan, so
+            // the fan slots, the clip queue and the partition test below never see it
+            if (g.cull != FRR_CULL_NONE && cull_drops(g.cull, pos)) { n = 0; clipped = false; }
+        }
     }
     if (seq_is_cancelled(first_bad, g.seq, g.epoch, false)) return;   // an earlier command failed: the host replays from there (nothing written yet)
     if (bid == 0 && threadIdx.x == 0) geom_bookkeeping(g);
@@ -872,6 +891,18 @@ __global__ __launch_bounds__(256) void k_instance_mvp(const float *__restrict__ 
     dst[c] = make_float4(o[0], o[1], o[2], o[3]);
     dst[4 + c] = b;
 }
+
+#ifndef __HIPCC_RTC__
+// The keep table of a predicated list pass (GeomArgs::keep): table[i] = item_kept(keep[i], min_value) over the list's items.
+// It runs in front of the pass's geometry kernel, beside k_instance_mvp and inside the command, so the caller's buffer is
+// read at this one place in the stream and a replay reads it again.  (Not part of a user shader's program: the geometry
+// kernels read the table alone.)
+__global__ __launch_bounds__(256) void k_item_keep(const uint32_t *__restrict__ keep, uint32_t min_value, uint32_t *__restrict__ table, uint32_t nitems)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nitems) table[i] = item_kept(keep[i], min_value) ? 1u : 0u;
+}
+#endif
 
 // frr_geometry_item_ranges: out[i], i in 0..nitems, = the emission index within the pass of the first input of item i (a
 // list pass: item_first; else the items are `stride` inputs each) -- from the pass's own tables, as the tile kernel's

@@ -115,4 +115,23 @@ inline Rule buffer_rule(BufferUse use, const void *buf, uint64_t entries, int K,
     return RULE_OK;
 }
 
+// ---- the keep rule -----------------------------------------------------------------------------------------------------
+// The caller's buffer of a predicated list pass (frr_geometry_list_if / frr_draw_list_if): one u32 per item of the list, in
+// device memory.  Item i is kept iff keep[i] >= min_value, compared as unsigned -- item_kept, the one comparison the device
+// (k_item_keep) and the CPU test share.  Entries at and beyond the list's item count are ignored; a list without items
+// reads nothing, so NULL is fine there -- a misaligned pointer never is.
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+#define FRR_RULE_HD __host__ __device__
+#else
+#define FRR_RULE_HD
+#endif
+FRR_RULE_HD inline bool item_kept(uint32_t value, uint32_t min_value) { return value >= min_value; }
+
+inline Rule keep_rule(const void *keep, uint64_t keep_entries, uint64_t nitems)
+{
+    if ((!keep && nitems > 0) || ((uintptr_t)keep & 3u)) return {FRR_ERR_INVALID, "keep buffer is NULL or not 4-byte aligned"};
+    if (keep_entries < nitems) return {FRR_ERR_INVALID, "keep_entries < the list's item count"};
+    return RULE_OK;
+}
+
 } // namespace frr

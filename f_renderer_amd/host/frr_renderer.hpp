@@ -468,6 +468,18 @@ public:
     {
         check(frr_draw_list(ctx_, l.id, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
     }
+    // The same with every item i whose keep[i] < min_value (unsigned) replaced by an empty mesh (include/frr.h:
+    // frr_geometry_list_if).  dev_keep_u32: device memory, one u32 per item -- what visible_pixels(FRR_PER_ITEM, dev, n) wrote
+    // for the previous frame, or a 0/1 mask.  It is read on the library's streams behind every earlier command of this
+    // renderer and behind pending frame_wait streams, with no host wait; keep it as it is until the next sync or clear.
+    void geometry_list_if(const DrawList &l, const void *dev_keep_u32, uint64_t entries, uint32_t min_value = 1)
+    {
+        check(frr_geometry_list_if(ctx_, l.id, dev_keep_u32, entries, min_value, nullptr));
+    }
+    void draw_list_if(const DrawList &l, const void *dev_keep_u32, uint64_t entries, int pixel_shader, uint32_t min_value = 1)
+    {
+        check(frr_draw_list_if(ctx_, l.id, dev_keep_u32, entries, min_value, pixel_shader, 0, (int32_t)width_, 0, (int32_t)height_));
+    }
     // per item of the latest geometry pass (list items, instances, or one for a plain pass): the triangle id of its first setup
     // triangle and how many it emitted -- body_offset / face_offset of phong.rs:333-359 without a read-back per draw
     void item_ranges(std::vector<uint32_t> &first, std::vector<uint32_t> &count)

@@ -529,6 +529,23 @@ class Renderer:
         hr = height_range or (0, self.height)
         self._check(self._lib.frr_draw_list(self._ctx, draw_list.id, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
 
+    def geometry_list_if(self, draw_list, keep_ptr, entries, min_value=1, count=False):
+        """geometry_list with every item i whose keep[i] < min_value (unsigned) replaced by an empty mesh
+        (frr_geometry_list_if).  keep_ptr: device memory, one uint32 per item, `entries` of them -- what
+        visible_pixels("item", out_ptr=...) wrote, or a 0/1 mask of a 32-bit integer torch tensor.  The buffer is read on the
+        library's streams behind every earlier command of this renderer and behind pending frame_wait streams; it has to
+        stay as it is until the next sync() or clear()."""
+        n = C.c_uint64()
+        self._check(self._lib.frr_geometry_list_if(self._ctx, draw_list.id, keep_ptr, entries, min_value, C.byref(n) if count else None))
+        return int(n.value) if count else None
+
+    def draw_list_if(self, draw_list, keep_ptr, entries, pixel_shader, min_value=1, width_range=None, height_range=None):
+        """geometry_list_if + rasterization: draw_list of the same list without the dropped items, bit for bit; the items keep
+        their numbers (item_ranges, visible_pixels("item")), a dropped one with nothing in it (frr_draw_list_if)."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        self._check(self._lib.frr_draw_list_if(self._ctx, draw_list.id, keep_ptr, entries, min_value, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
+
     def item_ranges(self, cap=None):
         """(first, count), uint32 arrays: per item of the latest geometry pass -- the items of a list pass, the instances of
         an instanced pass, one item for a plain pass -- the triangle id of its first setup triangle and how many it emitted

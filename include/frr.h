@@ -376,6 +376,44 @@ int frr_draw_list(frr_ctx *ctx, int list, int ps_id, int32_t x0, int32_t x1, int
  * partitioned ctx.  With cap < *nitems it writes cap entries and still returns *nitems; either array may be NULL. */
 int frr_geometry_item_ranges(frr_ctx *ctx, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems);
 
+/* Predicated list passes: keep or drop each item of a list by a value in device memory -- conditional rendering.
+ * dev_keep_u32 is a caller-owned device buffer of one u32 per item.  THE KEEP RULE: item i is kept iff
+ * keep[i] >= min_value, compared as unsigned; that one comparison is the whole rule.  With min_value = 1 the buffer is
+ * exactly what frr_visible_pixels(FRR_PER_ITEM) wrote, or a 0/1 mask of 32-bit integers; a larger min_value skips what had
+ * fewer than that many pixels; min_value = 0 keeps everything.  Entries at and beyond the list's item count are ignored.
+ * A predicated list pass is BY DEFINITION frr_geometry_list / frr_draw_list over the same list with the mesh of every
+ * dropped item replaced by an empty mesh.  Hence:
+ * - The setup list, emission order, triangle ids, depth bits, RGBA8, tris_setup, frag_covered and frag_nan are those of
+ *   that list, bit for bit -- the reference's loop over the kept items.  Ids stay dense over the survivors; the frame's
+ *   running count continues behind them.
+ * - The pass still has nitems items: frr_geometry_item_ranges reports every one, a dropped item with count 0 and first =
+ *   where it would have started, and frr_visible_pixels(FRR_PER_ITEM) has nitems units with dropped items at 0 -- item k
+ *   means the same object frame after frame, which is what lets a caller feed the counts back.
+ * - tris_in grows by the list's FULL input count, dropped items included (the host does not know the mask; frr_set_cull
+ *   counts the same way); draws by 1.  A dropped item's inputs emit nothing, like inputs with a w == 0: no fan slots, no
+ *   clip-queue entries, no binning entries, no test against the partition -- and no vertex is loaded or shaded for them.
+ * - The cull mode of the call still applies to the kept items, and everything downstream of a geometry pass takes the
+ *   setup list as it is (see above).
+ * Stream order: the buffer is read on the library's streams, once per execution of the pass, before the pass's geometry
+ * kernel.  That read is ordered behind every command issued earlier on this ctx, whichever frame in flight or private
+ * stream it ran on (the frr_visible_pixels of the previous frame that wrote the buffer is the intended producer), and
+ * behind the streams of pending frr_frame_wait calls (a caller that wrote the mask on a stream of its own).  No host wait
+ * is added for either.
+ * Lifetime: the pass is logged and replayed like frr_geometry_list, and a replay reads the buffer again.  So the buffer
+ * stays allocated until the next synchronisation point or frr_clear, and until then nobody but this ctx's own later
+ * commands may change it (the rule of frr_shade_varyings' input).  A later frr_visible_pixels into the same buffer is
+ * fine: a replay restarts at the failing command and runs in order.
+ * Verification: what the pass needs of the work lists depends on data the host never sees, so it is never taken as proven
+ * and proves nothing for any other call: the draw is verified inside the call every time, like a first pass.
+ * Errors, FRR_ERR_INVALID: an unknown, freed or dead list, as frr_draw_list answers; keep_entries below the list's item
+ * count; a NULL buffer with nitems > 0; a pointer that is not 4-byte aligned.  nitems == 0 is a valid pass that emits
+ * nothing, and its buffer may be NULL.  Window and shader errors are those of frr_draw_list, in its order.  A refused
+ * call leaves the ctx drawing. */
+int frr_geometry_list_if(frr_ctx *ctx, int list, const void *dev_keep_u32, uint64_t keep_entries, uint32_t min_value,
+                         uint64_t *ntris_setup);
+int frr_draw_list_if(frr_ctx *ctx, int list, const void *dev_keep_u32, uint64_t keep_entries, uint32_t min_value, int ps_id,
+                     int32_t x0, int32_t x1, int32_t y0, int32_t y1);
+
 /* ---- face culling ------------------------------------------------------------------------- */
 
 /* The reference draws every input triangle, whichever way it faces; frr_set_cull lets a geometry pass drop those that face

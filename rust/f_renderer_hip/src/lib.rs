@@ -106,6 +106,8 @@ pub mod ffi {
         pub fn frr_drawlist_free(ctx: *mut frr_ctx, list: c_int) -> c_int;
         pub fn frr_geometry_list(ctx: *mut frr_ctx, list: c_int, ntris_setup: *mut u64) -> c_int;
         pub fn frr_draw_list(ctx: *mut frr_ctx, list: c_int, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
+        pub fn frr_geometry_list_if(ctx: *mut frr_ctx, list: c_int, dev_keep_u32: *const c_void, keep_entries: u64, min_value: u32, ntris_setup: *mut u64) -> c_int;
+        pub fn frr_draw_list_if(ctx: *mut frr_ctx, list: c_int, dev_keep_u32: *const c_void, keep_entries: u64, min_value: u32, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32) -> c_int;
         pub fn frr_geometry_item_ranges(ctx: *mut frr_ctx, id_first: *mut u32, id_count: *mut u32, cap: u64, nitems: *mut u64) -> c_int;
         // unit: 0 = FRR_PER_ITEM, 1 = FRR_PER_TRIANGLE
         pub fn frr_visible_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
