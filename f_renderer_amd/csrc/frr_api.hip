@@ -2410,8 +2410,10 @@ static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y
     const FrameState &f = c->fs;
     if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_raster before frr_geometry");
     int rc = rule_rc(c, window_rule(WINDOW_RASTER, c->W, c->H, x0, x1, y0, y1));
-    // the mesh's vertex shader -- the same user shader, another one, or a built-in -- has to hand the pixel shader its varyings
-    if (rc == FRR_OK) rc = ps_check(c, K_OF_GEOMETRY, ps_id, frr_vs_num_varyings(f.geom_vs));
+    // the mesh's vertex shader -- the same user shader, another one, or a built-in -- has to hand the pixel shader its varyings.
+    // A list without items has no vertex shader (DrawList::vs is a placeholder): K_OF_NOTHING, as in draw_pass.
+    const bool no_vs = f.geom_list >= 0 && f.geom_nitems == 0;
+    if (rc == FRR_OK) rc = ps_check(c, no_vs ? K_OF_NOTHING : K_OF_GEOMETRY, ps_id, frr_vs_num_varyings(f.geom_vs));
     if (rc != FRR_OK) return rc;
     {
         // frr_draw on a partitioned ctx keeps only the triangles that touch the rank's tile rows of ITS window; that
@@ -2439,12 +2441,14 @@ int frr_raster(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_
 
 // frr_draw*: the geometry pass `cmd`, then frr_raster of its setup list.  The raster window is known here, so a partitioned
 // ctx can skip the setup records of triangles that touch none of its tile rows (frr_geometry* alone cannot: the window comes
-// later).  raster: false for a list without items -- no vertex shader either, so nothing a pixel shader could fail to match.
+// later).  raster: false for a list without items -- no vertex shader either, so nothing a pixel shader could fail to match
+// (K_OF_NOTHING: the id has to name a shader, as frr_raster behind frr_geometry_list of it demands).
 static int draw_pass(frr_ctx *c, Cmd &cmd, bool raster, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
     cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
     const int rc = exec_cmd(c, cmd);
-    if (rc != FRR_OK || !raster) return rc;
+    if (rc != FRR_OK) return rc;
+    if (!raster) return ps_check(c, K_OF_NOTHING, ps_id, 0);
     return frr_raster(c, ps_id, x0, x1, y0, y1);
 }
 

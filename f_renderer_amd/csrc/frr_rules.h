@@ -69,28 +69,33 @@ inline Rule window_rule(WindowUse use, uint32_t W, uint32_t H, int32_t x0, int32
 // K_OF_GEOMETRY  frr_raster / frr_draw*: K is what the latest geometry pass's vertex shader writes.
 // K_OF_BUFFER    frr_shade_varyings*: K is what the caller says its buffer holds, so it has to be a K at all, and
 //                FRR_PS_DEPTH has nothing to shade.
+// K_OF_NOTHING   frr_raster / frr_draw_list* of a list without items: the pass has no vertex shader and shades nothing, so
+//                there is no K and no texture a pixel shader could miss -- the id still has to name a shader.
 // FRR_PS_COLOR reads three varyings, FRR_PS_PHONG / FRR_PS_BLINN eight and the texture of uniforms.texture_slot,
 // FRR_PS_DEPTH / FRR_PS_FLAT none (any K goes); a user pixel shader needs the K it was registered with -- `user_K`, which
 // frr_api.hip looks up (USER_K_UNKNOWN: nobody registered that id; ignored for a built-in ps_id).
-enum VaryingsFrom { K_OF_GEOMETRY, K_OF_BUFFER };
+enum VaryingsFrom { K_OF_GEOMETRY, K_OF_BUFFER, K_OF_NOTHING };
 constexpr int USER_K_UNKNOWN = -1;
 
 inline Rule pixel_shader_rule(VaryingsFrom from, int ps_id, int K, int user_K, bool texture_bound)
 {
-    const bool buffer = from == K_OF_BUFFER;
+    const bool buffer = from == K_OF_BUFFER, nothing = from == K_OF_NOTHING;
     const bool lit = ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN;
     if (ps_id >= FRR_SHADER_USER_BASE) {
         if (user_K == USER_K_UNKNOWN) return {FRR_ERR_INVALID, "unknown shader id"};
-        if (user_K != K)
+        if (user_K != K && !nothing)
             return {FRR_ERR_INVALID, buffer ? "the user pixel shader's varyings do not match the buffer's K"
                                             : "the user pixel shader's varyings do not match the vertex shader's"};
     } else {
         if (buffer && ps_id == FRR_PS_DEPTH) return {FRR_ERR_INVALID, "FRR_PS_DEPTH: nothing to shade"};
         const bool bad_K = buffer && (K < 0 || K > FRR_MAX_VARYINGS);
-        if (ps_id < 0 || ps_id > FRR_PS_BLINN || bad_K || (ps_id == FRR_PS_COLOR && K != 3) || (lit && K != 8))
-            return {FRR_ERR_INVALID, buffer ? "pixel shader does not match the buffer's K" : "pixel shader does not match the vertex shader's varyings"};
+        const bool other_K = !nothing && ((ps_id == FRR_PS_COLOR && K != 3) || (lit && K != 8));
+        if (ps_id < 0 || ps_id > FRR_PS_BLINN || bad_K || other_K)
+            return {FRR_ERR_INVALID, buffer    ? "pixel shader does not match the buffer's K"
+                                     : nothing ? "unknown shader id"
+                                               : "pixel shader does not match the vertex shader's varyings"};
     }
-    if (lit && !texture_bound) return {FRR_ERR_INVALID, "no texture bound to uniforms.texture_slot"};
+    if (lit && !texture_bound && !nothing) return {FRR_ERR_INVALID, "no texture bound to uniforms.texture_slot"};
     return RULE_OK;
 }
 

@@ -352,7 +352,10 @@ int frr_draw_instanced(frr_ctx *ctx, int mesh, int inst, int ps_id, int32_t x0, 
  * - All items must carry the same vs_id, built-in or user: otherwise the upload fails with FRR_ERR_INVALID and
  *   frr_last_error names the first offending item.
  * - nitems == 0 is a pass that emits nothing (draws still counts it); an item whose mesh has no triangles is valid at
- *   any position, several in a row too.
+ *   any position, several in a row too.  A list without items names no vertex shader: its pass has K = 0
+ *   (frr_geometry_num_varyings), and there is nothing a pixel shader could fail to match -- frr_draw_list of it, and
+ *   frr_raster behind frr_geometry_list of it, take any ps_id that names a shader (a built-in one, or a registered user
+ *   shader of any K; FRR_PS_PHONG / FRR_PS_BLINN without a texture too) and draw nothing.
  * - The list is a SNAPSHOT taken at upload: the matrices, and per mesh its pointers, counts and registration.  Freeing a
  *   mesh that a live list names kills the list: frr_geometry_list / frr_draw_list of it return FRR_ERR_INVALID,
  *   frr_drawlist_free still takes it, and a later mesh that gets the freed id does not revive it.

@@ -244,6 +244,36 @@ class Frame:
         return None
 
 
+def pixel_shader(ps_id, uniforms, ctx):
+    """renderer.rs:380 for ONE pixel: the Vec4 the pixel shader returns for the varyings ctx [K]; RuntimeError where the
+    reference would have panicked (a texel outside the texture)."""
+    c = np.zeros(O_MAXK, np.float32)
+    v = np.asarray(ctx, np.float32).reshape(-1)
+    c[:v.size] = v
+    out = np.zeros(4, np.float32)
+    if lib().o_pixel_shader(ps_id, C.byref(uniforms), _f32p(c), _f32p(out)):
+        raise RuntimeError("oracle: the reference would have panicked (texel out of bounds)")
+    return out
+
+
+def vec4_to_u8(rgba):
+    """vec4_to_u8_array (renderer.rs:7-14)"""
+    v = np.ascontiguousarray(rgba, np.float32).reshape(4)
+    out = np.zeros(4, np.uint8)
+    lib().o_vec4_to_u8(_f32p(v), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
+
+
+def shade_pixels(ps_id, uniforms, ctx):
+    """vec4_to_u8_array(pixel_shader(uniforms, ctx[i])) for every row of ctx [n, K] -> uint8 [n, 4]: what set_pixel
+    receives at renderer.rs:380-381"""
+    ctx = np.ascontiguousarray(ctx, np.float32)
+    out = np.zeros((ctx.shape[0], 4), np.uint8)
+    for i in range(ctx.shape[0]):
+        out[i] = vec4_to_u8(pixel_shader(ps_id, uniforms, ctx[i]))
+    return out
+
+
 def draw_banded(width, height, vs_inputs, vs_id, ps_id, uniforms, rgba=(30, 30, 30, 255), depth=0.0, threads=None):
     """One frame with the row range split over `threads` host threads -- the reference's own sub-window
     feature (renderer.rs:270-271): every thread runs geometry + rasterization of ALL triangles into its band

@@ -1,7 +1,7 @@
 """The argument rules of f_renderer_amd/csrc/frr_rules.h as a host program: built once per session with the host compiler
 (as tests/test_tile_order_rule.py builds its rule) and asked over stdin, one query per line, one answer line each:
   w <use> W H x0 x1 y0 y1                       window_rule        (use: 0 raster, 1 entries)
-  p <from> ps_id K user_K texture               pixel_shader_rule  (from: 0 geometry, 1 buffer; user_K -1: unknown id)
+  p <from> ps_id K user_K texture               pixel_shader_rule  (from: 0 geometry, 1 buffer, 2 nothing; user_K -1: unknown id)
   b <use> pointer entries K x1 y0 y1            buffer_rule        (use: 0 varyings out, 1 counts out, 2 varyings in)
   c                                             MAX_PASS_INPUTS
 The answer is "<status code>\t<text>" (text empty where the rule passes)."""
@@ -15,7 +15,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, INVALID, UNSUPPORTED = 0, -1, -4
 RASTER, ENTRIES = 0, 1
-FROM_GEOMETRY, FROM_BUFFER = 0, 1
+FROM_GEOMETRY, FROM_BUFFER, FROM_NOTHING = 0, 1, 2
 VARYINGS_OUT, COUNTS_OUT, VARYINGS_IN = 0, 1, 2
 USER_K_UNKNOWN = -1
 
@@ -36,7 +36,7 @@ int main()
         } else if (kind == 'p') {
             int from, ps, K, user_K, tex;
             if (scanf("%d %d %d %d %d", &from, &ps, &K, &user_K, &tex) != 5) return 2;
-            answer(pixel_shader_rule(from ? K_OF_BUFFER : K_OF_GEOMETRY, ps, K, user_K, tex != 0));
+            answer(pixel_shader_rule(from == 0 ? K_OF_GEOMETRY : from == 1 ? K_OF_BUFFER : K_OF_NOTHING, ps, K, user_K, tex != 0));
         } else if (kind == 'b') {
             int use, K; uint64_t ptr, entries; int32_t x1, y0, y1;
             if (scanf("%d %" SCNu64 " %" SCNu64 " %d %" SCNd32 " %" SCNd32 " %" SCNd32, &use, &ptr, &entries, &K, &x1, &y0, &y1) != 7) return 2;

@@ -143,12 +143,13 @@ def uniform_kw(oracle, sc, ps):
     return kw
 
 
-def oracle_list_loop(oracle, sc, ps=None, frame=None, window=None, keep=None, tri_id_base=None):
+def oracle_list_loop(oracle, sc, ps=None, frame=None, window=None, keep=None, tri_id_base=None, kw=None):
     """The loop over items on the oracle: one draw of mesh_i under model_i per item into `frame` (default: a cleared one), ids
     running on from tri_id_base (default: behind what the frame holds).  keep: per item a bool mask of the inputs that are drawn (a culled pass), or None.
+    kw: the uniform keywords of the pass other than `model` (default: the demo camera and the scenes' texture).
     Returns (frame, setup list, triangles emitted per item)."""
     ps = ps or sc.ps
-    kw = uniform_kw(oracle, sc, ps)
+    kw = uniform_kw(oracle, sc, ps) if kw is None else kw
     if frame is None:
         frame = oracle.Frame(W, H)
         frame.clear(*CLEAR)

@@ -1,0 +1,976 @@
+"""Random whole-frame command sequences and their CPU model, for tests/test_frame_model_cpu.py and
+tests/test_gpu_frame_model.py.
+
+generate(seed) yields three frames of commands the way a caller composes them: state setters (cull mode, uniforms, textures),
+geometry passes of five kinds (plain, indexed, instanced, list, predicated list), each fused (draw*) or split into geometry*
+... rasterization with up to three other commands in between, lines, wireframes, resolves, shades, per-item and per-triangle
+counts, host queries, and a frame end that is a read-back or a fenced copy.  Model applies one step at a time to the two CPU
+oracles and to NumPy copies of the caller's buffers; run_model(oracle, frames) returns what every frame must leave behind.
+Nothing here is computed from the library.
+
+What a step means is what include/frr.h says, built from the pieces the per-feature tests already hold the library to:
+  a pass        drawlist_scenes.oracle_list_loop (an instanced pass is a list of one mesh, a plain pass a list of one item);
+                per item the inputs the cull mode keeps (cull_scenes.det_f32 / keeps under the pass's matrices), none of a
+                predicate-dropped item (predicate_scenes.kept_of over the keep buffer's contents AT THE GEOMETRY CALL)
+  a split pass  recorded at geometry* (setup list, item ranges, tris_in / tris_setup / draws), drawn at rasterization: the
+                commands in between see the frame without it and its setup list with it
+  lines         lines_reference.draw_lines; a wireframe: the same over lines_reference.wireframe_segments of the setup spi
+  counts        visible_scenes.want_counts over the frame's ids
+  varyings      oracle_np.draw(..., debug=) of the pass over the frame as it was before the pass; its depth, ids and colour
+                are asserted equal to the C oracle's every time
+  shade         the C oracle's pixel shader and quantisation over the buffer's entries (oracle.cref.shade_pixels)
+
+Work lists.  The tiny-list runs start with 64 bin records and 16 fan slots; finish() (f_renderer_amd/csrc/frr_api.hip) grows
+a list that was too small to need + need / 4 + 1024 records, need + need / 8 + 1024 fan slots (need: eight times the fullest
+of the eight regions the 256-input geometry blocks allocate in).  The model computes every pass's need (fan triangles per
+block; setup triangles times 32-pixel tiles under their bounding boxes) and keeps an UPPER bound of what the growth rule can
+have left behind.  A pass whose need is at least MARGIN times that bound is a rung: it must overflow, whatever rounding
+exec_geometry applies.  Two meshes are made for that, r1 and r2; each seed meets r1 in an earlier frame than r2.
+
+Left out: partitions, user shaders, x0 < 0, several rasters of one geometry pass, abandoned geometry passes, state setters
+that change the vertex shader's uniforms between a geometry* and its rasterization, resolves behind the rasterization of a
+rung mesh (the NumPy oracle's cost).  The generator issues set_cull between passes only; cull_inside_split() is the fixed
+sequence with one inside split passes."""
+import ctypes
+import hashlib
+
+import numpy as np
+
+from f_renderer_amd import scenes
+from oracle import oracle_np as onp
+
+from . import cull_scenes as CS
+from . import drawlist_scenes as D
+from . import instanced_scenes as S
+from . import lines_reference as R
+from . import predicate_scenes as P
+from . import varyings_scenes as V
+from . import visible_scenes as VIS
+
+F = np.float32
+W, H = S.W, S.H
+CLEAR = S.CLEAR
+FULL = (0, W, 0, H)
+SUB = (24, 120, 8, 88)                         # x0 > 0, y0 > 0, x1 < W: depth stride 120, partial tiles on every side
+NONE = 0xFFFFFFFF
+SENTINEL_BITS = V.SENTINEL_BITS
+ENTRIES = W * H                                # entries of every varyings buffer
+COUNT_CAP = 16384                              # entries of every count buffer
+SEEDS = range(24)
+FRAMES, MAX_STEPS = 3, 10
+MARGIN = 4
+TINY = {"bin_capacity": 64, "fan_capacity": 16}
+GEOM_BLOCK, FAN_REGIONS = 256, 8
+NOOP_SHARE = 0.2
+ORDINARY_FAN_NEED = 700                        # the most fan slots a pass that is no rung may need
+
+VS_PS = {"PHONG": ("DEPTH", "FLAT", "PHONG", "BLINN"), "GOURAUD": ("DEPTH", "FLAT", "COLOR")}
+VS_K = {"PHONG": 8, "GOURAUD": 3}
+PIN_VS = {"CLIP_COLOR": (3, ("DEPTH", "FLAT", "COLOR"))}   # what the generator never draws: the pinning sequences of the CPU tests
+K_PS = {8: ("FLAT", "PHONG", "BLINN"), 3: ("FLAT", "COLOR")}
+KINDS = ("plain", "indexed", "instanced", "list", "list_if")
+COMMANDS = ("lines", "wireframe", "resolve", "shade", "count_item", "count_triangle")
+QUERIES = ("item_ranges", "setup_triangles", "stats", "sync")
+WRITERS = ("geom", "draw", "lines", "wireframe", "resolve", "shade", "count", "set_cull", "set_uniforms", "set_texture")
+
+UP, FOVY, ZN, ZF = (0.0, 1.0, 0.0), scenes.demo_camera(W, H)[3], 0.1, 100.0
+CAMERAS = [((0.0, 1.0, 3.0), (0.0, 0.0, 0.0)), ((0.9, 0.6, 2.6), (0.0, 0.05, 0.0))]
+LIGHTS = [(1.2, 1.0, 2.0), (-1.5, 2.0, 1.0)]
+FLATS = [(1.0, 1.0, 1.0, 1.0), (1.0, 0.5, 0.25, 1.0), (0.1, 0.7, 0.9, 0.5)]
+WIRE_COLORS = [(255, 200, 0, 255), (0, 255, 120, 255)]
+MIN_VALUES = (1, 150)
+MASKS = {"mask0": np.array([1, 0, 1, 1, 0, 1, 0, 1], np.uint32), "mask1": np.array([0, 7, 300, 0, 149, 150, 0, 2], np.uint32),
+         "mask2": np.zeros(8, np.uint32)}
+
+
+class Undefined(Exception):
+    """the step is refused, or its result is not defined, at this place of the sequence"""
+
+
+# ---- the fixed material: meshes, matrices, textures, line lists ------------------------------------------------------------
+
+def _big(n, seed, radius=3.0):
+    """n triangles of `radius` object units around points in front of both cameras: every one crosses several frustum planes and
+    is clipped into a fan (7 to 9 fan triangles on average)"""
+    rs = np.random.RandomState(seed)
+    t = np.zeros((n, 3, 8), F)
+    c = np.stack([rs.uniform(-0.8, 0.8, n), rs.uniform(-0.5, 0.5, n), rs.uniform(-1.0, 0.5, n)], 1)
+    th0 = rs.uniform(0, 2 * np.pi, n)
+    for k in range(3):
+        th = th0 + k * 2 * np.pi / 3 + rs.uniform(-0.4, 0.4, n)
+        t[:, k, 0], t[:, k, 1] = c[:, 0] + radius * np.cos(th), c[:, 1] + radius * np.sin(th)
+        t[:, k, 2] = c[:, 2] + rs.uniform(-0.3, 0.3, n)
+        t[:, k, 3], t[:, k, 4] = 0.5 + 0.5 * np.cos(th), 0.5 + 0.5 * np.sin(th)
+        t[:, k, 5:8] = (0.0, 0.0, 1.0)
+    return t
+
+
+def _rung2():
+    """17 geometry blocks: blocks 0, 8 and 16 -- the three that allocate in fan region 0 -- hold 256 such triangles each, the
+    others small triangles in view"""
+    rs = np.random.RandomState(103)
+    n = 17 * GEOM_BLOCK
+    t = np.zeros((n, 3, 8), F)
+    c = np.stack([rs.uniform(-1.0, 1.0, n), rs.uniform(-0.7, 0.7, n), rs.uniform(-0.8, 0.4, n)], 1)
+    for k in range(3):
+        t[:, k, :3] = c + rs.uniform(-0.04, 0.04, (n, 3))
+        t[:, k, 3:5] = rs.uniform(0, 1, (n, 2))
+        t[:, k, 5:8] = (0.0, 0.0, 1.0)
+    for b in (0, 8, 16):
+        t[b * GEOM_BLOCK:(b + 1) * GEOM_BLOCK] = _big(GEOM_BLOCK, 104 + b)
+    return t
+
+
+_GRID = S.patch_grid(8, 8)                     # the indexed mesh: 81 vertices under 128 triangles
+MESHES = {
+    "p40": S.patch(40), "p100": S.patch(100), "p257": S.patch(257), "spiky": D.spiky(30),
+    "torus": scenes.torus(10, 6, R=0.3, r=0.12), "grid": np.ascontiguousarray(_GRID[0][_GRID[1].astype(np.int64)]),
+    "empty": np.zeros((0, 3, 8), F), "r1": _big(128, 101), "r2": _rung2(),
+}
+INDEXED = {"grid": _GRID}
+RUNGS = {1: "r1", 2: "r2"}
+SMALL = ("p40", "p100", "spiky", "torus", "grid")
+_IDENT = np.eye(4, dtype=F).reshape(16)
+MODELS = np.concatenate([S.clipped_models(), S.grid_models(7), CS.mirrored_model()[None], CS.left_model()[None], _IDENT[None]]).astype(F)
+M_CLIPPED, M_GRID, M_MIRROR, M_LEFT, M_IDENT = range(0, 6), range(6, 13), 13, 14, 15
+TEXTURES = [S.texture(), D.place_textures()[1]]
+
+
+def _line_list(seed, n=14):
+    rs = np.random.RandomState(seed)
+    xy = np.stack([rs.randint(0, W, n), rs.randint(0, H, n), rs.randint(0, W, n), rs.randint(0, H, n)], 1).astype(np.uint32)
+    xy[0, 2] = xy[0, 0]                        # a vertical, a horizontal and a single-pixel segment
+    xy[1, 3] = xy[1, 1]
+    xy[2, 2:] = xy[2, :2]
+    return xy, rs.randint(0, 256, (n, 4)).astype(np.uint8)
+
+
+LINES = [_line_list(7), _line_list(8, 9)]
+
+
+def buffer_names():
+    """the caller's device buffers: two pools (frames alternate), each with two varyings buffers per K and three count buffers"""
+    return [f"{p}.{b}" for p in "AB" for b in ("v8a", "v8b", "v3a", "v3b", "c0", "c1", "c2")]
+
+
+def buffer_k(name):
+    return {"v8": 8, "v3": 3}.get(name.split(".")[1][:2], 0)
+
+
+def new_buffers():
+    out = {}
+    for name in buffer_names():
+        k = buffer_k(name)
+        out[name] = np.full((ENTRIES, k) if k else COUNT_CAP, SENTINEL_BITS, np.uint32)
+    return out
+
+
+def uniform_kw(mod, cam, light, flat):
+    """the uniform keywords of a state for `mod` = the C oracle's binding or f_renderer_amd (set_look_at / set_perspective)"""
+    eye, at = CAMERAS[cam]
+    return dict(view=mod.set_look_at(eye, at, UP), proj=mod.set_perspective(FOVY, float(W) / float(H), ZN, ZF), view_pos=eye,
+                light_pos=LIGHTS[light], flat_color=FLATS[flat])
+
+
+# ---- geometry of one (mesh, matrix) under one camera, computed once ----------------------------------------------------------
+
+_GEOM, _DET, _NP_CTX = {}, {}, {}
+
+
+class _Memo(dict):
+    """results of the oracles by a digest of everything they depend on (the sensitivity runs repeat most steps unchanged);
+    the oldest entries leave when it is full"""
+
+    def __init__(self, size):
+        super().__init__()
+        self.size = size
+
+    def put(self, key, value):
+        if len(self) >= self.size:
+            for k in list(self)[:self.size // 4]:
+                del self[k]
+        self[key] = value
+        return value
+
+
+_RASTER, _SHADE, _PAINT = _Memo(400), _Memo(400), _Memo(200)
+
+
+def _digest(*parts):
+    h = hashlib.sha1()
+    for x in parts:
+        h.update(x if isinstance(x, (bytes, bytearray, memoryview)) else x.tobytes() if isinstance(x, np.ndarray) else repr(x).encode())
+    return h.digest()
+
+
+def painted(xyxy, rgba, W=W, H=H):
+    """lines_reference.draw_lines of a list as (pixel indices, colours), each pixel once with the colour of its last write"""
+    key = _digest(np.ascontiguousarray(xyxy), np.ascontiguousarray(rgba), (W, H))
+    if key not in _PAINT:
+        last = {}
+        for (x1, y1, x2, y2), c in zip(np.asarray(xyxy).tolist(), np.asarray(rgba, np.uint8)):
+            if R.panics(x1, y1, x2, y2, W, H):
+                raise IndexError("draw_line leaves the buffer")
+            for i in R.line_indices(x1, y1, x2, y2, W):
+                last[i] = c
+        idx = np.fromiter(last.keys(), np.int64, len(last))
+        _PAINT.put(key, (idx, np.array(list(last.values()), np.uint8).reshape(-1, 4)))
+    return _PAINT[key]
+
+
+def _item_geometry(oracle, mesh, mi, cam, light, vs, W=W, H=H):
+    """(setup list of every input concatenated, triangles each input emits)"""
+    key = (mesh, mi, cam, light, vs, W, H)
+    if key not in _GEOM:
+        kw = uniform_kw(oracle, cam, light, 0)
+        u = oracle.make_uniforms(model=MODELS[mi], **kw)
+        vs_id = getattr(oracle, "VS_" + vs)
+        parts = [oracle.geometry_processing(W, H, t, vs_id, u) for t in MESHES[mesh]]
+        counts = np.array([len(p) for p in parts], np.int64)
+        setup = np.concatenate(parts) if parts else np.zeros((0, 3), oracle.VERTEX_DTYPE)
+        _GEOM[key] = (setup, counts)
+    return _GEOM[key]
+
+
+def _det(mesh, mi, cam, vs):
+    """the facing determinant of every input (cull_scenes.det_f32 of oracle_np.vertex_shader's clip positions)"""
+    key = (mesh, mi, cam)
+    if key not in _DET:
+        eye, at = CAMERAS[cam]
+        u = onp.Uniforms(model=MODELS[mi], view=onp.set_look_at(eye, at, UP), proj=onp.set_perspective(FOVY, float(W) / float(H), ZN, ZF))
+        vs_id = getattr(onp, "VS_" + vs)
+        clip = np.array([[onp.vertex_shader(vs_id, u, v)[0] for v in t] for t in MESHES[mesh]], F).reshape(-1, 3, 4)
+        _DET[key] = CS.det_f32(clip)
+    return _DET[key]
+
+
+def growth(need, extra):
+    """what finish() grows a list to after a pass that needed `need`: need + need / extra + 1024"""
+    return need + need // extra + 1024
+
+
+def pass_needs(setup, fans):
+    """(fan slots, bin records) a pass needs, as finish() counts them: eight times the fullest region's fan triangles (block b
+    of 256 inputs allocates in region b % 8; `fans`: fan triangles per submitted input, 0 for one that is not clipped or emits
+    nothing); setup triangles times the 32-pixel tiles under their bounding boxes"""
+    region = np.zeros(FAN_REGIONS, np.int64)
+    for b in range(0, len(fans), GEOM_BLOCK):
+        region[(b // GEOM_BLOCK) % FAN_REGIONS] += int(fans[b:b + GEOM_BLOCK].sum())
+    spi = setup["spi"].astype(np.int64)
+    if spi.shape[0]:
+        lo = np.clip(spi.min(axis=1), 0, [W, H])
+        hi = np.clip(spi.max(axis=1), 0, [W, H])
+        tiles = np.maximum((hi + 31) // 32 - lo // 32, 0)
+        bins = int((tiles[:, 0] * tiles[:, 1] * ((hi > lo).all(axis=1))).sum())
+    else:
+        bins = 0
+    return int(region.max()) * FAN_REGIONS, bins
+
+
+class _Pass:
+    pass
+
+
+def _vs_k(vs):
+    return VS_K[vs] if vs in VS_K else PIN_VS[vs][0]
+
+
+def _vs_ps(vs):
+    return VS_PS[vs] if vs in VS_PS else PIN_VS[vs][1]
+
+
+# ---- the model ---------------------------------------------------------------------------------------------------------------
+
+class Model:
+    """The state a sequence of steps leaves behind: the frame on the C oracle, the caller's buffers, the state that travels
+    with commands, the latest geometry pass, the host's statistics, and the upper bounds of the work lists."""
+
+    def __init__(self, oracle, size=(W, H), clear=CLEAR):
+        self.o, (self.W, self.H), self.clear = oracle, size, clear
+        self.cull, self.cam, self.light, self.flat, self.slot, self.tex = 0, 0, 0, 0, 0, [0, 1]
+        self.frame = oracle.Frame(*size)
+        self.window, self.fno = FULL, -1
+        self.tris_in = self.draws = self.emitted = 0
+        self.last = None
+        self.bufs = new_buffers()
+        self.prov = {}                         # count buffer -> what the latest frr_visible_pixels into it was
+        self.fan_cap, self.bin_cap = TINY["fan_capacity"], TINY["bin_capacity"]
+        self.crossed = False                   # a rung was crossed in this frame
+        self.changed = False                   # the latest step changed a target or a buffer
+
+    def copy(self):
+        m = Model.__new__(Model)
+        m.__dict__.update(self.__dict__)
+        m.tex = list(self.tex)
+        m.frame = self.o.Frame(self.W, self.H)
+        m.frame.color[...] = self.frame.color
+        m.frame.depth[...] = self.frame.depth
+        m.frame.tri_id[...] = self.frame.tri_id
+        ctypes.memmove(ctypes.byref(m.frame.counters), ctypes.byref(self.frame.counters), ctypes.sizeof(self.frame.counters))
+        m.bufs = {k: v.copy() for k, v in self.bufs.items()}
+        m.prov = dict(self.prov)
+        return m
+
+    # -- uniforms of the moment --
+    def _uniforms(self):
+        return uniform_kw(self.o, self.cam, self.light, self.flat), self.tex[self.slot]
+
+    def _window_entries(self):
+        x0, x1, y0, y1 = self.window
+        return (y1 - y0) * x1
+
+    def _window_index(self):
+        x0, x1, y0, y1 = self.window
+        cy, cx = np.meshgrid(np.arange(y0, y1), np.arange(x0, x1), indexing="ij")
+        return (cy - y0) * x1 + (cx - x0), cy - y0, cx - x0
+
+    def _latest(self, cleared_ok=False):
+        if self.last is None or (self.last.cleared and not cleared_ok):
+            raise Undefined("no geometry pass in this frame yet")
+        return self.last
+
+    # -- steps --
+    def apply(self, s):
+        """apply one step; returns the host's answer of a query, or None"""
+        self.changed = False
+        return getattr(self, "_" + s["op"])(s)
+
+    def _clear(self, s):
+        self.frame.clear(*self.clear)
+        self.frame.counters = type(self.frame.counters)()
+        self.window, self.fno = tuple(s["window"]), self.fno + 1
+        self.tris_in = self.draws = self.emitted = 0
+        self.crossed = False
+        if self.last is not None:
+            self.last = self._copy_pass(self.last)
+            self.last.cleared = True
+
+    @staticmethod
+    def _copy_pass(p):
+        q = _Pass()
+        q.__dict__.update(p.__dict__)
+        return q
+
+    def _set_cull(self, s):
+        self.cull = s["mode"]
+
+    def _set_uniforms(self, s):
+        if self.last is not None and not self.last.cleared and not self.last.rastered and (s["cam"], s["light"]) != (self.cam, self.light):
+            raise Undefined("the model does not change the vertex shader's uniforms inside a split pass")
+        self.cam, self.light, self.flat, self.slot = s["cam"], s["light"], s["flat"], s["slot"]
+
+    def _set_texture(self, s):
+        self.tex[s["slot"]] = s["image"]
+
+    def _geom(self, s):
+        if self.last is not None and not self.last.cleared and not self.last.rastered:
+            raise Undefined("the model rasters every geometry pass once")
+        items, vs = [tuple(i) for i in s["items"]], s["vs"]
+        if s["kind"] == "list_if":
+            kept = P.kept_of(self.bufs[s["keep"]].reshape(-1)[:len(items)], s["min"]) if s["keep"] in self.bufs else \
+                P.kept_of(MASKS[s["keep"]][:len(items)], s["min"])
+        else:
+            kept = np.ones(len(items), bool)
+        p = _Pass()
+        # (a list without items names no vertex shader: its K is 0, and any pixel shader goes with nothing)
+        p.items, p.vs, p.K, p.kind, p.cam, p.light = items, vs, _vs_k(vs) if items else 0, s["kind"], self.cam, self.light
+        p.keep, p.per_item, setups, fans = [], [], [], []
+        for i, (mesh, mi) in enumerate(items):
+            setup, counts = _item_geometry(self.o, mesh, mi, self.cam, self.light, vs, self.W, self.H)
+            k = np.full(counts.size, bool(kept[i]), bool)
+            if self.cull != CS.NONE and counts.size:
+                k &= CS.keeps(_det(mesh, mi, self.cam, vs), self.cull)
+            emit = np.where(k, counts, 0)
+            p.keep.append(k)
+            p.per_item.append(int(emit.sum()))
+            fans.append(np.where(emit > 1, emit, 0))
+            setups.append(setup[np.repeat(k, counts)])
+        p.setup = np.concatenate(setups) if setups else np.zeros((0, 3), self.o.VERTEX_DTYPE)
+        p.base, p.emit, p.rastered, p.cleared = self.emitted, sum(p.per_item), False, False
+        p.fan_need, p.bin_need = pass_needs(p.setup, np.concatenate(fans) if fans else np.zeros(0, np.int64))
+        p.fan_rung, p.bin_rung = p.fan_need >= MARGIN * self.fan_cap, p.bin_need >= MARGIN * self.bin_cap
+        self.crossed |= p.fan_rung or p.bin_rung
+        if p.fan_need > TINY["fan_capacity"]:     # the pass may have overflowed: what the growth rule can have left
+            self.fan_cap = max(self.fan_cap, growth(p.fan_need, 8))
+        if p.bin_need > TINY["bin_capacity"]:
+            self.bin_cap = max(self.bin_cap, growth(p.bin_need, 4))
+        self.tris_in += sum(MESHES[m].shape[0] for m, _ in items)
+        self.draws += 1
+        self.emitted += p.emit
+        self.last = p
+
+    def _raster(self, s):
+        p = self._latest()
+        if p.rastered:
+            raise Undefined("the model rasters every geometry pass once")
+        if p.items and s["ps"] not in _vs_ps(p.vs):
+            raise Undefined("a pixel shader for another K")
+        if (p.cam, p.light) != (self.cam, self.light):
+            raise Undefined("the model does not change the vertex shader's uniforms inside a split pass")
+        p = self.last = self._copy_pass(p)
+        f = self.frame
+        p.before = (f.color.copy(), f.depth.copy(), f.tri_id.copy())
+        sc = D.Scene([D.Mesh(MESHES[m]) for m, _ in p.items], range(len(p.items)), MODELS[[mi for _, mi in p.items]].reshape(-1, 16), p.vs, s["ps"])
+        kw, image = self._uniforms()
+        kw["tex"] = self.o.Texture(TEXTURES[image])
+        key = _digest(*p.before, (p.items, p.vs, s["ps"], p.cam, p.light, self.flat, image, self.window, p.base), *p.keep,
+                      bytes(f.counters))
+        if key in _RASTER:
+            p.after, counters = _RASTER[key]
+            f.color[...], f.depth[...], f.tri_id[...] = p.after
+            ctypes.memmove(ctypes.byref(f.counters), counters, len(counters))
+        else:
+            _, setup, per = D.oracle_list_loop(self.o, sc, s["ps"], frame=f, window=self.window, keep=p.keep, tri_id_base=p.base, kw=kw)
+            assert per == p.per_item and setup.tobytes() == p.setup.tobytes(), "the split pass's geometry is the fused pass's"
+            p.after = (f.color.copy(), f.depth.copy(), f.tri_id.copy())
+            _RASTER.put(key, (p.after, bytes(f.counters)))
+        p.rastered, p.ps, p.state = True, s["ps"], (self.flat, image)
+        self.changed = any((a != b).any() for a, b in zip(p.before[1:], p.after[1:])) or (p.before[0] != p.after[0]).any() or p.emit > 0
+
+    def _draw(self, s):
+        self._geom(s)
+        self._raster(s)
+
+    def _lines(self, s):
+        self._paint(*LINES[s["list"]])
+
+    def _paint(self, xyxy, rgba):
+        idx, col = painted(xyxy, rgba, self.W, self.H)
+        flat = self.frame.color.reshape(-1, 4)
+        self.changed = bool((flat[idx] != col).any())
+        flat[idx] = col
+
+    def _wireframe(self, s):
+        p = self._latest()
+        if not hasattr(p, "segs"):
+            p.segs = R.wireframe_segments(p.setup["spi"], self.W, self.H)[0]       # (of the pass: whoever holds it later finds it there)
+        segs = p.segs
+        if segs:
+            self._paint(np.array(segs, np.uint32), np.tile(np.array(WIRE_COLORS[s["color"]], np.uint8), (len(segs), 1)))
+
+    def _owned(self, p):
+        t = self.frame.tri_id
+        return (t != NONE) & (t >= p.base) & (t < p.base + p.emit)
+
+    def _resolve(self, s):
+        p = self._latest()
+        buf = self.bufs[s["buf"]]
+        if buffer_k(s["buf"]) != p.K:
+            raise Undefined("a buffer of another K")
+        if not p.rastered or not p.emit:
+            return
+        n = self._window_entries()
+        own = self._owned(p)[:n]
+        ctx = self._np_ctx(p)[:n]
+        assert not np.isnan(ctx[own]).all(axis=1).any(), "an owned entry without varyings"
+        before = buf[:n][own].copy()
+        buf[:n][own] = ctx[own].view(np.uint32)
+        self.changed = (before != buf[:n][own]).any()
+
+    def _np_ctx(self, p):
+        """the interpolated varyings of every fragment of the latest pass that passed the depth test, by depth index: the NumPy
+        oracle's draw of the pass over the frame as it was before, held to the C oracle's frame after it"""
+        color, depth, tri = (a.copy() for a in p.before)
+        key = hashlib.sha1(repr((p.items, p.vs, p.ps, p.cam, p.light, p.state, self.window, p.base, self.W, self.H, [k.tobytes() for k in p.keep])).encode()
+                           + depth.tobytes() + tri.tobytes()).hexdigest()
+        if key in _NP_CTX:
+            return _NP_CTX[key]
+        eye, at = CAMERAS[p.cam]
+        flat, image = p.state
+        ps = V.zero_ps if p.ps == "DEPTH" else getattr(onp, "PS_" + p.ps)
+        debug, base = {}, p.base
+        for (mesh, mi), keep, emit in zip(p.items, p.keep, p.per_item):
+            tris = MESHES[mesh][keep]
+            if tris.shape[0]:
+                u = onp.Uniforms(model=MODELS[mi], view=onp.set_look_at(eye, at, UP), proj=onp.set_perspective(FOVY, float(W) / float(H), ZN, ZF),
+                                 view_pos=eye, flat_color=FLATS[flat], tex=TEXTURES[image], light_pos=LIGHTS[p.light])
+                setup, _ = onp.draw(self.W, self.H, tris, getattr(onp, "VS_" + p.vs), ps, u, color, depth, tri, window=self.window, tri_id_base=base, debug=debug)
+                assert len(setup) == emit
+            base += emit
+        np.testing.assert_array_equal(tri, p.after[2], err_msg="the NumPy oracle's ids differ from the C oracle's")
+        np.testing.assert_array_equal(depth.view(np.uint32), p.after[1].view(np.uint32), err_msg="the NumPy oracle's depth differs from the C oracle's")
+        if p.ps != "DEPTH":
+            np.testing.assert_array_equal(color, p.after[0], err_msg="the NumPy oracle's colour differs from the C oracle's")
+        _NP_CTX[key] = debug.get("ctx", np.full((self.W * self.H, p.K), np.nan, F))
+        return _NP_CTX[key]
+
+    def _shade(self, s):
+        buf, K = self.bufs[s["buf"]], buffer_k(s["buf"])
+        if s["ps"] not in K_PS[K]:
+            raise Undefined("a pixel shader for another K")
+        first, count = s["ids"]
+        idx, ry, rx = self._window_index()
+        ids = self.frame.tri_id[idx].astype(np.int64)
+        sel = (ids != NONE) & (((ids - first) & 0xFFFFFFFF) < count)
+        if not sel.any():
+            return
+        kw, image = self._uniforms()
+        kw["tex"] = self.o.Texture(TEXTURES[image])
+        ctx = np.ascontiguousarray(buf[idx[sel]])
+        key = _digest((s["ps"], self.cam, self.light, self.flat, image), ctx)
+        rgba = _SHADE[key] if key in _SHADE else \
+            _SHADE.put(key, self.o.shade_pixels(getattr(self.o, "PS_" + s["ps"]), self.o.make_uniforms(**kw), ctx.view(F)))
+        before = self.frame.color[ry[sel], rx[sel]].copy()
+        self.frame.color[ry[sel], rx[sel]] = rgba
+        self.changed = (before != rgba).any()
+
+    def _count(self, s):
+        buf, e = self.bufs[s["buf"]], int(s["entries"])
+        if not 0 < e <= COUNT_CAP:
+            raise Undefined("out_entries")
+        x0, x1, y0, y1 = self.window
+        if s["unit"] == "item":
+            p = self._latest(cleared_ok=True)
+            n = len(p.items)
+            out = np.zeros(e, np.uint32) if p.cleared else \
+                VIS.want_counts(self.frame.tri_id, (x0, x1), (y0, y1), bounds=VIS.bounds_of(p.per_item, p.base), entries=e)
+        else:
+            p = self._latest()
+            n = p.base + p.emit
+            out = VIS.want_counts(self.frame.tri_id, (x0, x1), (y0, y1), units=n, entries=e)
+        self.changed = (buf[:e] != out).any()
+        buf[:e] = out
+        self.prov[s["buf"]] = dict(frame=self.fno, unit=s["unit"], n=n, entries=e, items=p.items, kind=p.kind)
+
+    def _item_ranges(self, s):
+        p = self._latest()
+        return dict(first=VIS.bounds_of(p.per_item, p.base)[:-1], count=np.array(p.per_item, np.uint32))
+
+    def _setup_triangles(self, s):
+        p = self._latest()
+        return dict(spi=p.setup["spi"].copy(), spf=p.setup["spf"].copy(), rhw=p.setup["rhw"].copy())
+
+    def stats(self):
+        c = self.frame.counters
+        return dict(tris_in=self.tris_in, tris_setup=self.emitted, draws=self.draws, frag_covered=int(c.frag_covered), frag_nan=int(c.frag_nan))
+
+    def _stats(self, s):
+        return self.stats()
+
+    def _sync(self, s):
+        return None
+
+    def _readback(self, s):
+        return None
+
+    _fenced = _readback
+
+    def outputs(self):
+        """what a frame end is compared with"""
+        f = self.frame
+        return dict(color=f.color.copy(), depth=f.depth.copy(), tri_id=f.tri_id.copy(), stats=self.stats(),
+                    bufs={k: v.copy() for k, v in self.bufs.items()}, crossed=self.crossed)
+
+
+def run_frames(model, frames, skip=None):
+    """apply frames (lists of steps) to `model`; skip: a set of id(step) left out.  Returns per frame the model's outputs at the
+    frame end with the queries' answers, in order, under "answers"."""
+    out = []
+    for steps in frames:
+        answers = []
+        for s in steps:
+            if skip and id(s) in skip:
+                continue
+            a = model.apply(s)
+            if s["op"] in QUERIES:
+                answers.append((s["op"], a))
+        o = model.outputs()
+        o["answers"] = answers
+        out.append(o)
+    return out
+
+
+def run_model(oracle, frames, **kw):
+    """what every frame of a sequence must leave behind: per frame the colour, depth and triangle ids, the statistics, every
+    caller buffer, the host queries' answers in order, and whether the model says a rung is crossed in it"""
+    return run_frames(Model(oracle, **kw), frames)
+
+
+def same_outputs(a, b):
+    """do two frame outputs agree in everything that is compared?"""
+    if a["stats"] != b["stats"] or len(a["answers"]) != len(b["answers"]):
+        return False
+    for k in ("color", "depth", "tri_id"):
+        if a[k].tobytes() != b[k].tobytes():
+            return False
+    if any(a["bufs"][k].tobytes() != b["bufs"][k].tobytes() for k in a["bufs"]):
+        return False
+    for (na, xa), (nb, xb) in zip(a["answers"], b["answers"]):
+        if na != nb or (xa is None) != (xb is None):
+            return False
+        if isinstance(xa, dict) and any(np.asarray(xa[k]).tobytes() != np.asarray(xb[k]).tobytes() for k in xa):
+            return False
+    return True
+
+
+def pass_partner(steps, s):
+    """the rasterization that belongs to the geometry step s of a split pass"""
+    i = next(k for k, x in enumerate(steps) if x is s)
+    return next(x for x in steps[i + 1:] if x["op"] == "raster")
+
+
+def insensitive_steps(oracle, frames):
+    """The writing steps, not marked as no-ops, whose removal changes no compared output (a split pass is removed as a whole,
+    the commands inside it stay).  A removal after which a later step is refused or undefined counts as a change."""
+    starts, m = [], Model(oracle)
+    want = []
+    for steps in frames:
+        starts.append(m.copy())
+        want += run_frames(m, [steps])
+    bad = []
+    for fi, steps in enumerate(frames):
+        for s in steps:
+            if s["op"] not in WRITERS or s.get("noop"):
+                continue
+            skip = {id(s)}
+            if s["op"] == "geom":
+                skip.add(id(pass_partner(steps, s)))
+            try:
+                m = starts[fi].copy()
+                same = all(same_outputs(run_frames(m, [frames[k]], skip)[0], want[k]) for k in range(fi, len(frames)))
+            except (Undefined, RuntimeError):
+                same = False
+            if same:
+                bad.append((fi, s))
+    return bad
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------------------
+
+class _Gen:
+    """Draws steps with np.random.RandomState(seed) and consults the model for each: a step that is refused or undefined at its
+    place is drawn again, a step that writes is kept only if it changes a target or a buffer (or is a no-op on purpose, while
+    the seed's share of those allows one more), a state setter only in front of a command that comes out differently under it."""
+
+    def __init__(self, oracle, seed):
+        self.o, self.seed, self.rng, self.m = oracle, seed, np.random.RandomState(seed), Model(oracle)
+        self.frames, self.steps, self.reserve = [], None, 0
+        self.noops = self.total = 0
+        self.ranges = []                       # (first, count) of the items of this frame's rastered passes
+        self.resolved = []                     # varyings buffers a resolve has written into
+        self.geom_step = None
+
+    def pick(self, seq, p=None):
+        return seq[self.rng.choice(len(seq), p=p)]
+
+    def room(self):
+        """steps this frame can still take before its end (the clear does not count, the frame end does)"""
+        return MAX_STEPS - 1 - (len(self.steps) - 1) - self.reserve
+
+    def noop_allowed(self):
+        return self.noops + 1 <= NOOP_SHARE * (self.total + 1)
+
+    def probe(self, steps):
+        """(a digest of the targets and the setup list after `steps` on a copy of the model, did the last one change
+        anything), or (None, False) where a step is refused or undefined"""
+        trial = self.m.copy()
+        try:
+            for s in steps:
+                trial.apply(s)
+        except (Undefined, RuntimeError):
+            return None, False
+        f, p = trial.frame, trial.last
+        self.probed = trial
+        return (f.color.tobytes(), f.depth.tobytes(), f.tri_id.tobytes(), p.setup.tobytes() if p is not None else b"", trial.emitted), trial.changed
+
+    def add(self, s, noop_ok=False, force=False):
+        if self.room() < (2 if s["op"] == "geom" else 1) and not force:
+            return False
+        trial = self.m.copy()
+        try:
+            trial.apply(s)
+        except (Undefined, RuntimeError):
+            return False
+        if s["op"] in ("lines", "wireframe", "resolve", "shade", "count", "draw", "raster") and not trial.changed:
+            if not force and not (noop_ok and self.noop_allowed()):
+                return False
+            (self.geom_step if s["op"] == "raster" else s)["noop"] = True
+            self.noops += 1
+        self.m = trial
+        self.steps.append(s)
+        self.total += 1
+        if s["op"] == "geom":
+            self.geom_step = s
+        if s["op"] in ("draw", "raster"):
+            p = trial.last
+            first = VIS.bounds_of(p.per_item, p.base)
+            self.ranges += [(int(first[i]), int(c)) for i, c in enumerate(p.per_item)]
+            (self.geom_step if s["op"] == "raster" else s).update(fan_need=p.fan_need, bin_need=p.bin_need, fan_rung=bool(p.fan_rung),
+                                                                   bin_rung=bool(p.bin_rung))
+        return True
+
+    # -- candidates --
+    def setter(self, inside):
+        """inside a split pass only what the pixel shader reads changes (the model's restriction)"""
+        rng, m = self.rng, self.m
+        kind = self.pick(("cull", "uniforms", "texture"), p=(0.0, 0.6, 0.4) if inside else (0.35, 0.45, 0.2))
+        if kind == "cull":
+            return dict(op="set_cull", mode=int(self.pick([x for x in (0, 1, 2) if x != m.cull])))
+        if kind == "texture":
+            slot = m.slot if rng.rand() < 0.8 else 1 - m.slot      # (mostly the slot the pixel shaders sample)
+            return dict(op="set_texture", slot=slot, image=1 - m.tex[slot])
+        s = dict(op="set_uniforms", cam=m.cam, light=m.light, flat=m.flat, slot=m.slot)
+        what = self.pick(("flat", "slot")) if inside else self.pick(("cam", "light", "flat", "slot"), p=(0.4, 0.2, 0.2, 0.2))
+        s[what] = int(self.pick([x for x in range(3 if what == "flat" else 2) if x != s[what]]))
+        return s
+
+    def new_pass(self, rung):
+        rng, m = self.rng, self.m
+        s = dict(vs=self.pick(("PHONG", "GOURAUD")))
+        if rung:
+            kind = self.pick(("plain", "list", "list_if"), p=(0.5, 0.3, 0.2))
+            items = [(RUNGS[rung], M_IDENT)]
+            if kind != "plain":
+                items += [(self.pick(("p40", "empty", "torus")), int(M_GRID[i])) for i in range(int(rng.randint(2, 4)))]
+        else:
+            kind = self.pick(KINDS)
+            fed = [(b, pr) for b, pr in sorted(m.prov.items()) if pr["unit"] == "item" and pr["frame"] >= m.fno - 1 and pr["kind"] in ("list", "list_if")
+                   and pr["entries"] >= pr["n"] >= 3 and all(mesh not in RUNGS.values() for mesh, _ in pr["items"])]
+            if fed and rng.rand() < 0.4:
+                kind = "list_if"               # the counts of an earlier pass are there to be fed back
+            if kind == "plain":
+                items = [(self.pick(("p40", "p100", "p257", "spiky", "torus")), int(self.pick(list(M_CLIPPED) + [M_MIRROR, M_LEFT, M_IDENT])))]
+            elif kind == "indexed":
+                items = [("grid", int(self.pick(list(M_CLIPPED)[:4] + [M_IDENT])))]
+            elif kind == "instanced":
+                n = int(rng.randint(2, 6))
+                ms = [int(x) for x in rng.choice(list(M_GRID) + list(M_CLIPPED), n, replace=False)]
+                ms[int(rng.randint(n))] = M_MIRROR
+                mesh = self.pick(("p40", "p100", "torus", "spiky"))
+                items = [(mesh, mi) for mi in ms]
+            else:
+                if kind == "list_if" and fed and rng.rand() < 0.8:
+                    b, pr = fed[int(rng.randint(len(fed)))]
+                    items = list(pr["items"])
+                    s.update(keep=b, keep_entries=pr["entries"], min=int(self.pick(MIN_VALUES)), fed=True)
+                else:
+                    n = int(rng.randint(3, 8)) if rng.rand() < 0.93 else 0
+                    ms = [int(x) for x in rng.choice(list(M_GRID) + list(M_CLIPPED), n, replace=False)]
+                    items = [(self.pick(SMALL + ("empty", "empty")), mi) for mi in ms]
+        if kind == "list_if" and "keep" not in s:
+            mask = "mask0" if rung else self.pick(sorted(MASKS), p=(0.45, 0.45, 0.1))
+            s.update(keep=mask, keep_entries=8, min=int(self.pick(MIN_VALUES)) if mask == "mask1" else 1, fed=False)
+        s.update(kind=kind, items=[tuple(i) for i in items], rung=rung)
+        return s
+
+    def command(self, kind, inside):
+        """one target or buffer command of the given kind at this place, or None"""
+        rng, m, pool = self.rng, self.m, "AB"[self.m.fno % 2]
+        p = m.last if m.last is not None and not m.last.cleared else None
+        if kind == "lines":
+            return dict(op="lines", list=int(rng.randint(2)))
+        if kind == "wireframe":
+            return dict(op="wireframe", color=int(rng.randint(2))) if p else None
+        if kind == "resolve":
+            if not p or (p.rastered and any(mesh in RUNGS.values() for mesh, _ in p.items)):
+                return None                    # (the NumPy oracle is not run over a rung's thousands of triangles)
+            return dict(op="resolve", buf=f"{pool}.v{p.K}{self.pick('ab')}")
+        if kind == "shade":
+            if not self.resolved:
+                return None
+            K = buffer_k(self.pick(self.resolved))
+            written = [b for b in self.resolved if buffer_k(b) == K]
+            ids = (0, NONE) if inside or not self.ranges or rng.rand() < 0.5 else self.ranges[int(rng.randint(len(self.ranges)))]
+            return dict(op="shade", buf=self.pick(written), ps=self.pick(K_PS[K]), ids=tuple(int(x) for x in ids))
+        unit = kind.split("_")[1]
+        if unit == "item":
+            if m.last is None:
+                return None
+            n = len(m.last.items)
+        else:
+            if p is None:
+                return None
+            n = p.base + p.emit
+        e = n + int(self.pick((0, -1, 3)))
+        return dict(op="count", unit=unit, buf=f"{pool}.c{int(rng.randint(3))}", entries=e) if e > 0 else None
+
+    def place(self, kind, inside):
+        """one command of the kind; a shade half the time behind a state setter it comes out differently under"""
+        c = self.command(kind, inside)
+        if c and c["op"] == "shade" and self.room() > (2 if inside else 1) and self.rng.rand() < 0.6:
+            t = self.setter(inside)
+            if t["op"] != "set_cull":
+                a, b = self.probe([t, c])[0], self.probe([c])[0]
+                if a is not None and b is not None and a != b:
+                    self.add(t)
+        return self.add_command(c)
+
+    def kind_of_command(self):
+        """shades and resolves come up more often where they can do something"""
+        p = self.m.last
+        w = {k: 1.0 for k in COMMANDS}
+        w["shade"] = 2.5 if self.resolved else 0.0
+        w["resolve"] = 2.0 if p is not None and p.rastered and not p.cleared else 0.5
+        ws = np.array([w[k] for k in COMMANDS])
+        return self.pick(COMMANDS, p=ws / ws.sum())
+
+    def add_command(self, c):
+        ok = bool(c) and self.add(c, noop_ok=c["op"] in ("resolve", "count") or (c["op"] == "shade" and c["ids"][1] == 0))
+        if ok and c["op"] == "resolve" and not c.get("noop") and c["buf"] not in self.resolved:
+            self.resolved.append(c["buf"])
+        return ok
+
+    # -- one pass, fused or split --
+    def one_pass(self, rung):
+        rng = self.rng
+        for _ in range(16):
+            s = self.new_pass(rung)
+            # (a rung covers the screen: behind a depth-only rasterization the lines and shades inside its pass stay visible)
+            ps = "DEPTH" if rung and rng.rand() < 0.6 else self.pick(("DEPTH", "FLAT") if rung == 2 else VS_PS[s["vs"]])
+            draw = dict(s, op="draw", ps=ps, fused=True)
+            if rung and self.m.cull != 0:
+                self.add(dict(op="set_cull", mode=0), force=True)      # a rung is sized for the whole mesh
+            elif not rung and self.room() >= 3 and rng.rand() < 0.6:
+                t = self.setter(False)
+                a, b = self.probe([t, draw])[0], self.probe([draw])[0]
+                if a is not None and b is not None and a != b:
+                    self.add(t)
+            digest, changed = self.probe([draw])
+            if digest is None or (not changed and not self.noop_allowed()):
+                continue
+            if not rung and self.probed.last.fan_need > ORDINARY_FAN_NEED:
+                continue                       # (the rungs are sized against what an ordinary pass can need)
+            if self.room() < 3 or rng.rand() < (0.2 if rung else 0.5):
+                if self.add(draw, noop_ok=True):
+                    return
+                continue
+            added = self.add(dict(s, op="geom", fused=False))
+            assert added
+            want = int(rng.randint(1, 4)) if rung else int(rng.randint(0, 4))
+            kinds = [str(k) for k in rng.permutation(COMMANDS)]
+            if rung:                            # every kind of command is the first one tried inside the rungs of some seeds
+                first = COMMANDS[(self.seed + 3 * rung) % len(COMMANDS)]
+                kinds.remove(first)
+                kinds.append(first)
+            elif self.resolved and rng.rand() < 0.6:
+                kinds.remove("shade")
+                kinds.append("shade")
+            n = 0
+            for _ in range(12):
+                if n >= want or self.room() <= 1 or not kinds:
+                    break
+                r = rng.rand()
+                if r < 0.15:
+                    n += self.add(dict(op=self.pick(QUERIES)))
+                else:
+                    n += self.place(kinds.pop(), True)
+            added = self.add(dict(op="raster", ps=ps), force=True)
+            assert added, "a geometry pass whose rasterization is refused"
+            return
+        raise AssertionError("no pass could be placed")
+
+    # -- one frame --
+    def frame(self, fno, window, rung, end):
+        rng = self.rng
+        self.steps, self.ranges, self.reserve = [dict(op="clear", window=tuple(window))], [], 0
+        self.m.apply(self.steps[0])
+        npass = int(rng.randint(2, 5))
+        at = int(rng.randint(npass)) if rung else -1
+        if fno > 0 and rng.rand() < 0.3:       # a per-item count of the previous frame's pass right after the clear: zeros
+            self.reserve = 3
+            self.add_command(self.command("count_item", False))
+        for k in range(npass):
+            r = rung if k == at else 0
+            self.reserve = 3 if rung and k < at else 0        # (room for the rung's pass behind this one)
+            if not r and self.room() < 2:
+                continue
+            self.one_pass(r)
+            p = self.m.last
+            if not r and p.kind in ("list", "list_if") and len(p.items) >= 3 and self.room() >= 1 and rng.rand() < 0.6:
+                n = len(p.items)
+                self.add_command(dict(op="count", unit="item", buf=f"{'AB'[fno % 2]}.c{int(rng.randint(3))}", entries=n + int(self.pick((0, 3)))))
+            if not r and not self.resolved and self.room() >= 1 and rng.rand() < 0.7:
+                self.add_command(self.command("resolve", False))
+            for _ in range(int(rng.randint(1, 4))):
+                if self.room() < 1:
+                    break
+                if rng.rand() < 0.2:
+                    self.add(dict(op=self.pick(QUERIES)))
+                else:
+                    self.place(self.kind_of_command(), False)
+        self.reserve = 0
+        self.steps.append(dict(op=end))
+        self.m.apply(self.steps[-1])
+        self.total += 1
+        self.frames.append(self.steps)
+
+
+_GENERATED = {}
+
+
+def steps_of(frames):
+    return [s for steps in frames for s in steps if s["op"] != "clear"]
+
+
+def generate(seed, oracle=None):
+    """The frames of a seed: a list of FRAMES lists of steps (dicts: "op" and its arguments; "noop" on a step that writes
+    nothing on purpose; "rung" on a pass over a rung mesh; "fan_rung", "bin_rung", "fan_need", "bin_need" on every pass, from
+    the model).  Every frame starts with its "clear" and ends with "readback" or "fenced"; the steps after the clear are at most
+    MAX_STEPS.  A pure function of the seed: np.random.RandomState(seed) is the only source of randomness, and the model the
+    generator consults is deterministic."""
+    if seed in _GENERATED:
+        return _GENERATED[seed]
+    if oracle is None:
+        from oracle import cref as oracle
+    g = _Gen(oracle, seed)
+    rng = g.rng
+    f1 = int(rng.randint(0, 2))
+    f2 = int(rng.randint(f1 + 1, FRAMES))
+    sub = int(rng.randint(FRAMES))
+    for fno in range(FRAMES):
+        g.frame(fno, SUB if fno == sub else FULL, 1 if fno == f1 else 2 if fno == f2 else 0, g.pick(("readback", "fenced")))
+    frames = g.frames
+    # what a later step overwrote: a step whose removal changes no compared output any more leaves the sequence
+    for _ in range(24):
+        bad = insensitive_steps(oracle, frames)
+        if not bad:
+            break
+        fi, s = bad[0]
+        drop = {id(s)} | ({id(pass_partner(frames[fi], s))} if s["op"] == "geom" else set())
+        frames = [[x for x in steps if id(x) not in drop] for steps in frames]
+    # ... and the share of no-ops on purpose holds for what is left
+    while True:
+        flat = steps_of(frames)
+        noops = [s for s in flat if s.get("noop")]
+        if len(noops) <= NOOP_SHARE * len(flat):
+            break
+        for s in sorted(noops, key=lambda x: x["op"] in ("geom", "draw")):       # (a command before a pass)
+            fi = next(k for k, steps in enumerate(frames) if any(x is s for x in steps))
+            drop = {id(s)} | ({id(pass_partner(frames[fi], s))} if s["op"] == "geom" else set())
+            fewer = [[x for x in steps if id(x) not in drop] for steps in frames]
+            try:
+                run_model(oracle, fewer)
+            except (Undefined, RuntimeError):
+                continue
+            frames = fewer
+            break
+        else:
+            raise AssertionError("the share of no-ops cannot be met")
+    _GENERATED[seed] = frames
+    return frames
+
+
+def cull_inside_split():
+    """A fixed frame for what the generator never draws: frr_set_cull between a geometry* and its rasterization.  The mode
+    travels with the geometry command -- the pass that is open keeps the mode of its geometry call, through a replay too,
+    and the next pass takes the new one.  With the tiny lists the first pass overflows, so its geometry is cancelled and
+    replayed with the later set_cull already issued."""
+    inst = [("torus", mi) for mi in (int(M_CLIPPED[0]), M_MIRROR, int(M_CLIPPED[2]), int(M_GRID[0]), int(M_CLIPPED[4]))]
+    return [[dict(op="clear", window=FULL),
+             dict(op="set_cull", mode=CS.NEG),
+             dict(op="geom", kind="instanced", vs="PHONG", items=inst, rung=0, fused=False),
+             dict(op="set_cull", mode=CS.POS),
+             dict(op="count", unit="item", buf="A.c0", entries=5),
+             dict(op="raster", ps="PHONG"),
+             dict(op="item_ranges"),
+             dict(op="geom", kind="plain", vs="GOURAUD", items=[("spiky", int(M_CLIPPED[1]))], rung=0, fused=False),
+             dict(op="set_cull", mode=CS.NONE),
+             dict(op="raster", ps="COLOR"),
+             dict(op="stats"),
+             dict(op="draw", kind="plain", vs="PHONG", items=[("torus", M_LEFT)], ps="BLINN", rung=0, fused=True),
+             dict(op="readback")]]
+
+
+def describe(s):
+    """one step as a line of a failure report"""
+    return s["op"] + "(" + ", ".join(f"{k}={v}" for k, v in s.items() if k not in ("op", "fan_need", "bin_need")) + ")"

@@ -61,6 +61,21 @@ def panics(x1, y1, x2, y2, width, height):
     return False
 
 
+def wireframe_segments(spi, width, height):
+    """The list a host would build for frr_draw_wireframe from a setup list's spi [n, 3, 2] (emission-order vertices):
+    segment 3t + e is edge e of triangle t, (v0,v1), (v1,v2), (v2,v0); an edge with an endpoint outside 0 <= x < width,
+    0 <= y < height is skipped whole.  Returns (segments [(x1, y1, x2, y2)], skipped edges)."""
+    segs, skipped = [], 0
+    for tri in spi:
+        for e in range(3):
+            (xa, ya), (xb, yb) = tri[e], tri[(e + 1) % 3]
+            if 0 <= xa < width and 0 <= xb < width and 0 <= ya < height and 0 <= yb < height:
+                segs.append((xa, ya, xb, yb))
+            else:
+                skipped += 1
+    return segs, skipped
+
+
 def draw_line(image, x1, y1, x2, y2, color):
     """draw_line on a uint8 [H, W, 4] array, in place; IndexError where the reference panics (nothing is written then:
     callers compare whole lists, which the library refuses whole)."""

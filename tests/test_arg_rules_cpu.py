@@ -178,6 +178,22 @@ def test_pixel_shader_rule_truth_table():
     assert "vertex shader" in by[(FROM_GEOMETRY, PS_COLOR, 8, R.USER_K_UNKNOWN, True)][1]
 
 
+def nothing_cases():
+    """the table's shaders, Ks and textures for a pass without a vertex shader"""
+    return [(R.FROM_NOTHING,) + c[1:] for c in ps_cases() if c[0] == FROM_GEOMETRY]
+
+
+def test_pixel_shader_rule_of_a_pass_without_a_vertex_shader():
+    """A list without items (include/frr.h): the id has to name a shader -- a built-in one, or a user id somebody
+    registered -- and neither the K nor the texture is asked for."""
+    cases = nothing_cases()
+    assert len(cases) == 10 * 5 * 2
+    got = R.ask(R.shader(*c) for c in cases)
+    for (_, ps, K, user_K, tex), (code, text) in zip(cases, got):
+        known = 0 <= ps <= PS_BLINN or (ps >= USER and user_K != R.USER_K_UNKNOWN)
+        assert code == (OK if known else INVALID) and (text == "" if known else "unknown shader id" in text), (ps, K, user_K, tex, code, text)
+
+
 # (use, pointer, entries, K, x1, y0, y1) -> code: a 40-wide window of 25 rows needs 1,000 entries
 BUFFERS = [
     ((R.VARYINGS_OUT, 4096, 1000, 0, 40, 5, 30), OK), ((R.VARYINGS_OUT, 4096, 999, 0, 40, 5, 30), INVALID),
@@ -206,5 +222,5 @@ def test_rules_under_the_undefined_behaviour_sanitizer():
     exe = R.build(("-fsanitize=undefined", "-fno-sanitize-recover=all"))
     if exe is None:
         pytest.skip("the host compiler's UBSan runtime is not installed")
-    queries = grid_queries() + edge_queries() + [R.shader(*c) for c in ps_cases()] + [R.buffer(*q) for q, _ in BUFFERS] + ["c"]
+    queries = grid_queries() + edge_queries() + [R.shader(*c) for c in ps_cases() + nothing_cases()] + [R.buffer(*q) for q, _ in BUFFERS] + ["c"]
     assert R.ask(queries, exe) == R.ask(queries)

@@ -311,14 +311,7 @@ def test_wireframe_after_an_instanced_geometry(oracle):
     c, d, t = r.readback()
     setup = r.setup_triangles()
     np.testing.assert_array_equal(setup["spi"], osetup["spi"])
-    segs, skipped = [], 0
-    for tri in setup["spi"]:
-        for e in range(3):
-            (xa, ya), (xb, yb) = tri[e], tri[(e + 1) % 3]
-            if 0 <= xa < W and 0 <= xb < W and 0 <= ya < H and 0 <= yb < H:
-                segs.append((xa, ya, xb, yb))
-            else:
-                skipped += 1
+    segs, skipped = R.wireframe_segments(setup["spi"], W, H)
     xyxy = np.array(segs, np.uint32).reshape(-1, 4)
     assert skipped > 0 and len(xyxy) > 0
     np.testing.assert_array_equal(t, of.tri_id)
