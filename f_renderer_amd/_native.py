@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("FRR_LIB") or os.path.join(_HERE, "libfrr_hip.so")  # FRR_LIB: developer override
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_rules.h", "frr_lines.h", "frr_varyings.h", "frr_shade.h", "frr_visible.h", "frr_own.h")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_rules.h", "frr_proof.h", "frr_lines.h", "frr_varyings.h", "frr_shade.h", "frr_visible.h", "frr_own.h")]
 _HDR = os.path.join(_ROOT, "include", "frr.h")
 
 HIPCC_FLAGS = [

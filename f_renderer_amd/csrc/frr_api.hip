@@ -3,6 +3,7 @@
 #include "frr_kernels.h"
 #include "frr_tile_order.h"
 #include "frr_rules.h"
+#include "frr_proof.h"
 #include "frr_lines.h"
 #include "frr_varyings.h"
 #include "frr_shade.h"
@@ -198,45 +199,52 @@ struct BinSet {
     ReaderFence reader;
 };
 
-struct GeomFilter { bool active; int32_t y0, y1; int rank, world; bool blocked; };
-
 // Everything a command reads and changes on the host.  Every logged command carries the state it started from, so that
-// the commands from a failed one onwards can be replayed (finish()).
-struct FrameState {
+// the commands from a failed one onwards can be replayed (finish()).  Its parts:
+
+// Bound: set by the calls between commands, so a replay gives every command its own copy and puts the current one back afterwards.
+struct Bound {
     uint8_t *color = nullptr; float *depth = nullptr; uint32_t *tri_id = nullptr; // the frame targets (own or caller-bound)
     int tset = 0;                                                                 // which of the ctx's own target sets is current
     int rank = 0, world = 1; bool part_blocked = false;                           // tile-row ownership (frr_set_partition*)
-    // frr_clear is deferred: the first full-window draw of the span kernel performs it inside the tile kernel
-    // (keys start from the clear depth, every pixel of the tile is written); anything else that looks at the
-    // targets first settles it with k_clear.  option clear_eager restores the immediate clear.
-    bool clear_pending = false;    // targets not cleared yet
+};
+// frr_clear is deferred: the first full-window draw of the span kernel performs it inside the tile kernel
+// (keys start from the clear depth, every pixel of the tile is written); anything else that looks at the
+// targets first settles it with k_clear.  option clear_eager restores the immediate clear.
+struct Clear {
+    bool pending = false;          // targets not cleared yet
     bool unowned_debt = false;     // partitioned ctx: the tile rows of other ranks missed a fused clear
     int debt_tiles_y = 0;          //   (tile rows of the window of the draw that left the debt)
-    uint32_t clear_rgba = 0; float clear_depth = 0.0f;
+    uint32_t rgba = 0; float depth = 0.0f;
+    uint32_t wait_serial = 0;      // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
+};
+// The latest geometry pass: what it read (frr_proof.h: the half a raster pass's signature takes), and what it left for the commands behind it.
+struct GeomPass {
+    GeomRead read;
+    int part_rank = 0, part_world = 1; bool part_blocked = false;   // the partition read.filter was built under (raster_check)
+    uint32_t fan_cap = 0;          // fan capacity it was launched with
+    uint32_t nblocks = 0;
+    uint32_t seq = 0;              // its sequence number
+    bool scan_pending = false;     // its block sums are not scanned yet (geom_scan: by the binning launch, or k_geom_scan)
+    int set = 0;                   // its workspace set (GeomSet)
+    bool on_g = false;             // it runs on the second stream (its binning follows it there)
+    // its items (frr_geometry_item_ranges): the items of a list pass, the instances of an instanced pass (stride inputs each), else one
+    uint64_t nitems = 1, stride = 0;
+    bool pred = false;             // it is a predicated list pass: what it needs of the work lists hangs on device data (never proven)
+    bool none() const { return read.vs < 0; }      // no geometry pass yet
+    void setup_list_gone() { read.ntris = 0; }     // frr_clear: frr_raster then draws nothing (nitems stays: frr_visible_pixels_host reports it)
+};
+struct FrameState {
+    Bound bound;
+    Clear clear;
     uint32_t frame_no = 1;         // frr_clear count (device statistics are tagged with it)
     uint64_t tris_in = 0; uint32_t draws = 0;   // statistics the host knows: inputs submitted / geometry passes since frr_clear
     int lane = 0;                  // which of the two sets of device tables this frame's passes use (frr_device.h: Lane)
     int gpars[2] = {0, 0}, bpars[2] = {0, 0};   // per lane: parity of the latest geometry / raster pass (GeomTab / BinTab)
     int gpar() const { return gpars[lane]; }
     int bpar() const { return bpars[lane]; }
-    int gset = 0, bset = 0;        // workspace set of the latest geometry / raster pass (GeomSet / BinSet)
-    bool on_g = false;             // the latest geometry pass runs on the second stream (its binning follows it there)
-    GeomFilter geom_filter = {false, 0, 0, 0, 1, false}; // tile-row ownership filter the latest setup list was built with (frr_draw on a partitioned ctx)
-    uint32_t geom_fan_cap = 0;     // fan capacity the latest geometry pass was launched with
-    uint32_t geom_nblocks = 0;
-    uint32_t geom_seq = 0;         // its sequence number
-    bool scan_pending = false;     // its block sums are not scanned yet (geom_scan: by the binning launch, or k_geom_scan)
-    int geom_vs = -1;              // VS of the latest frr_geometry
-    uint64_t geom_ntris = 0;
-    const float *geom_mesh = nullptr; uint64_t geom_mesh_gen = 0, geom_duni_hash = 0;   // ... its mesh and (a digest of) its uniforms: DrawSig
-    const float *geom_inst = nullptr; uint64_t geom_inst_gen = 0, geom_ninst = 0;   // ... and, an instanced pass, its table: DrawSig
-    uint64_t geom_tex_epoch = 0, geom_sync_epoch = 0;  // ... the texture uploads and (device-bound mesh) the frr_sync calls before it: DrawSig
-    int geom_cull = FRR_CULL_NONE;                     // ... and the cull mode it ran under: DrawSig
-    int geom_list = -1; uint64_t geom_list_gen = 0;    // ... and, a list pass, its list: DrawSig
-    // its items (frr_geometry_item_ranges): the items of a list pass, the instances of an instanced pass (geom_stride inputs each), else one
-    uint64_t geom_nitems = 1, geom_stride = 0;
-    bool geom_pred = false;        // it is a predicated list pass: what it needs of the work lists hangs on device data (never proven)
-    uint32_t clear_wait_serial = 0;   // frr_frame_wait calls before the pending frr_clear was issued (frr_ctx::waits)
+    int bset = 0;                  // workspace set of the latest raster pass (BinSet)
+    GeomPass geom;
 };
 
 struct Cmd {
@@ -267,25 +275,19 @@ struct Cmd {
     int lane = 0;              // the lane of device tables it ran in
 };
 
-// What decides how much of the work lists (fan space, (triangle, tile) records) a raster pass and its geometry pass need.
-// Everything the geometry pass reads can change what it emits: the mesh (its registration, and for a device-bound one the
-// frr_sync calls since -- the caller may rewrite it in place then), the uniforms (a user VS may read any field, texture
-// pointers and sizes included) and the texture contents (frr_texture_upload count).
-// So can the cull mode (frr_set_cull): a pass proven to fit under one mode says nothing about another.
-// (An indexed mesh needs no field of its own: its index list and vertex count belong to its registration, mesh_gen, and
-// binding it again after a rewrite is a new registration.)
-struct DrawSig {
-    const float *inst; uint64_t inst_gen, ninst;   // an instanced pass: its table (bound again, or device-bound and behind a frr_sync: unproven again, like a mesh)
-    uint64_t list_gen;   // a list pass: which upload its id meant -- a pass proven for one list says nothing about a later list with that id
-    const float *mesh; uint64_t mesh_gen; uint64_t ntris; uint64_t duni_hash; uint64_t tex_epoch, sync_epoch; uint32_t join_epoch;
-    int32_t vs, x0, x1, y0, y1, rank, world, blocked, filter, fy0, fy1, gset, bset, cull, list;
-};
 static_assert(std::is_trivially_copyable<FrameState>::value && std::is_trivially_copyable<Cmd>::value, "the replay copies them: views only, no owner");
-inline bool same_sig(const DrawSig &a, const DrawSig &b) { return memcmp(&a, &b, sizeof a) == 0; }
 inline uint64_t fnv1a(const void *p, size_t n, uint64_t h = 1469598103934665603ull)
 {
     for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
     return h;
+}
+// GeomRead::duni_hash: every field a vertex shader can read (field ranges without padding: the struct has some in front of its texture pointer)
+inline uint64_t geom_uniform_digest(const DevUniforms &du)
+{
+    uint64_t h = fnv1a(&du, offsetof(DevUniforms, flat_color) + sizeof du.flat_color);
+    h = fnv1a(&du.tex, offsetof(DevUniforms, tex_h) + sizeof du.tex_h - offsetof(DevUniforms, tex), h);
+    h = fnv1a(du.user, sizeof du.user, h);
+    return fnv1a(du.slot_tex, offsetof(DevUniforms, slot_h) + sizeof du.slot_h - offsetof(DevUniforms, slot_tex), h);
 }
 
 } // namespace
@@ -341,13 +343,13 @@ struct frr_ctx {
     // need of the work lists is not known to fit -- no pass with the same DrawSig has completed on the current lists -- is
     // VERIFIED before frr_raster returns: the host waits for the pass's binning launch (not for its tile kernel), looks at
     // host_bad, and repairs (finish(): grow + replay) if the pass or its geometry overflowed.  A proven pass is not waited for.
-    std::vector<DrawSig> proven;
+    ProvenSet proven;               // (frr_proof.h)
     uint64_t mesh_gen = 0;          // meshes registered so far (Mesh::gen)
     uint64_t tex_epoch = 0;         // frr_texture_upload calls so far (DrawSig: a user VS may sample a texture)
     uint64_t sync_epoch = 0;        // frr_sync calls so far (DrawSig of a device-bound mesh: rewritten in place behind one?)
     Event ev_verify;
     bool verify_pending = false;
-    bool verify_proves = true;      // the pass being verified enters `proven` (false: a predicated pass, verified every time)
+    bool verify_pred = false;       // the pass being verified is predicated: verified every time, it never enters `proven`
     DrawSig verify_sig;
     // own targets handed out (frr_target_ptrs / frr_frame_fence): the frame that next renders into that set waits for what
     // the stream they were handed to holds by then (the caller's reads), see frr_clear
@@ -435,20 +437,20 @@ int nomem(frr_ctx *c, const char *what) { return fail(c, FRR_ERR_NOMEM, std::str
 
 bool own_targets(const frr_ctx *c)
 {
-    const FrameState &f = c->fs;
-    return f.color == c->own_color[f.tset] && f.depth == c->own_depth[f.tset] && f.tri_id == c->own_tri_id[f.tset];
+    const Bound &b = c->fs.bound;
+    return b.color == c->own_color[b.tset] && b.depth == c->own_depth[b.tset] && b.tri_id == c->own_tri_id[b.tset];
 }
 // do consecutive frames (frr_clear) alternate between two streams / target sets / workspace sets / lanes?
 bool frames_alternate(const frr_ctx *c) { return c->frames_in_flight == 2 && (own_targets(c) || c->bound_in_flight); }
 // the stream of everything that touches the current frame targets: `stream`, or the current target set's c->tstream[tset]
 hipStream_t tstream_of(const frr_ctx *c)
 {
-    const hipStream_t t = c->tstream[c->fs.tset].st;
-    if (own_targets(c)) return t && c->fs.tset == 1 ? t : c->stream;
+    const hipStream_t t = c->tstream[c->fs.bound.tset].st;
+    if (own_targets(c)) return t && c->fs.bound.tset == 1 ? t : c->stream;
     return c->bound_in_flight && c->tstream[0].st && c->tstream[1].st ? t : c->stream;
 }
 // the stream of the latest geometry pass and of the binning that follows it: the second stream, or the targets' stream
-hipStream_t gstream_of(const frr_ctx *c) { return c->fs.on_g ? c->gstream : tstream_of(c); }
+hipStream_t gstream_of(const frr_ctx *c) { return c->fs.geom.on_g ? c->gstream : tstream_of(c); }
 // do passes ever run beside each other on this ctx (workspace sets then carry events)?
 bool multi_stream(const frr_ctx *c) { return c->g_used || c->tstream[0].st || c->tstream[1].st; }
 
@@ -554,7 +556,7 @@ int gstream_join(frr_ctx *c)
 {
     hipStream_t st = gstream_of(c);
     if (st == c->stream) return FRR_OK;
-    uint32_t &joined = st == c->gstream ? c->joined_g : c->tstream[c->fs.tset].joined;   // (tstream_of)
+    uint32_t &joined = st == c->gstream ? c->joined_g : c->tstream[c->fs.bound.tset].joined;   // (tstream_of)
     if (joined == c->join_epoch) return FRR_OK;
     HIP_TRY(c, hipEventRecord(c->ev_join, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_join, 0));
@@ -666,8 +668,9 @@ void blocked_rows(int tiles_y, int rank, int world, int *t0, int *t1)
 // reader (owns_tile_row -- so k_clear_unowned_rows too --, local_tile_row, tri_rows_owned) answers from `world <= 1` before the layout.
 RowOwner row_owner(const FrameState &f, int tiles_y)
 {
-    RowOwner o = {f.rank, f.world, (f.part_blocked && f.world > 1) ? 1 : 0, 0, 0};
-    if (o.blocked) blocked_rows(tiles_y, f.rank, f.world, &o.brow0, &o.brow1);
+    const Bound &b = f.bound;
+    RowOwner o = {b.rank, b.world, (b.part_blocked && b.world > 1) ? 1 : 0, 0, 0};
+    if (o.blocked) blocked_rows(tiles_y, b.rank, b.world, &o.brow0, &o.brow1);
     return o;
 }
 
@@ -755,11 +758,11 @@ void launch_geometry_vs(frr_ctx *c, GeomArgs &g, uint32_t nblocks, int vs, const
 int scan_now(frr_ctx *c)
 {
     FrameState &f = c->fs;
-    if (!f.scan_pending) return FRR_OK;
+    if (!f.geom.scan_pending) return FRR_OK;
     hipStream_t st = gstream_of(c);
-    { ProfScope p(c, KID_GEOM_SCAN, st); hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(1024), 0, st, c->gset[f.gset].block_sums, c->gset[f.gset].block_prefix, f.geom_nblocks, c->cnt, f.lane, f.gpar(), f.geom_fan_cap, f.geom_seq, c->epoch); }
+    { ProfScope p(c, KID_GEOM_SCAN, st); hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(1024), 0, st, c->gset[f.geom.set].block_sums, c->gset[f.geom.set].block_prefix, f.geom.nblocks, c->cnt, f.lane, f.gpar(), f.geom.fan_cap, f.geom.seq, c->epoch); }
     HIP_TRY(c, hipGetLastError());
-    f.scan_pending = false;
+    f.geom.scan_pending = false;
     return FRR_OK;
 }
 
@@ -807,7 +810,7 @@ template <int K, int PS> void launch_raster(frr_ctx *c, hipStream_t ts, const Ra
 // `ts` (tstream_of) has been given work: a frame stream is dirty until fence_stream joins it
 void frame_stream_dirty(frr_ctx *c, hipStream_t ts)
 {
-    if (ts != c->stream) c->tstream[c->fs.tset].dirty = c->tstream[c->fs.tset].xdirty = true;
+    if (ts != c->stream) c->tstream[c->fs.bound.tset].dirty = c->tstream[c->fs.bound.tset].xdirty = true;
 }
 // which of the buffers kept per stream that can carry target work (frr_ctx::line_owner, vis_bounds) goes with `ts`
 int stream_slot(const frr_ctx *c, hipStream_t ts) { return ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2; }
@@ -818,7 +821,7 @@ void tables_read(frr_ctx *c, Cmd &cmd, hipStream_t ts)
     const FrameState &f = c->fs;
     ReaderFence &wr = c->wire_reader[f.lane];
     wr.pending = true; wr.stream = ts; wr.recorded = false;
-    cmd.par = f.gpar(); cmd.set = f.gset; cmd.lane = f.lane;
+    cmd.par = f.gpar(); cmd.set = f.geom.set; cmd.lane = f.lane;
 }
 
 // Every launch that writes the frame targets goes on the stream this returns (*ts, the targets' stream).  The write follows
@@ -847,11 +850,11 @@ int clear_now(frr_ctx *c, uint32_t packed, float depth, bool issued_after_waits)
     {
         ProfScope p(c, KID_CLEAR, ts);
         uint32_t grid = std::min<uint32_t>((n4 + 255) / 256, 2048);
-        hipLaunchKernelGGL(k_clear, dim3(grid ? grid : 1), dim3(256), 0, ts, (uint4 *)f.color, (uint4 *)f.depth,
-                           (uint4 *)f.tri_id, n4, packed, depth);
+        hipLaunchKernelGGL(k_clear, dim3(grid ? grid : 1), dim3(256), 0, ts, (uint4 *)f.bound.color, (uint4 *)f.bound.depth,
+                           (uint4 *)f.bound.tri_id, n4, packed, depth);
         if (n4 * 4 < n)
-            hipLaunchKernelGGL(k_clear_tail, dim3(1), dim3(64), 0, ts, (uint32_t *)f.color, (uint32_t *)f.depth,
-                               f.tri_id, n4 * 4, n, packed, depth);
+            hipLaunchKernelGGL(k_clear_tail, dim3(1), dim3(64), 0, ts, (uint32_t *)f.bound.color, (uint32_t *)f.bound.depth,
+                               f.bound.tri_id, n4 * 4, n, packed, depth);
     }
     HIP_TRY(c, hipGetLastError());
     return FRR_OK;
@@ -861,19 +864,19 @@ int clear_now(frr_ctx *c, uint32_t packed, float depth, bool issued_after_waits)
 int settle_targets(frr_ctx *c)
 {
     FrameState &f = c->fs;
-    if (f.clear_pending) {
-        int rc = clear_now(c, f.clear_rgba, f.clear_depth, f.clear_wait_serial == c->wait_serial);
+    if (f.clear.pending) {
+        int rc = clear_now(c, f.clear.rgba, f.clear.depth, f.clear.wait_serial == c->wait_serial);
         if (rc != FRR_OK) return rc;
-        f.clear_pending = f.unowned_debt = false;
-    } else if (f.unowned_debt) {
-        const RowOwner own = row_owner(f, f.debt_tiles_y);
+        f.clear.pending = f.clear.unowned_debt = false;
+    } else if (f.clear.unowned_debt) {
+        const RowOwner own = row_owner(f, f.clear.debt_tiles_y);
         // (the rest of a clear issued with an earlier draw: it follows the pending waits, the next frame's writes consume them)
         hipStream_t ts;
         { int rc = target_write(c, false, &ts); if (rc != FRR_OK) return rc; }
-        hipLaunchKernelGGL(k_clear_unowned_rows, dim3(c->H), dim3(256), 0, ts, (uint32_t *)f.color, (uint32_t *)f.depth,
-                           f.tri_id, c->W, c->H, own, f.clear_rgba, f.clear_depth);
+        hipLaunchKernelGGL(k_clear_unowned_rows, dim3(c->H), dim3(256), 0, ts, (uint32_t *)f.bound.color, (uint32_t *)f.bound.depth,
+                           f.bound.tri_id, c->W, c->H, own, f.clear.rgba, f.clear.depth);
         HIP_TRY(c, hipGetLastError());
-        f.unowned_debt = false;
+        f.clear.unowned_debt = false;
     }
     return FRR_OK;
 }
@@ -909,7 +912,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     // tile kernel spends long stretches shading (4K textured frame -6 %, a rank of 8 of it -10 %), not for depth-only ones.
     const bool fif2 = frames_alternate(c);   // consecutive frames already run beside each other, on two streams (frr_clear)
     const bool on_g = !fif2 && (c->overlap == 1 || (c->overlap == 2 && K > 0));
-    const int si = on_g ? (f.gset ^ 1) : (fif2 ? f.tset : 0);
+    const int si = on_g ? (f.geom.set ^ 1) : (fif2 ? f.bound.tset : 0);
     GeomSet &S = c->gset[si];
     int rc;
     const UserModule *um = nullptr;
@@ -948,13 +951,13 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
         // share one run nothing beside each other -- a ctx that never needs this stream does not take a queue for it
         HIP_TRY(c, acquire_stream(c->device, &c->gstream));
     }
-    if (on_g != f.on_g) {
+    if (on_g != f.geom.on_g) {
         // this pass changes streams: it follows the previous pass's geometry + binning (tri_base, fan cursors)
         hipEvent_t e = c->ev_bin[++c->bin_serial & 3];
         HIP_TRY(c, hipEventRecord(e, gstream_of(c)));
         HIP_TRY(c, hipStreamWaitEvent(on_g ? c->gstream : tstream_of(c), e, 0));
     }
-    f.on_g = on_g;
+    f.geom.on_g = on_g;
     if (on_g) c->g_used = true;
     // second stream: after whatever the caller's stream holds that this pass may read (first use), and after the tile
     // kernel that last read this workspace
@@ -980,7 +983,7 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.fan_cap = (uint32_t)fan_cap;
     g.seq = cmd.seq; g.epoch = c->epoch; g.frame_no = f.frame_no;
     const RowOwner own = row_owner(f, (int)(((int64_t)cmd.fy1 - cmd.fy0 + TILE - 1) / TILE));
-    g.part_rank = f.rank; g.part_world = cmd.filter ? f.world : 1; g.part_y0 = cmd.fy0; g.part_y1 = cmd.fy1;
+    g.part_rank = f.bound.rank; g.part_world = cmd.filter ? f.bound.world : 1; g.part_y0 = cmd.fy0; g.part_y1 = cmd.fy1;
     g.part_blocked = own.blocked; g.part_brow0 = own.brow0; g.part_brow1 = own.brow1;
     g.gpar = par; g.lane = f.lane;
     g.block_sums = S.block_sums; g.block_prefix = S.block_prefix; g.tinfo = S.tinfo; g.fanbase = S.fanbase; g.fan_okey = S.fan_okey;
@@ -991,34 +994,32 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     g.items = dl && nt > 0 ? dl->rows.get() : nullptr; g.item_first = dl ? dl->first.get() : nullptr; g.item_ntris = dl ? dl->first.get() + dl->n : nullptr;
     g.cull = cmd.cull;
     g.keep = keep_tab ? S.keep_tab.get() : nullptr;
-    f.geom_pred = cmd.pred;
-    // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it)
-    f.geom_filter = GeomFilter{cmd.filter, cmd.fy0, cmd.fy1, f.rank, f.world, f.part_blocked};
-    f.gpars[f.lane] = par; cmd.par = par; cmd.lane = f.lane; f.gset = si;
-    f.geom_fan_cap = (uint32_t)fan_cap;
-    f.geom_nblocks = nblocks;
-    f.geom_seq = cmd.seq;
-    f.geom_vs = vs; f.geom_ntris = nt;
-    f.geom_mesh = m.dev; f.geom_mesh_gen = m.gen;
-    f.geom_list = cmd.list; f.geom_list_gen = dl ? dl->gen : 0;
-    f.geom_nitems = dl || it ? nmat : 1; f.geom_stride = m.ntris;
-    {   // (field ranges without padding: the struct has some in front of its texture pointer)
-        const DevUniforms &du = cmd.duni;
-        uint64_t h = fnv1a(&du, offsetof(DevUniforms, flat_color) + sizeof du.flat_color);
-        h = fnv1a(&du.tex, offsetof(DevUniforms, tex_h) + sizeof du.tex_h - offsetof(DevUniforms, tex), h);
-        h = fnv1a(du.user, sizeof du.user, h);
-        h = fnv1a(du.slot_tex, offsetof(DevUniforms, slot_h) + sizeof du.slot_h - offsetof(DevUniforms, slot_tex), h);
-        f.geom_duni_hash = h;
-    }
-    f.geom_tex_epoch = c->tex_epoch; f.geom_cull = cmd.cull;
-    f.geom_inst = it ? it->dev : nullptr; f.geom_inst_gen = it ? it->gen : 0; f.geom_ninst = it ? it->n : 0;
-    f.geom_sync_epoch = (dl ? !dl->any_dev : m.own_dev && (!it || it->own || !it->n)) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
+    f.gpars[f.lane] = par; cmd.par = par; cmd.lane = f.lane;
+    GeomPass &gp = f.geom;
+    gp.pred = cmd.pred;
+    gp.set = si;
+    gp.fan_cap = (uint32_t)fan_cap;
+    gp.nblocks = nblocks;
+    gp.seq = cmd.seq;
+    gp.nitems = dl || it ? nmat : 1; gp.stride = m.ntris;
+    // what the setup list about to be built was filtered by (frr_raster / frr_readback_setup check it), under which partition
+    gp.part_rank = f.bound.rank; gp.part_world = f.bound.world; gp.part_blocked = f.bound.part_blocked;
+    GeomRead rd;   // (from scratch: nothing of the previous pass stays)
+    rd.filter = cmd.filter ? 1 : 0; rd.fy0 = cmd.fy0; rd.fy1 = cmd.fy1;
+    rd.vs = vs; rd.ntris = nt;
+    rd.mesh = m.dev; rd.mesh_gen = m.gen;
+    rd.list = cmd.list; rd.list_gen = dl ? dl->gen : 0;
+    rd.duni_hash = geom_uniform_digest(cmd.duni);
+    rd.tex_epoch = c->tex_epoch; rd.cull = cmd.cull;
+    rd.inst = it ? it->dev : nullptr; rd.inst_gen = it ? it->gen : 0; rd.ninst = it ? it->n : 0;
+    rd.sync_epoch = (dl ? !dl->any_dev : m.own_dev && (!it || it->own || !it->n)) ? 0 : c->sync_epoch;   // (a host-uploaded mesh or table cannot change under the library)
+    gp.read = rd;
     f.tris_in += nt; f.draws += 1;
     if (nt == 0) {
         hipLaunchKernelGGL(k_geom_empty, dim3(1), dim3(64), 0, gstream_of(c), g);
     } else {
         launch_geometry_vs(c, g, nblocks, vs, cmd.duni, um, dl ? dl->models.get() : it ? it->dev : nullptr, cmd.pv, cmd.keep, cmd.min_value);
-        f.scan_pending = true;
+        f.geom.scan_pending = true;
     }
     HIP_TRY(c, hipGetLastError());
     return FRR_OK;
@@ -1034,25 +1035,25 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     const UserModule *um = nullptr;
     if (ps_id >= FRR_SHADER_USER_BASE) { const int rcu = user_module(c, ps_id, &um); if (rcu != FRR_OK) return rcu; }
     bool fuse = false;
-    if (f.clear_pending) {
+    if (f.clear.pending) {
         const bool full = x0 == 0 && y0 == 0 && x1 == (int32_t)c->W && y1 == (int32_t)c->H;
         if (full && !c->raster_sweep) fuse = true; // the tile kernel performs the clear
         else { int rcs = settle_targets(c); if (rcs != FRR_OK) return rcs; }
     }
-    GeomSet &S = c->gset[f.gset];
+    GeomSet &S = c->gset[f.geom.set];
     RasterArgs a;
-    a.fused_clear = fuse ? 1 : 0; a.clear_rgba = f.clear_rgba; a.clear_depth = f.clear_depth;
+    a.fused_clear = fuse ? 1 : 0; a.clear_rgba = f.clear.rgba; a.clear_depth = f.clear.depth;
     a.x0 = x0; a.x1 = x1; a.y0 = y0; a.y1 = y1; a.win_w = (int)ww; a.win_h = (int)wh;
     a.cstride = (int)c->W; a.dstride = x1;
     a.tiles_x = (int)((ww + TILE - 1) / TILE); a.tiles_y = (int)((wh + TILE - 1) / TILE);
     a.tiles_x_magic = 0u; // set below once the grid is known (exact only for block indices and tile counts < 2^16)
     a.own = row_owner(f, a.tiles_y);
     a.recs = S.recs; a.vary = S.vary; a.pbox = S.pbox; a.bcount = S.bcount;
-    a.tinfo = S.tinfo; a.fanbase = S.fanbase; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix; a.ntris_draw = (uint32_t)f.geom_ntris;
+    a.tinfo = S.tinfo; a.fanbase = S.fanbase; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix; a.ntris_draw = (uint32_t)f.geom.read.ntris;
     a.tile_counts = c->tile_counts; a.tile_offsets = c->tile_offsets; a.tile_cursor = c->tile_cursor;
-    a.gpar = f.gpar(); a.lane = f.lane; a.bpar = 0; a.seq = cmd.seq; a.epoch = c->epoch; a.frame_no = f.frame_no; a.geom_seq = f.geom_seq;
+    a.gpar = f.gpar(); a.lane = f.lane; a.bpar = 0; a.seq = cmd.seq; a.epoch = c->epoch; a.frame_no = f.frame_no; a.geom_seq = f.geom.seq;
     const uint32_t ntiles = (uint32_t)a.tiles_x * a.tiles_y;
-    a.color = f.color; a.depth = f.depth; a.tri_id = f.tri_id; a.cnt = c->cnt;
+    a.color = f.bound.color; a.depth = f.bound.depth; a.tri_id = f.bound.tri_id; a.cnt = c->cnt;
 #ifdef FRR_DEBUG_COUNTERS
     if (!c->dbg_tiles && getenv("FRR_DEBUG_TILES")) (void)c->dbg_tiles.reset((size_t)c->max_tiles * 8);   // (empty if that fails)
     if (c->dbg_tiles) (void)hipMemsetAsync(c->dbg_tiles, 0, (size_t)c->max_tiles * 64, tstream_of(c));
@@ -1060,17 +1061,17 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
 #endif
     a.seg = nullptr; a.nseg = 0;
     a.tile_perm = nullptr; a.tile_cost = nullptr;
-    const int owned_rows = a.own.blocked ? a.own.brow1 - a.own.brow0 : (a.tiles_y > f.rank ? (a.tiles_y - f.rank + f.world - 1) / f.world : 0);
+    const int owned_rows = a.own.blocked ? a.own.brow1 - a.own.brow0 : (a.tiles_y > f.bound.rank ? (a.tiles_y - f.bound.rank + f.bound.world - 1) / f.bound.world : 0);
     const uint32_t grid = (uint32_t)a.tiles_x * owned_rows;
     if (a.tiles_x >= 2 && a.tiles_x < 65536 && grid < 65536u) a.tiles_x_magic = (uint32_t)(0x100000000ull / (uint64_t)a.tiles_x + 1ull);
-    const SpanShape sh = span_shape(c, grid, f.geom_ntris, ps_id);
+    const SpanShape sh = span_shape(c, grid, f.geom.read.ntris, ps_id);
     const bool segmented = grid <= BIN_LDS_MAX_TILES && !c->bin_atomics && !c->raster_sweep;
     const int q = segmented ? (f.bpar() ^ 1) : 0;   // (the CSR fallback has one set of tile tables: it uses workspace 0 and overlaps nothing)
-    const int bi = !segmented ? 0 : f.on_g ? (f.bset ^ 1) : (frames_alternate(c) ? f.tset : 0);
+    const int bi = !segmented ? 0 : f.geom.on_g ? (f.bset ^ 1) : (frames_alternate(c) ? f.bound.tset : 0);
     BinSet &B = c->bset[bi];
     int rc;
     if (!B.bins) {
-        size_t want = std::max<size_t>((size_t)f.geom_ntris * 8 + 4 * (size_t)c->max_tiles, (size_t)1 << 22);
+        size_t want = std::max<size_t>((size_t)f.geom.read.ntris * 8 + 4 * (size_t)c->max_tiles, (size_t)1 << 22);
         if (c->bin_cap_init) want = c->bin_cap_init;      // option bin_capacity (tests of the replay)
         want = std::max(want, c->bset[bi ^ 1].bins.cap());   // (what the other workspace has grown to)
         if ((rc = ensure(c, B.bins, want)) != FRR_OK) return rc;
@@ -1083,7 +1084,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         const uint32_t ltiles = std::max<uint32_t>(grid, 1u);   // the binning numbers the rank's OWN tiles only (local_tile_row)
         // segmented LDS multi-split (one launch, no per-entry global atomics): G chunk workgroups, ~3K triangles each
         // (small meshes: one triangle per thread, so that the launch is not three workgroups doing all the work)
-        uint32_t G = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((f.geom_ntris + BIN_WG - 1) / BIN_WG, 1), BIN_MAX_G);
+        uint32_t G = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((f.geom.read.ntris + BIN_WG - 1) / BIN_WG, 1), BIN_MAX_G);
         if (c->bin_g > 0) G = (uint32_t)std::min(c->bin_g, BIN_MAX_G);
         G = std::min<uint32_t>(G, sh.nw == 3 ? 256u : (uint32_t)sh.nw * 64u); // the tile kernel reads one segment per thread (three waves: wave 0 reads a second one)
         // Option tile_order 1: the tile kernel records each tile's records in tile_cost; a later pass over the same grid on
@@ -1096,7 +1097,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
             B.cost_known = false;
             HIP_TRY(c, hipMemsetAsync(B.tile_cost, 0, (size_t)ltiles * sizeof(uint32_t), gs));
         }
-        const TileOrderKey okey = {grid, a.tiles_x, x0, x1, y0, y1, f.rank, f.world, a.own.blocked, sh.nw};
+        const TileOrderKey okey = {grid, a.tiles_x, x0, x1, y0, y1, f.bound.rank, f.bound.world, a.own.blocked, sh.nw};
         const bool ordered = tile_order_built(c->tile_order, c->in_replay, okey, B.cost_known, B.cost_key);
         const bool record = c->tile_order == TILE_ORDER_HEAVY_FIRST;
         a.tile_cost = record ? B.tile_cost : nullptr;
@@ -1105,7 +1106,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         // (+ one workgroup that scans the geometry kernel's block sums, unless an earlier launch has, and builds the order;
         // a binning workgroup fills a CU's LDS, so the launch stays within 256 workgroups: a 257th would wait for a whole
         // one to finish)
-        const int do_scan = f.scan_pending ? 1 : 0;
+        const int do_scan = f.geom.scan_pending ? 1 : 0;
         const uint32_t extra = (do_scan || ordered) ? 1u : 0u;
         if (extra && G > 255u) G = 255u;
         if ((rc = ensure(c, B.bin_matrix, (size_t)BIN_MAX_G * ((size_t)c->max_tiles + 1))) != FRR_OK) return rc;
@@ -1120,7 +1121,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         }
         a.seg = B.bin_matrix; a.nseg = G; a.bpar = q;
         // near-first copies (bins2): a fixed slot per tile, 8x the mean tile load, + an overflow arena of bin_cap records
-        uint64_t SL = std::max<uint64_t>(256, (f.geom_ntris * 16 + ntiles - 1) / ntiles);   // (per-tile load of the whole window: ownership does not change it)
+        uint64_t SL = std::max<uint64_t>(256, (f.geom.read.ntris * 16 + ntiles - 1) / ntiles);   // (per-tile load of the whole window: ownership does not change it)
         SL = std::min<uint64_t>(SL, ((uint64_t)1 << 30) / ltiles);
         if (c->ent_slot_override) SL = c->ent_slot_override;
         a.ent_slot = (uint32_t)SL;
@@ -1131,14 +1132,14 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         {
             ProfScope p(c, KID_BIN_SEG, gs);
             hipLaunchKernelGGL(k_bin_seg, dim3(G + extra), dim3(BIN_WG), lds, gs, a, ltiles, B.bin_matrix, stage_cap,
-                               f.geom_fan_cap, S.block_sums, S.block_prefix, f.geom_nblocks, do_scan, perm_seed);
+                               f.geom.fan_cap, S.block_sums, S.block_prefix, f.geom.nblocks, do_scan, perm_seed);
         }
         // The tile kernel launched below writes every tile's cost -- unless the pass is cancelled (a list overflowed): then
         // the costs stay what an earlier pass (or the zeroing above) left, and the replay of the pass writes them.  Any values
         // give a permutation (build_tile_perm); only how well it orders depends on them.
         B.cost_known = record; B.cost_key = okey;
         if (ordered) ++c->ordered_passes;
-        f.scan_pending = false;
+        f.geom.scan_pending = false;
         f.bpars[f.lane] = q; f.bset = bi;
     } else {
         // fallback for frames with more tiles than fit LDS counters: global atomics (one set of tile tables: after every
@@ -1146,32 +1147,20 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         for (GeomSet &G2 : c->gset) if ((rc = gstream_wait_readers(c, G2.reader)) != FRR_OK) return rc;
         for (BinSet &B2 : c->bset) if ((rc = gstream_wait_readers(c, B2.reader)) != FRR_OK) return rc;
         if ((rc = scan_now(c)) != FRR_OK) return rc;
-        const uint32_t bin_grid = (uint32_t)std::min<uint64_t>((f.geom_ntris + f.geom_fan_cap + 255) / 256, 2048);
-        { ProfScope p(c, KID_BIN_COUNT, gs); hipLaunchKernelGGL(k_bin<false>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom_fan_cap); }
+        const uint32_t bin_grid = (uint32_t)std::min<uint64_t>((f.geom.read.ntris + f.geom.fan_cap + 255) / 256, 2048);
+        { ProfScope p(c, KID_BIN_COUNT, gs); hipLaunchKernelGGL(k_bin<false>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom.fan_cap); }
         { ProfScope p(c, KID_TILE_SCAN, gs); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, gs, a, ntiles); }
-        { ProfScope p(c, KID_BIN_FILL, gs); hipLaunchKernelGGL(k_bin<true>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom_fan_cap); }
+        { ProfScope p(c, KID_BIN_FILL, gs); hipLaunchKernelGGL(k_bin<true>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom.fan_cap); }
     }
     cmd.par = q; cmd.set = bi; cmd.lane = f.lane;
     HIP_TRY(c, hipGetLastError());
     if (!c->in_replay) {
         // does this pass's need of the work lists fit for sure?  (exec_cmd waits for the event if not: frr_ctx::proven)
-        DrawSig sig;
-        memset(&sig, 0, sizeof sig);
-        sig.inst = f.geom_inst; sig.inst_gen = f.geom_inst_gen; sig.ninst = f.geom_ninst;
-        sig.list = f.geom_list; sig.list_gen = f.geom_list_gen;
-        sig.mesh = f.geom_mesh; sig.mesh_gen = f.geom_mesh_gen; sig.ntris = f.geom_ntris; sig.duni_hash = f.geom_duni_hash; sig.join_epoch = c->join_epoch;
-        sig.tex_epoch = f.geom_tex_epoch; sig.sync_epoch = f.geom_sync_epoch;
-        sig.vs = f.geom_vs; sig.x0 = x0; sig.x1 = x1; sig.y0 = y0; sig.y1 = y1; sig.rank = f.rank; sig.world = f.world;
-        sig.blocked = f.part_blocked ? 1 : 0; sig.filter = f.geom_filter.active ? 1 : 0; sig.fy0 = f.geom_filter.y0; sig.fy1 = f.geom_filter.y1;
-        sig.gset = f.gset; sig.bset = bi; sig.cull = f.geom_cull;
-        // (a predicated pass is never known: which items it keeps is device data, so neither its own earlier runs nor the
-        // unpredicated pass over the same list say what it needs -- and it proves nothing for anybody else)
-        bool known = false;
-        if (!f.geom_pred) for (const DrawSig &p : c->proven) known = known || same_sig(p, sig);
-        if (!known) {
+        const DrawSig sig = draw_sig(f.geom.read, x0, x1, y0, y1, f.bound.rank, f.bound.world, f.bound.part_blocked, f.geom.set, bi, c->join_epoch);
+        if (!c->proven.known(sig, f.geom.pred)) {
             HIP_TRY(c, hipEventRecord(c->ev_verify, gs));
             c->verify_pending = true;
-            c->verify_proves = !f.geom_pred;
+            c->verify_pred = f.geom.pred;
             c->verify_sig = sig;
         }
     }
@@ -1183,7 +1172,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     // x0 < 0: the depth stride x1 is smaller than the window's width and pixels of neighbouring rows share depth entries,
     // which only a resolve per ENTRY reproduces (k_raster_entries).  On a partitioned ctx the pixels of an entry belong to
     // different ranks, each with a depth buffer of its own: there the tile kernels run as for any window.
-    const bool shared_entries = ww > (int64_t)x1 && f.world <= 1;
+    const bool shared_entries = ww > (int64_t)x1 && f.bound.world <= 1;
     // the span algebra needs every coordinate it touches within +-SPAN_SAFE (no i32 wrap)
     const int win_safe = a.x0 >= -SPAN_SAFE && a.y0 >= -SPAN_SAFE && a.x1 <= SPAN_SAFE && a.y1 <= SPAN_SAFE;
     if (grid && shared_entries) {
@@ -1222,11 +1211,11 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     HIP_TRY(c, hipGetLastError());
     if ((rc = tile_launched(c, ts, S, B)) != FRR_OK) return rc;
     if (fuse) {
-        f.clear_pending = false;
+        f.clear.pending = false;
         // the tile rows of other ranks missed this clear: owed to the ctx's own targets (frr_readback shows the
         // whole image); caller-bound targets of a partitioned ctx only ever have their owned rows defined
-        f.unowned_debt = f.world > 1 && own_targets(c);
-        f.debt_tiles_y = a.tiles_y;
+        f.clear.unowned_debt = f.bound.world > 1 && own_targets(c);
+        f.clear.debt_tiles_y = a.tiles_y;
     }
     return FRR_OK;
 }
@@ -1240,15 +1229,15 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
     const bool wire = cmd.lines < 0;
     int rc;
     if (wire && (rc = scan_now(c)) != FRR_OK) return rc;   // a fan space that was too small is flagged before the edges are read (they are then cancelled, and replayed)
-    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
     LinesArgs a;
     memset(&a, 0, sizeof a);
     uint32_t batches;
     if (wire) {
-        const GeomSet &S = c->gset[f.gset];
-        a.recs = S.recs; a.tinfo = S.tinfo; a.fan_cap = f.geom_fan_cap; a.wire_rgba = cmd.wire_rgba;
+        const GeomSet &S = c->gset[f.geom.set];
+        a.recs = S.recs; a.tinfo = S.tinfo; a.fan_cap = f.geom.fan_cap; a.wire_rgba = cmd.wire_rgba;
         a.gpar = f.gpar(); a.lane = f.lane;
-        batches = (uint32_t)((3ull * (f.geom_ntris + f.geom_fan_cap) + 63) / 64);
+        batches = (uint32_t)((3ull * (f.geom.read.ntris + f.geom.fan_cap) + 63) / 64);
         if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     } else {
         const Lines &L = c->lines[cmd.lines];
@@ -1270,7 +1259,7 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
     a.own = row_owner(f, (int)((c->H + TILE - 1) / TILE));
     a.chunk = c->lines_chunk ? c->lines_chunk : LINES_CHUNK;
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
-    a.owner = owner; a.color = (uint32_t *)f.color;
+    a.owner = owner; a.color = (uint32_t *)f.bound.color;
     const dim3 grid(std::max<uint32_t>(std::min<uint32_t>(batches, 16384u), 1u)), block(64);
     {
         ProfScope p(c, KID_LINES_MARK, ts);
@@ -1296,8 +1285,8 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     FrameState &f = c->fs;
     int rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass (a fan space that was too small is flagged here)
-    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
-    GeomSet &S = c->gset[f.gset];
+    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    GeomSet &S = c->gset[f.geom.set];
     const int par = f.gpar();
     bool fresh_table;
     if ((rc = ensure(c, S.vslot[par], S.recs.cap(), &fresh_table)) != FRR_OK) return rc;
@@ -1315,19 +1304,19 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     VaryArgs a;
     memset(&a, 0, sizeof a);
     a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
-    a.K = frr_vs_num_varyings(f.geom_vs);
+    a.K = frr_vs_num_varyings(f.geom.read.vs);
     a.recs = S.recs; a.vary = S.vary; a.tinfo = S.tinfo; a.fan_okey = S.fan_okey; a.block_prefix = S.block_prefix;
     a.table = S.vslot[par];
-    a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.recs.cap(), S.vslot[par].cap()), 0xFFFFFFFFu); a.fan_cap = f.geom_fan_cap;
-    a.ntris = (uint32_t)f.geom_ntris;
+    a.setup_cap = (uint32_t)std::min<size_t>(std::min(S.recs.cap(), S.vslot[par].cap()), 0xFFFFFFFFu); a.fan_cap = f.geom.fan_cap;
+    a.ntris = (uint32_t)f.geom.read.ntris;
     a.gpar = par; a.lane = f.lane;
     a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
-    a.tri_id = f.tri_id; a.out = cmd.vary_out;
-    if (S.vslot_seq[par] != f.geom_seq || S.vslot_epoch[par] != c->epoch) {   // (else: an earlier resolve of this pass built the table)
-        const uint32_t sgrid = (uint32_t)std::min<uint64_t>((f.geom_ntris + f.geom_fan_cap + VARY_WG - 1) / VARY_WG, 4096);
+    a.tri_id = f.bound.tri_id; a.out = cmd.vary_out;
+    if (S.vslot_seq[par] != f.geom.seq || S.vslot_epoch[par] != c->epoch) {   // (else: an earlier resolve of this pass built the table)
+        const uint32_t sgrid = (uint32_t)std::min<uint64_t>((f.geom.read.ntris + f.geom.fan_cap + VARY_WG - 1) / VARY_WG, 4096);
         hipLaunchKernelGGL(k_vary_slots, dim3(std::max<uint32_t>(sgrid, 1u)), dim3(VARY_WG), 0, ts, a);
-        S.vslot_seq[par] = f.geom_seq; S.vslot_epoch[par] = c->epoch;
+        S.vslot_seq[par] = f.geom.seq; S.vslot_epoch[par] = c->epoch;
     }
     const dim3 grid((unsigned)((ww + VARY_WG - 1) / VARY_WG), (unsigned)wh), block(VARY_WG);
     // 16-byte stores where every entry's address allows them: K a multiple of 4 and an aligned buffer
@@ -1342,6 +1331,17 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// *item_first: where the latest geometry pass, a list pass, keeps the first triangle of every item (GeomArgs::item_first); else null
+int list_item_first(frr_ctx *c, const uint32_t **item_first)
+{
+    const GeomRead &rd = c->fs.geom.read;
+    *item_first = nullptr;
+    if (rd.list < 0) return FRR_OK;
+    if (!slot_ok(c->lists, rd.list) || c->lists[rd.list].gen != rd.list_gen) return fail(c, FRR_ERR_INVALID, "the draw list of the latest geometry pass was freed");
+    *item_first = c->lists[rd.list].first;
+    return FRR_OK;
+}
+
 // frr_visible_pixels: the triangle-id target of a window as counts per item of the latest geometry pass, or per triangle of
 // the frame (frr_visible.h).  Ordered like frr_resolve_varyings: on the targets' stream behind the pass's geometry, it reads
 // the pass's tables on the device (no host wait), cannot fail there and owns no device table, so a replay runs it again in
@@ -1351,37 +1351,34 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
     FrameState &f = c->fs;
     int rc;
     if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass
-    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
     const bool item = cmd.vis_unit == FRR_PER_ITEM;
     const bool cleared = f.draws == 0;   // frr_clear since the pass: the id target holds nothing of it, and its tables are gone
     const uint32_t *item_first = nullptr;
-    if (item && !cleared && f.geom_list >= 0) {
-        if (!slot_ok(c->lists, f.geom_list) || c->lists[f.geom_list].gen != f.geom_list_gen) return fail(c, FRR_ERR_INVALID, "the draw list of the latest geometry pass was freed");
-        item_first = c->lists[f.geom_list].first;
-    }
+    if (item && !cleared && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     hipStream_t ts = tstream_of(c);
     // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
     frame_stream_dirty(c, ts);
     // the units the histogram can meet: decides the path, and whether there is anything to count at all
-    const uint64_t bound = cleared ? 0 : item ? std::min<uint64_t>(f.geom_nitems, cmd.vis_entries) : cmd.vis_entries;
-    const GeomSet &S = c->gset[f.gset];
+    const uint64_t bound = cleared ? 0 : item ? std::min<uint64_t>(f.geom.nitems, cmd.vis_entries) : cmd.vis_entries;
+    const GeomSet &S = c->gset[f.geom.set];
     const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
     VisibleArgs a;
     memset(&a, 0, sizeof a);
     a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
     a.unit = cmd.vis_unit;
-    a.ntris = cleared ? 0u : (uint32_t)f.geom_ntris;
+    a.ntris = cleared ? 0u : (uint32_t)f.geom.read.ntris;
     a.tinfo = S.tinfo; a.block_prefix = S.block_prefix;
     if (item && bound > 0) {
         DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
-        if ((rc = ensure(c, tab, (size_t)f.geom_nitems + 1)) != FRR_OK) return rc;
-        a.nitems = (uint32_t)f.geom_nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom_stride; a.bounds = tab;
+        if ((rc = ensure(c, tab, (size_t)f.geom.nitems + 1)) != FRR_OK) return rc;
+        a.nitems = (uint32_t)f.geom.nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom.stride; a.bounds = tab;
     }
     a.gpar = f.gpar(); a.lane = f.lane;
     a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
-    a.tri_id = f.tri_id; a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
+    a.tri_id = f.bound.tri_id; a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
     const uint32_t cap = c->visible_lds_bins ? c->visible_lds_bins : VIS_LDS_BINS;
     const bool lds = bound <= cap;
     // rows per workgroup: a span is a chain of dependent loads, so what counts is waves in flight -- as many workgroups as
@@ -1423,7 +1420,7 @@ int exec_shade(frr_ctx *c, Cmd &cmd)
     int rc;
     const UserModule *um = nullptr;
     if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
-    if (f.clear_pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
     hipStream_t ts;
     if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
     const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
@@ -1434,8 +1431,8 @@ int exec_shade(frr_ctx *c, Cmd &cmd)
     a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
     a.id_first = cmd.id_first; a.id_count = cmd.id_count;
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
-    a.tri_id = f.tri_id; a.in = cmd.shade_in; a.in_entries = cmd.shade_entries;
-    a.color = (uint32_t *)f.color;
+    a.tri_id = f.bound.tri_id; a.in = cmd.shade_in; a.in_entries = cmd.shade_entries;
+    a.color = (uint32_t *)f.bound.color;
     const dim3 grid((unsigned)((ww + SHADE_WG - 1) / SHADE_WG), (unsigned)wh);
     // 16-byte loads where every entry's address allows them: K a multiple of 4 and an aligned buffer
     const bool vec = cmd.shade_K > 0 && (cmd.shade_K & 3) == 0 && ((uintptr_t)cmd.shade_in & 15u) == 0u;
@@ -1478,9 +1475,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
             failed = *(volatile uint32_t *)c->host_bad != c->seen_bad;
         }
         if (failed) { const int rf = finish(c); if (rf != FRR_OK) return rf; }   // grows the lists and replays, as often as it takes
-        if (!c->verify_proves) return FRR_OK;
-        if (c->proven.size() >= 32) c->proven.erase(c->proven.begin());
-        c->proven.push_back(sig);
+        c->proven.add(sig, c->verify_pred);
         return FRR_OK;
     }
     if (c->log.size() >= 4096 && !c->in_replay) return finish(c);   // (a caller that never synchronises: bound the log)
@@ -1551,20 +1546,17 @@ int finish(frr_ctx *c)
         // replay
         std::vector<Cmd> todo(c->log.begin() + (ptrdiff_t)i, c->log.end());
         c->log.resize(i);
-        const FrameState now = c->fs;
+        const Bound now = c->fs.bound;
         c->fs = todo[0].pre;
         c->epoch = c->next_seq;
         c->in_replay = true;
         ++c->replays;
         for (const Cmd &m : todo) {
-            // what the caller set between the commands travels with them
-            c->fs.color = m.pre.color; c->fs.depth = m.pre.depth; c->fs.tri_id = m.pre.tri_id; c->fs.tset = m.pre.tset;
-            c->fs.rank = m.pre.rank; c->fs.world = m.pre.world; c->fs.part_blocked = m.pre.part_blocked;
+            c->fs.bound = m.pre.bound;   // what the caller set between the commands travels with them
             if ((rc = exec_cmd(c, m)) != FRR_OK) { c->in_replay = false; return rc; }
         }
         c->in_replay = false;
-        c->fs.color = now.color; c->fs.depth = now.depth; c->fs.tri_id = now.tri_id; c->fs.tset = now.tset;
-        c->fs.rank = now.rank; c->fs.world = now.world; c->fs.part_blocked = now.part_blocked;
+        c->fs.bound = now;
         if ((rc = settle(c)) != FRR_OK) return rc;
     }
     drop_log(c);
@@ -1590,7 +1582,7 @@ int ps_check(frr_ctx *c, VaryingsFrom from, int ps_id, int K)
 // that touch the rank's tile rows of its window (frr_raster of that window and partition alone takes such a list: raster_check)
 int need_unfiltered_list(frr_ctx *c, const char *who)
 {
-    if (!c->fs.geom_filter.active) return FRR_OK;
+    if (!c->fs.geom.read.filter) return FRR_OK;
     return fail(c, FRR_ERR_INVALID, std::string("the setup list of a partitioned frr_draw holds only this rank's triangles; run frr_geometry* (unfiltered) and frr_raster before ") + who);
 }
 // the common part of a command: its kind, the uniforms and the cull mode at the time of the call, its window
@@ -1608,7 +1600,7 @@ int geometry_count(frr_ctx *c, uint64_t *ntris_setup)
     if (!ntris_setup) return FRR_OK;
     const int rc = finish(c);
     if (rc != FRR_OK) return rc;
-    *ntris_setup = c->fs.geom_ntris ? c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit : 0;
+    *ntris_setup = c->fs.geom.read.ntris ? c->hc.lane[c->fs.lane].gtab[c->fs.gpar()].n_emit : 0;
     return FRR_OK;
 }
 // The host form of a command that writes a caller's buffer (`out`: which field of the command names it): the command runs
@@ -1683,7 +1675,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
                      &c->ev_bin[0], &c->ev_bin[1], &c->ev_bin[2], &c->ev_bin[3], &c->ev_join, &c->wire_reader[0].ev, &c->wire_reader[1].ev,
                      &c->ev_verify, &c->ev_export, &c->ev_keep[0], &c->ev_keep[1], &c->ev_keep[2], &c->ev_keep[3]}) ok = ok && e->create() == hipSuccess;
     if (!ok) { frr_destroy(c); return FRR_ERR_NOMEM; }
-    c->fs.color = c->own_color[0]; c->fs.depth = c->own_depth[0]; c->fs.tri_id = c->own_tri_id[0];
+    c->fs.bound.color = c->own_color[0]; c->fs.bound.depth = c->own_depth[0]; c->fs.bound.tri_id = c->own_tri_id[0];
     // tables of frame 0 (no frame has that number), no failed command
     memset(&c->hc, 0, sizeof c->hc);
     c->hc.first_bad = SEQ_NONE;
@@ -1756,14 +1748,14 @@ int frr_set_partition(frr_ctx *c, int rank, int world)
 {
     if (!c || world < 1 || rank < 0 || rank >= world) return fail(c, FRR_ERR_INVALID, "bad partition");
     { int rc = settle(c); if (rc != FRR_OK) return rc; } // rows skipped by a fused clear are defined by the old partition
-    c->fs.rank = rank; c->fs.world = world;
+    c->fs.bound.rank = rank; c->fs.bound.world = world;
     return FRR_OK;
 }
 int frr_set_partition_layout(frr_ctx *c, int blocked)
 {
     if (!c) return FRR_ERR_INVALID;
     { int rc = settle(c); if (rc != FRR_OK) return rc; }
-    c->fs.part_blocked = blocked != 0;
+    c->fs.bound.part_blocked = blocked != 0;
     return FRR_OK;
 }
 // owned tile rows of a window of `wh` pixel rows, by the same rule the kernels use (owns_tile_row)
@@ -1790,7 +1782,7 @@ static int owned_band_of(int rank, int world, bool blocked, int64_t wh, int band
 }
 static int owned_band(const frr_ctx *c, int64_t wh, int band, int32_t *row0, int32_t *row1)
 {
-    return owned_band_of(c->fs.rank, c->fs.world, c->fs.part_blocked, wh, band, row0, row1);
+    return owned_band_of(c->fs.bound.rank, c->fs.bound.world, c->fs.bound.part_blocked, wh, band, row0, row1);
 }
 int frr_partition_rows(int32_t y0, int32_t y1, int rank, int world, int blocked, int32_t band, int32_t *row0, int32_t *row1)
 {
@@ -1850,12 +1842,13 @@ int frr_bind_targets(frr_ctx *c, void *color, void *depth, void *tri_id)
     if (!color || !depth || !tri_id) {
         // (part of) the ctx's own set: frames on bound targets may have toggled the set index without it ever being allocated
         if (c->bound_in_flight) { int rc = finish(c); if (rc != FRR_OK) return rc; }   // back to own targets: nothing of the bound frames in flight
-        int rc = ensure_own_set(c, c->fs.tset);
+        int rc = ensure_own_set(c, c->fs.bound.tset);
         if (rc != FRR_OK) return rc;
     }
-    c->fs.color = color ? (uint8_t *)color : c->own_color[c->fs.tset];
-    c->fs.depth = depth ? (float *)depth : c->own_depth[c->fs.tset];
-    c->fs.tri_id = tri_id ? (uint32_t *)tri_id : c->own_tri_id[c->fs.tset];
+    Bound &b = c->fs.bound;
+    b.color = color ? (uint8_t *)color : c->own_color[b.tset];
+    b.depth = depth ? (float *)depth : c->own_depth[b.tset];
+    b.tri_id = tri_id ? (uint32_t *)tri_id : c->own_tri_id[b.tset];
     return FRR_OK;
 }
 int frr_target_ptrs(frr_ctx *c, void **color, void **depth, void **tri_id)
@@ -1863,10 +1856,10 @@ int frr_target_ptrs(frr_ctx *c, void **color, void **depth, void **tri_id)
     if (!c) return FRR_ERR_INVALID;
     { int rc = settle(c); if (rc != FRR_OK) return rc; } // the caller is about to look at them ...
     { int rc = join_tile_streams(c); if (rc != FRR_OK) return rc; } // ... from its stream
-    if (own_targets(c)) { c->exported[c->fs.tset] = true; c->export_stream[c->fs.tset] = c->stream; }   // (frr_clear orders the set's next frame behind those reads)
-    if (color) *color = c->fs.color;
-    if (depth) *depth = c->fs.depth;
-    if (tri_id) *tri_id = c->fs.tri_id;
+    if (own_targets(c)) { c->exported[c->fs.bound.tset] = true; c->export_stream[c->fs.bound.tset] = c->stream; }   // (frr_clear orders the set's next frame behind those reads)
+    if (color) *color = c->fs.bound.color;
+    if (depth) *depth = c->fs.bound.depth;
+    if (tri_id) *tri_id = c->fs.bound.tri_id;
     return FRR_OK;
 }
 
@@ -2016,11 +2009,11 @@ int frr_draw_wireframe(frr_ctx *c, const uint8_t rgba[4])
 {
     if (!c || !rgba) return fail(c, FRR_ERR_INVALID, "bad arguments");
     const FrameState &f = c->fs;
-    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_draw_wireframe before frr_geometry");
+    if (f.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_draw_wireframe before frr_geometry");
     { const int rc = need_unfiltered_list(c, "frr_draw_wireframe"); if (rc != FRR_OK) return rc; }
-    if (f.geom_ntris == 0) return FRR_OK;
+    if (f.geom.read.ntris == 0) return FRR_OK;
     // (segment numbers + 1 are u32, and a wave's last batch of 64 must not wrap either)
-    if (3ull * (f.geom_ntris + f.geom_fan_cap) + 64ull >= 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "wireframe: more than 2^32 / 3 setup slots (owner numbers are u32)");
+    if (3ull * (f.geom.read.ntris + f.geom.fan_cap) + 64ull >= 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "wireframe: more than 2^32 / 3 setup slots (owner numbers are u32)");
     HIP_TRY(c, hipSetDevice(c->device));
     Cmd cmd = new_cmd(c, Cmd::LINES);
     cmd.lines = -1;
@@ -2171,17 +2164,17 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
     c->replays = 0;
     f.frame_no += 1;
     f.tris_in = 0; f.draws = 0;
-    f.geom_ntris = 0;          // the setup list of a preceding frr_geometry is gone (frr_raster then draws nothing)
-    f.scan_pending = false;
-    f.unowned_debt = false;    // superseded: the clear covers every row
+    f.geom.setup_list_gone();        // (of a preceding frr_geometry)
+    f.geom.scan_pending = false;
+    f.clear.unowned_debt = false;    // superseded: the clear covers every row
     if (c->frames_in_flight == 2 && own_targets(c)) {
         // own targets: this frame takes the other set (and its tile kernels the other stream), so that it need not wait
         // for the previous frame's tile kernel to drain; the old set's content is dead (the clear overwrites everything)
-        const int t = f.tset ^ 1;
+        const int t = f.bound.tset ^ 1;
         { const int rc = ensure_own_set(c, t); if (rc != FRR_OK) return rc; }
         if (!c->tstream[1].st && acquire_stream(c->device, &c->tstream[1].st) != hipSuccess) return fail(c, FRR_ERR_HIP, "frame stream");
-        f.tset = t;
-        f.color = c->own_color[t]; f.depth = c->own_depth[t]; f.tri_id = c->own_tri_id[t];
+        f.bound.tset = t;
+        f.bound.color = c->own_color[t]; f.bound.depth = c->own_depth[t]; f.bound.tri_id = c->own_tri_id[t];
         f.lane = t;    // ... and its own device tables: nothing the two frames' bookkeeping threads write is shared
     } else if (frames_alternate(c)) {
         // caller-bound targets, option bound_targets_in_flight: the caller has bound another target set for this frame;
@@ -2189,26 +2182,26 @@ int frr_clear(frr_ctx *c, const uint8_t rgba[4], float depth)
         bool ok = (c->tstream[1].st || acquire_stream(c->device, &c->tstream[1].st) == hipSuccess) &&
                   (c->tstream[0].st || acquire_stream(c->device, &c->tstream[0].st) == hipSuccess);
         if (!ok) return fail(c, FRR_ERR_HIP, "frame streams");
-        f.tset ^= 1;
-        f.lane = f.tset;
+        f.bound.tset ^= 1;
+        f.lane = f.bound.tset;
     } else {
         f.lane = 0;
     }
-    if (own_targets(c) && c->exported[f.tset]) {
+    if (own_targets(c) && c->exported[f.bound.tset]) {
         // The pointers of this own target set were handed out (frr_target_ptrs / frr_frame_fence) when it last held a frame:
         // what the caller has queued on that stream since -- its reads of that frame -- comes before this frame's writes.
         // (Same stream: in order anyway.  Only callers that take the pointers pay for the event.)
-        c->exported[f.tset] = false;
+        c->exported[f.bound.tset] = false;
         hipStream_t ts = tstream_of(c);
-        if (c->export_stream[f.tset] != ts) {
-            HIP_TRY(c, hipEventRecord(c->ev_export, c->export_stream[f.tset]));
+        if (c->export_stream[f.bound.tset] != ts) {
+            HIP_TRY(c, hipEventRecord(c->ev_export, c->export_stream[f.bound.tset]));
             HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_export, 0));
         }
     }
-    if (c->clear_eager) { f.clear_pending = false; return clear_now(c, packed, depth, true); }
-    f.clear_rgba = packed; f.clear_depth = depth;
-    f.clear_pending = true;
-    f.clear_wait_serial = c->wait_serial;
+    if (c->clear_eager) { f.clear.pending = false; return clear_now(c, packed, depth, true); }
+    f.clear.rgba = packed; f.clear.depth = depth;
+    f.clear.pending = true;
+    f.clear.wait_serial = c->wait_serial;
     return FRR_OK;
 }
 
@@ -2369,23 +2362,20 @@ int frr_geometry_list_if(frr_ctx *c, int list, const void *dev_keep_u32, uint64_
 }
 int frr_geometry_item_ranges(frr_ctx *c, uint32_t *id_first, uint32_t *id_count, uint64_t cap, uint64_t *nitems)
 {
-    if (!c || !nitems || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry pass to take item ranges from");
+    if (!c || !nitems || c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, "no geometry pass to take item ranges from");
     { const int rc = need_unfiltered_list(c, "frr_geometry_item_ranges"); if (rc != FRR_OK) return rc; }
     { int rcs = finish(c); if (rcs != FRR_OK) return rcs; }
     const FrameState &f = c->fs;
     const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
-    const GeomSet &S = c->gset[f.gset];
-    const uint64_t n = f.geom_nitems, w = std::min(cap, n);
+    const GeomSet &S = c->gset[f.geom.set];
+    const uint64_t n = f.geom.nitems, w = std::min(cap, n);
     const uint32_t *item_first = nullptr;
-    if (f.geom_list >= 0) {
-        if (!slot_ok(c->lists, f.geom_list) || c->lists[f.geom_list].gen != f.geom_list_gen) return fail(c, FRR_ERR_INVALID, "the draw list of the latest geometry pass was freed");
-        item_first = c->lists[f.geom_list].first;
-    }
+    { const int rc = list_item_first(c, &item_first); if (rc != FRR_OK) return rc; }
     *nitems = n;
     if (!w || (!id_first && !id_count)) return FRR_OK;
-    const uint32_t nt = (uint32_t)f.geom_ntris, n_emit = nt ? gt.n_emit : 0u;
+    const uint32_t nt = (uint32_t)f.geom.read.ntris, n_emit = nt ? gt.n_emit : 0u;
     { int rc = ensure(c, c->item_tmp, (size_t)n + 1); if (rc != FRR_OK) return rc; }
-    hipLaunchKernelGGL(k_item_firsts, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, c->stream, item_first, (uint32_t)f.geom_stride, (uint32_t)n, nt,
+    hipLaunchKernelGGL(k_item_firsts, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, c->stream, item_first, (uint32_t)f.geom.stride, (uint32_t)n, nt,
                        S.tinfo.get(), S.block_prefix.get(), n_emit, c->item_tmp.get());
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> e(w + 1);
@@ -2408,22 +2398,22 @@ int64_t frr_host_list_item(const uint32_t *first, const uint32_t *ntris, uint64_
 static int raster_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, bool *nothing)
 {
     const FrameState &f = c->fs;
-    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_raster before frr_geometry");
+    if (f.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_raster before frr_geometry");
     int rc = rule_rc(c, window_rule(WINDOW_RASTER, c->W, c->H, x0, x1, y0, y1));
     // the mesh's vertex shader -- the same user shader, another one, or a built-in -- has to hand the pixel shader its varyings.
     // A list without items has no vertex shader (DrawList::vs is a placeholder): K_OF_NOTHING, as in draw_pass.
-    const bool no_vs = f.geom_list >= 0 && f.geom_nitems == 0;
-    if (rc == FRR_OK) rc = ps_check(c, no_vs ? K_OF_NOTHING : K_OF_GEOMETRY, ps_id, frr_vs_num_varyings(f.geom_vs));
+    const bool no_vs = f.geom.read.list >= 0 && f.geom.nitems == 0;
+    if (rc == FRR_OK) rc = ps_check(c, no_vs ? K_OF_NOTHING : K_OF_GEOMETRY, ps_id, frr_vs_num_varyings(f.geom.read.vs));
     if (rc != FRR_OK) return rc;
     {
         // frr_draw on a partitioned ctx keeps only the triangles that touch the rank's tile rows of ITS window; that
         // list serves no other window or partition (the reference may reuse one geometry for several ranges,
         // renderer.rs:269-271: use frr_geometry for that, it never filters)
-        const GeomFilter &gf = f.geom_filter;
-        if (gf.active && (gf.y0 != y0 || gf.y1 != y1 || gf.rank != f.rank || gf.world != f.world || gf.blocked != f.part_blocked))
+        const GeomPass &gp = f.geom;
+        if (gp.read.filter && (gp.read.fy0 != y0 || gp.read.fy1 != y1 || gp.part_rank != f.bound.rank || gp.part_world != f.bound.world || gp.part_blocked != f.bound.part_blocked))
             return fail(c, FRR_ERR_INVALID, "the setup list was filtered by frr_draw for another window/partition; re-run frr_geometry (unfiltered) before frr_raster");
     }
-    *nothing = x0 == x1 || y0 == y1 || f.geom_ntris == 0;
+    *nothing = x0 == x1 || y0 == y1 || f.geom.read.ntris == 0;
     return FRR_OK;
 }
 
@@ -2445,7 +2435,7 @@ int frr_raster(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_
 // (K_OF_NOTHING: the id has to name a shader, as frr_raster behind frr_geometry_list of it demands).
 static int draw_pass(frr_ctx *c, Cmd &cmd, bool raster, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1)
 {
-    cmd.filter = c->fs.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
+    cmd.filter = c->fs.bound.world > 1 && y0 <= y1; cmd.fy0 = y0; cmd.fy1 = y1;
     const int rc = exec_cmd(c, cmd);
     if (rc != FRR_OK) return rc;
     if (!raster) return ps_check(c, K_OF_NOTHING, ps_id, 0);
@@ -2488,7 +2478,7 @@ int frr_frame_fence(frr_ctx *c, void *stream)
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = settle(c); if (rc != FRR_OK) return rc; }
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (own_targets(c)) { c->exported[c->fs.tset] = true; c->export_stream[c->fs.tset] = st; }
+    if (own_targets(c)) { c->exported[c->fs.bound.tset] = true; c->export_stream[c->fs.bound.tset] = st; }
     return fence_stream(c, st);
 }
 
@@ -2523,35 +2513,35 @@ int frr_readback(frr_ctx *c, uint8_t *rgba, float *depth, uint32_t *tri_id)
     if (!c) return FRR_ERR_INVALID;
     { int rc = finish(c); if (rc != FRR_OK) return rc; }
     const size_t bytes = (size_t)c->W * c->H * 4;
-    if (rgba) HIP_TRY(c, hipMemcpyAsync(rgba, c->fs.color, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (depth) HIP_TRY(c, hipMemcpyAsync(depth, c->fs.depth, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (tri_id) HIP_TRY(c, hipMemcpyAsync(tri_id, c->fs.tri_id, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rgba) HIP_TRY(c, hipMemcpyAsync(rgba, c->fs.bound.color, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (depth) HIP_TRY(c, hipMemcpyAsync(depth, c->fs.bound.depth, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (tri_id) HIP_TRY(c, hipMemcpyAsync(tri_id, c->fs.bound.tri_id, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FRR_OK;
 }
 
 int frr_readback_setup(frr_ctx *c, frr_setup_vertex *out, uint64_t cap_tris, uint64_t *ntris)
 {
-    if (!c || !ntris || c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "no geometry to read back");
+    if (!c || !ntris || c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, "no geometry to read back");
     { const int rc = need_unfiltered_list(c, "frr_readback_setup (the full Vec<[Vertex;3]>)"); if (rc != FRR_OK) return rc; }
     { int rcs = finish(c); if (rcs != FRR_OK) return rcs; }
     const FrameState &f = c->fs;
     const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
-    const GeomSet &S = c->gset[f.gset];
-    const uint64_t nt = f.geom_ntris;
+    const GeomSet &S = c->gset[f.geom.set];
+    const uint64_t nt = f.geom.read.ntris;
     *ntris = nt ? gt.n_emit : 0;
     if (!out || !nt) return FRR_OK;
     // the records live at slots (frr_device.h): input t's own slot, or its fan's slots behind the inputs; walking the
     // inputs in order and each fan in order is the reference's emission order
-    const uint64_t slots = nt + f.geom_fan_cap;   // (fan slots are spread over the regions of the fan space)
-    const int K = frr_vs_num_varyings(f.geom_vs);
+    const uint64_t slots = nt + f.geom.fan_cap;   // (fan slots are spread over the regions of the fan space)
+    const int K = frr_vs_num_varyings(f.geom.read.vs);
     std::vector<uint32_t> tinfo(nt), fanbase(nt);
     std::vector<RasterRec> recs(slots);
     std::vector<float> vary((size_t)slots * 3 * K);
     HIP_TRY(c, hipMemcpy(tinfo.data(), S.tinfo, nt * 4, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(fanbase.data(), S.fanbase, nt * 4, hipMemcpyDeviceToHost));
     // the inputs' own slots, then the used part of every fan region
-    const uint64_t region = f.geom_fan_cap / FAN_REGIONS;
+    const uint64_t region = f.geom.fan_cap / FAN_REGIONS;
     for (int k = -1; k < FAN_REGIONS; ++k) {
         const uint64_t first = k < 0 ? 0 : nt + (uint64_t)k * region;
         const uint64_t count = k < 0 ? nt : std::min<uint64_t>(gt.fan_cursor[k].v, region);
@@ -2586,20 +2576,20 @@ static int vary_check(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1
 {
     if (!c) return FRR_ERR_INVALID;
     const FrameState &f = c->fs;
-    if (f.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
+    if (f.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_resolve_varyings before frr_geometry");
     int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
     if (rc == FRR_OK) rc = need_unfiltered_list(c, "frr_resolve_varyings");
     if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_VARYINGS_OUT, buf, out_entries, 0, x1, y0, y1));
     if (rc != FRR_OK) return rc;
-    *K = frr_vs_num_varyings(f.geom_vs);
-    *nothing = *K <= 0 || f.geom_ntris == 0;   // (geom_ntris == 0: an empty mesh, or frr_clear since -- the setup list is gone)
+    *K = frr_vs_num_varyings(f.geom.read.vs);
+    *nothing = *K <= 0 || f.geom.read.ntris == 0;   // (geom.read.ntris == 0: an empty mesh, or frr_clear since -- the setup list is gone)
     return FRR_OK;
 }
 
 int frr_geometry_num_varyings(const frr_ctx *c)
 {
-    if (!c || c->fs.geom_vs < 0) return FRR_ERR_INVALID;
-    return frr_vs_num_varyings(c->fs.geom_vs);
+    if (!c || c->fs.geom.none()) return FRR_ERR_INVALID;
+    return frr_vs_num_varyings(c->fs.geom.read.vs);
 }
 
 int frr_resolve_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_f32, uint64_t out_entries)
@@ -2634,7 +2624,7 @@ static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y
 {
     if (!c) return FRR_ERR_INVALID;
     if (unit != FRR_PER_ITEM && unit != FRR_PER_TRIANGLE) return fail(c, FRR_ERR_INVALID, "unknown frr_visible_unit");
-    if (c->fs.geom_vs < 0) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
+    if (c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
     int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
     if (rc == FRR_OK) rc = need_unfiltered_list(c, "frr_visible_pixels");
     if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, buf, out_entries, 0, x1, y0, y1));
@@ -2667,7 +2657,7 @@ int frr_visible_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_
     if (nunits) {
         const FrameState &f = c->fs;
         const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
-        *nunits = unit == FRR_PER_ITEM ? f.geom_nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom_ntris ? gt.n_emit : 0u);
+        *nunits = unit == FRR_PER_ITEM ? f.geom.nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom.read.ntris ? gt.n_emit : 0u);
     }
     return FRR_OK;
 }
