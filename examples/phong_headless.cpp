@@ -25,6 +25,9 @@
 //       pixel is dropped -- with no host wait between the count and the draw; it prints how many items the second frame dropped
 //       and whether its colour equals the first frame's.  (The mechanism only: an item that was hidden stays dropped until the
 //       caller's own policy sets its entry again.)
+//   --materials with --list --deferred gives every object a material of its own -- texture slots 0, 1, 2 in turn (the diffuse
+//       texture, and it with its first / its second channel inverted) and a flat colour in turn -- and shades the whole list
+//       with ONE pass over the frame (shade_items_host): phong.rs:361-370, a ps_uniform per object, for a list
 //   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
 //       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
@@ -52,10 +55,12 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false;
+    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false, materials = false;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible" || std::string(argv[i]) == "--reuse") {
-            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : std::string(argv[i]) == "--reuse" ? reuse : deferred) = true;
+        if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible" || std::string(argv[i]) == "--reuse" ||
+            std::string(argv[i]) == "--materials") {
+            (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : std::string(argv[i]) == "--reuse" ? reuse :
+             std::string(argv[i]) == "--materials" ? materials : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -77,6 +82,7 @@ int main(int argc, char **argv)
         }
     if (visible && !list && instances < 0) { std::cerr << "--visible goes with --list or --instances N\n"; return 2; }
     if (reuse && (!list || !visible || wireframe || deferred)) { std::cerr << "--reuse goes with --list --visible (and without --wireframe / --deferred)\n"; return 2; }
+    if (materials && (!list || !deferred)) { std::cerr << "--materials goes with --list --deferred\n"; return 2; }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -98,7 +104,8 @@ int main(int argc, char **argv)
                      "        --instances N: N copies on a grid in one instanced pass; --list: the objects as one list pass;\n"
                      "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign;\n"
                      "        --visible (with --list or --instances N): print the pixels every item owns on screen;\n"
-                     "        --reuse (with --list --visible): a second frame by draw_list_if on the first one's counts)\n";
+                     "        --reuse (with --list --visible): a second frame by draw_list_if on the first one's counts;\n"
+                     "        --materials (with --list --deferred): a texture slot and a flat colour per object, one shade_items)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -175,7 +182,29 @@ int main(int argc, char **argv)
             renderer.rasterization({0, (int32_t)W}, {0, (int32_t)H}, FRR_PS_DEPTH);             // loop B without renderer.rs:380-381 ...
             std::vector<float> varyings;
             const int num_varyings = renderer.readback_varyings(varyings);                      // ... its `input` (:368-378) per pixel ...
-            renderer.shade_varyings_host(FRR_PS_PHONG, varyings, num_varyings);                 // ... and :380-381 over that buffer
+            if (!materials) renderer.shade_varyings_host(FRR_PS_PHONG, varyings, num_varyings); // ... and :380-381 over that buffer
+            else {
+                // ... under a ps_uniform per object (phong.rs:34-47, 361-370): slots 1 and 2 hold the diffuse texture with its
+                // first / second channel inverted, object k samples slot k % 3; one pass over the frame for all of them
+                for (int slot = 1; slot <= 2; ++slot) {
+                    frr::FrameBuffer t = diffuse;
+                    for (size_t i = (size_t)slot - 1; i < t.get_data_mut().size(); i += 4) t.get_data_mut()[i] = (uint8_t)(255 - t.get_data_mut()[i]);
+                    renderer.set_texture(slot, t);
+                }
+                std::vector<frr_material> mats(models.size());
+                for (size_t k = 0; k < mats.size(); ++k) {
+                    frr_material &m = mats[k];
+                    std::memset(&m, 0, sizeof m);
+                    m.texture_slot = (int32_t)(k % 3);
+                    m.ambient_strength = renderer.uniforms.ambient_strength; m.specular_strength = renderer.uniforms.specular_strength;
+                    for (int ch = 0; ch < 3; ++ch) m.flat_color[ch] = (float)((k + (size_t)ch) % 4) / 3.0f;
+                    m.flat_color[3] = 1.0f;
+                }
+                frr::Materials table = renderer.upload_materials(mats);
+                renderer.shade_items_host(FRR_PS_PHONG, varyings, num_varyings, table);
+                renderer.free_materials(table);                                                 // (finishes the shade first)
+                std::printf("materials: n=%zu\n", mats.size());
+            }
         }
         if (visible) {
             // which objects ended up on screen: the id target counted per item on the device (the wireframe and the shade pass

@@ -34,6 +34,8 @@ CULL_NONE, CULL_NEG, CULL_POS = 0, 1, 2
 PER_ITEM, PER_TRIANGLE = 0, 1
 VISIBLE_LDS_BINS = 4096   # units the LDS histogram of frr_visible_pixels takes (frr_visible.h: VIS_LDS_BINS)
 MAX_VARYINGS = 16
+MAX_TEXTURES = 4
+MATERIAL_USER = 8   # floats of u.user a material replaces (include/frr.h: FRR_MATERIAL_USER)
 
 
 class FrrError(RuntimeError):
@@ -57,6 +59,12 @@ class SetupVertex(C.Structure):
 
 class DrawItem(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("reserved", C.c_int32), ("model", C.c_float * 16)]
+
+
+class Material(C.Structure):
+    """frr_material: the pixel uniforms of one item of a pass (frr_shade_items), 64 bytes"""
+    _fields_ = [("texture_slot", C.c_int32), ("ambient_strength", C.c_float), ("specular_strength", C.c_float), ("reserved", C.c_int32),
+                ("flat_color", C.c_float * 4), ("user", C.c_float * MATERIAL_USER)]
 
 
 class Xfer(C.Structure):
@@ -154,6 +162,12 @@ SIGNATURES = {
     "frr_shade_varyings_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32]),
     "frr_visible_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
     "frr_visible_pixels_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "frr_materials_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_materials_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
+    "frr_materials_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "frr_shade_items": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int, C.c_int]),
+    "frr_shade_items_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int, C.c_int]),
+    "frr_host_entry_items": (C.c_int64, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "frr_host_visible_counts": (C.c_int64, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "frr_host_line_pixels": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
     "frr_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),

@@ -35,9 +35,10 @@ FRR_EMBED(frr_src_exact_h, "frr_exact.h");
 FRR_EMBED(frr_src_kernels_h, "frr_kernels.h");
 FRR_EMBED(frr_src_raster_h, "frr_raster.h");
 FRR_EMBED(frr_src_shade_h, "frr_shade.h");
+FRR_EMBED(frr_src_visible_h, "frr_visible.h");
 FRR_EMBED(frr_src_frr_h, "../../include/frr.h");
 #endif
-extern "C" const char frr_src_device_h[], frr_src_exact_h[], frr_src_kernels_h[], frr_src_raster_h[], frr_src_shade_h[], frr_src_frr_h[];
+extern "C" const char frr_src_device_h[], frr_src_exact_h[], frr_src_kernels_h[], frr_src_raster_h[], frr_src_shade_h[], frr_src_visible_h[], frr_src_frr_h[];
 
 using namespace frr;
 static_assert(PASS_FAN_BITS == FAN_BITS && MAX_PASS_INPUTS << FAN_BITS == 1ull << PASS_ORDER_KEY_BITS, "frr_rules.h: an input's order keys are 32 * input + (0 .. 31), in 32 bits (frr_device.h)");
@@ -79,6 +80,14 @@ struct Instances {
     bool used = false;
     uint64_t gen = 0;              // which registration of the ctx this is (DrawSig, like Mesh::gen)
 };
+// a material table (frr_materials_upload / frr_materials_bind_device): one frr_material per item of a pass (frr_shade_items)
+struct Materials {
+    DevBuf<frr_material> own;          // a host upload: the library's copy; else empty, and dev is the caller's
+    const frr_material *dev = nullptr; // [n], 16-byte aligned, every entry material_ok when registered
+    uint64_t n = 0;
+    uint32_t slots = 0;                // bit s: some entry names texture slot s (a lit shader needs a texture there)
+    bool used = false;
+};
 // a draw list (frr_drawlist_upload): a snapshot of its items -- per item the mesh's pointers, counts and generation, and the
 // model matrix -- so a pass over it reads nothing of frr_ctx::meshes.  Freeing a mesh it names kills it for good (dead).
 struct DrawList {
@@ -111,7 +120,7 @@ struct UserShader {
     std::vector<char> code;
     std::string geom_inst[2], clip_inst[2];   // ... of an instanced pass ([indexed mesh])
     std::string geom_list, clip_list;         // ... of a list pass
-    std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6], shade[2];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel; shade: k_shade_vary [16-byte loads])
+    std::string geom, clip, geom_idx, clip_idx, sweep, entries, span[2][6], shade[2], shade_items[2];   // lowered kernel names (geom_idx / clip_idx: the geometry kernels of an indexed mesh; [count fragments][shape]; sweep: the brute-force tile kernel; shade / shade_items: k_shade_vary / k_shade_items [16-byte loads])
 };
 std::mutex g_shader_mu;
 std::vector<UserShader *> g_shaders;      // id = FRR_SHADER_USER_BASE + index; never shrinks
@@ -147,7 +156,7 @@ void release_stream(int device, hipStream_t st)
 struct UserModule {
     hipModule_t mod = nullptr;
     hipFunction_t geom_inst[2] = {}, clip_inst[2] = {}, geom_list = nullptr, clip_list = nullptr;
-    hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {}, shade[2] = {};
+    hipFunction_t geom = nullptr, clip = nullptr, geom_idx = nullptr, clip_idx = nullptr, sweep = nullptr, entries = nullptr, span[2][6] = {}, shade[2] = {}, shade_items[2] = {};
 };
 
 // One of the ctx's private frame streams (frr_ctx::tstream) and what orders it against the other streams.
@@ -248,7 +257,7 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE } kind;
+    enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE, SHADE_ITEMS } kind;
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -268,6 +277,9 @@ struct Cmd {
     // SHADE (frr_shade_varyings): the window in x0 .. y1, the shader in ps, the buffer ([shade_entries][shade_K]: the caller's,
     // or one of frr_ctx::shade_tmp) and the range of triangle ids
     const float *shade_in = nullptr; uint64_t shade_entries = 0; int shade_K = 0; uint32_t id_first = 0, id_count = 0;
+    // SHADE_ITEMS (frr_shade_items): SHADE's window, shader and buffer (no id range), and the material table -- a view: the
+    // table cannot go while the command is logged (frr_materials_free finishes first), and a replay reads it again
+    const frr_material *mats = nullptr;
     // VISIBLE (frr_visible_pixels): the window in x0 .. y1, the unit and the caller's buffer
     int vis_unit = 0; uint32_t *vis_out = nullptr; uint64_t vis_entries = 0;
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
@@ -379,6 +391,10 @@ struct frr_ctx {
     std::vector<Mesh> meshes;
     std::vector<Lines> lines;
     std::vector<Instances> instances;
+    std::vector<Materials> materials;
+    // frr_shade_items: what the material of an EMPTY texture slot samples (ShadeItemsArgs::zero_tex): one texel of zeros, so
+    // that frr::sample_2d of such a material reads memory that exists; written once by frr_create
+    DevBuf<uint8_t> zero_texel;
     uint64_t inst_gen = 0;          // instance tables registered so far (Instances::gen)
     std::vector<DrawList> lists;
     uint64_t list_gen = 0;          // draw lists uploaded so far (DrawList::gen)
@@ -388,7 +404,8 @@ struct frr_ctx {
     // commands of two frames in flight run beside each other.  Allocated and zeroed on first use.
     DevBuf<uint32_t> line_owner[3];
     uint32_t lines_chunk = 0;       // option lines_chunk (0: LINES_CHUNK)
-    // frr_visible_pixels: the item boundaries of a count in flight, one table per stream that can carry one (as line_owner)
+    // frr_visible_pixels, frr_shade_items: the item boundaries of a command in flight, one table per stream that can carry one
+    // (as line_owner); commands of one stream follow each other, and every one builds the table again
     DevBuf<uint32_t> vis_bounds[3];
     uint32_t visible_lds_bins = 0;  // option visible_lds_bins (0: VIS_LDS_BINS)
     // per lane of device tables: the latest wireframe reads its geometry pass's fan cursors, which the next pass IN THAT LANE
@@ -698,7 +715,10 @@ int user_module(frr_ctx *c, int id, const UserModule **out)
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) HIP_TRY(c, hipModuleGetFunction(&m.span[cnt][sh], m.mod, us->span[cnt][sh].c_str()));
     for (int vec = 0; vec < 2; ++vec)
-        if (!us->shade[vec].empty()) HIP_TRY(c, hipModuleGetFunction(&m.shade[vec], m.mod, us->shade[vec].c_str()));   // ([1]: only where K is a multiple of 4)
+        if (!us->shade[vec].empty()) {   // ([1]: only where K is a multiple of 4)
+            HIP_TRY(c, hipModuleGetFunction(&m.shade[vec], m.mod, us->shade[vec].c_str()));
+            HIP_TRY(c, hipModuleGetFunction(&m.shade_items[vec], m.mod, us->shade_items[vec].c_str()));
+        }
     *out = &(c->user_modules[id] = m);
     return FRR_OK;
 }
@@ -1453,6 +1473,70 @@ int exec_shade(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_shade_items: frr_shade_varyings with the pixel uniforms of each pixel's item (frr_shade.h: k_shade_items).  It writes a
+// target, so it is ordered like exec_shade; it reads the tables of the latest geometry pass on the device, so it also takes
+// the steps of exec_visible against that pass -- scan_now, tstream_wait_gstream, tables_read -- and the item boundaries are
+// built by that command's own k_visible_prep (with no counts to zero it writes the boundaries alone), into the same
+// per-stream table.  It cannot fail on the device and owns no device table, so a replay runs it again in its place, under
+// the uniforms of the call and over the material table as it is then.
+template <int K, int PS> void launch_shade_items(hipStream_t ts, dim3 grid, const ShadeItemsArgs &a, const DevUniforms &du, bool vec)
+{
+    if constexpr (K > 0 && K % 4 == 0) { if (vec) { hipLaunchKernelGGL((k_shade_items<K, PS, true>), grid, dim3(SHADE_WG), 0, ts, a, du); return; } }
+    hipLaunchKernelGGL((k_shade_items<K, PS, false>), grid, dim3(SHADE_WG), 0, ts, a, du);
+}
+int exec_shade_items(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    int rc;
+    const UserModule *um = nullptr;
+    if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
+    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass
+    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    const uint32_t *item_first = nullptr;
+    if ((rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
+    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
+    hipStream_t ts;
+    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
+    DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
+    if ((rc = ensure(c, tab, (size_t)f.geom.nitems + 1)) != FRR_OK) return rc;
+    const GeomSet &S = c->gset[f.geom.set];
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    VisibleArgs v;   // the boundaries, as a per-item count builds them
+    memset(&v, 0, sizeof v);
+    v.unit = FRR_PER_ITEM;
+    v.nitems = (uint32_t)f.geom.nitems; v.item_first = item_first; v.stride = (uint32_t)f.geom.stride; v.ntris = (uint32_t)f.geom.read.ntris;
+    v.tinfo = S.tinfo; v.block_prefix = S.block_prefix; v.bounds = tab;
+    v.gpar = f.gpar(); v.lane = f.lane;
+    v.seq = cmd.seq; v.epoch = c->epoch; v.cnt = c->cnt;
+    ShadeItemsArgs a;
+    memset(&a, 0, sizeof a);
+    a.s.x0 = cmd.x0; a.s.x1 = cmd.x1; a.s.y0 = cmd.y0; a.s.y1 = cmd.y1;
+    a.s.cstride = (int32_t)c->W;
+    a.s.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
+    a.s.seq = cmd.seq; a.s.epoch = c->epoch; a.s.cnt = c->cnt;
+    a.s.tri_id = f.bound.tri_id; a.s.in = cmd.shade_in; a.s.in_entries = cmd.shade_entries;
+    a.s.color = (uint32_t *)f.bound.color;
+    a.bounds = tab; a.nitems = v.nitems; a.mats = cmd.mats; a.zero_tex = c->zero_texel;
+    hipLaunchKernelGGL(k_visible_prep, dim3((uint32_t)std::min<uint64_t>(((uint64_t)v.nitems + 1 + VIS_WG - 1) / VIS_WG, 2048)), dim3(VIS_WG), 0, ts, v);
+    const dim3 grid((unsigned)((ww + SHADE_WG - 1) / SHADE_WG), (unsigned)wh);
+    const bool vec = cmd.shade_K > 0 && (cmd.shade_K & 3) == 0 && ((uintptr_t)cmd.shade_in & 15u) == 0u;
+    if (um) {
+        ShadeItemsArgs sa = a; DevUniforms d = cmd.duni;
+        void *args[] = {&sa, &d};
+        (void)hipModuleLaunchKernel(um->shade_items[vec ? 1 : 0], grid.x, grid.y, 1, SHADE_WG, 1, 1, 0, ts, args, nullptr);
+    } else {
+        switch (cmd.ps) {
+        case FRR_PS_FLAT: launch_shade_items<0, FRR_PS_FLAT>(ts, grid, a, cmd.duni, false); break;   // (reads no varying, whatever K the buffer has)
+        case FRR_PS_COLOR: launch_shade_items<3, FRR_PS_COLOR>(ts, grid, a, cmd.duni, false); break;
+        case FRR_PS_PHONG: launch_shade_items<8, FRR_PS_PHONG>(ts, grid, a, cmd.duni, vec); break;
+        case FRR_PS_BLINN: launch_shade_items<8, FRR_PS_BLINN>(ts, grid, a, cmd.duni, vec); break;
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    tables_read(c, cmd, ts);   // like a count
+    return FRR_OK;
+}
+
 int finish(frr_ctx *c);
 
 // run a command and remember it (finish() replays the commands from a failed one onwards)
@@ -1461,7 +1545,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : cmd.kind == Cmd::VISIBLE ? exec_visible(c, cmd) : exec_shade(c, cmd);
+    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : cmd.kind == Cmd::VISIBLE ? exec_visible(c, cmd) : cmd.kind == Cmd::SHADE_ITEMS ? exec_shade_items(c, cmd) : exec_shade(c, cmd);
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1531,7 +1615,7 @@ int finish(frr_ctx *c)
         // (line, varyings, count and shade commands in between own no table: the "next" command is the next geometry or raster pass)
         for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
-            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE || m.kind == Cmd::VISIBLE) continue;
+            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE || m.kind == Cmd::VISIBLE || m.kind == Cmd::SHADE_ITEMS) continue;
             ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
@@ -1669,7 +1753,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     else { if (acquire_stream(device, &c->stream) != hipSuccess) { delete c; return FRR_ERR_HIP; } c->own_stream = true; }
     const size_t npx = (size_t)width * height;
     c->max_tiles = ((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
-    bool ok = ensure_own_set(c, 0) == FRR_OK && c->cnt.reset(1) == hipSuccess;
+    bool ok = ensure_own_set(c, 0) == FRR_OK && c->cnt.reset(1) == hipSuccess && c->zero_texel.reset(16) == hipSuccess;
     for (DevBuf<uint32_t> *b : {&c->tile_counts, &c->tile_offsets, &c->tile_cursor}) ok = ok && b->reset((size_t)c->max_tiles + 1) == hipSuccess;
     for (Event *e : {&c->gset[0].reader.ev, &c->gset[1].reader.ev, &c->bset[0].reader.ev, &c->bset[1].reader.ev, &c->tstream[1].ev, &c->tstream[0].ev,
                      &c->ev_bin[0], &c->ev_bin[1], &c->ev_bin[2], &c->ev_bin[3], &c->ev_join, &c->wire_reader[0].ev, &c->wire_reader[1].ev,
@@ -1689,6 +1773,7 @@ int frr_create(int device, uint32_t width, uint32_t height, void *stream, frr_ct
     (void)hipMemsetAsync(c->own_color[0], 0, npx * 4, c->stream);      // FrameBuffer::new zero-fills (renderer.rs:423)
     (void)hipMemsetAsync(c->own_depth[0], 0, npx * 4, c->stream);
     (void)hipMemsetAsync(c->own_tri_id[0], 0xFF, npx * 4, c->stream);
+    (void)hipMemsetAsync(c->zero_texel, 0, 16, c->stream);
     for (Event &e : c->ev) (void)e.create(true);
     memset(&c->uni, 0, sizeof c->uni);
     frr_set_identity(c->uni.model); frr_set_identity(c->uni.view); frr_set_identity(c->uni.proj);
@@ -2084,10 +2169,10 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     src += "#include \"frr_device.h\"\n#line 1 \"user_shader\"\n";
     src += hip_source;
     src += "\n#include \"frr_kernels.h\"\n#include \"frr_shade.h\"\n";
-    const char *hdr_txt[] = {frr_src_device_h, frr_src_exact_h, frr_src_kernels_h, frr_src_raster_h, frr_src_shade_h, frr_src_frr_h};
-    const char *hdr_name[] = {"frr_device.h", "frr_exact.h", "frr_kernels.h", "frr_raster.h", "frr_shade.h", "../../include/frr.h"};
+    const char *hdr_txt[] = {frr_src_device_h, frr_src_exact_h, frr_src_kernels_h, frr_src_raster_h, frr_src_shade_h, frr_src_visible_h, frr_src_frr_h};
+    const char *hdr_name[] = {"frr_device.h", "frr_exact.h", "frr_kernels.h", "frr_raster.h", "frr_shade.h", "frr_visible.h", "../../include/frr.h"};
     hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "frr_user_program.hip", 6, hdr_txt, hdr_name) != HIPRTC_SUCCESS) return fail(c, FRR_ERR_HIP, "hiprtcCreateProgram");
+    if (hiprtcCreateProgram(&prog, src.c_str(), "frr_user_program.hip", 7, hdr_txt, hdr_name) != HIPRTC_SUCCESS) return fail(c, FRR_ERR_HIP, "hiprtcCreateProgram");
     UserShader *us = new UserShader();
     us->nf = vs_input_floats; us->K = num_varyings;
     const std::string U = std::to_string(FRR_SHADER_USER_BASE), Ks = std::to_string(num_varyings);
@@ -2112,7 +2197,8 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     // frr_shade_varyings (frr_shade.h): scalar loads, and -- where K allows them -- 16-byte loads
     const bool shade_vec = num_varyings > 0 && num_varyings % 4 == 0;
     const std::string shade_expr[2] = {"frr::k_shade_vary<" + Ks + ", " + U + ", false>", "frr::k_shade_vary<" + Ks + ", " + U + ", true>"};
-    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) (void)hiprtcAddNameExpression(prog, shade_expr[vec].c_str());
+    const std::string shade_items_expr[2] = {"frr::k_shade_items<" + Ks + ", " + U + ", false>", "frr::k_shade_items<" + Ks + ", " + U + ", true>"};   // frr_shade_items
+    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) { (void)hiprtcAddNameExpression(prog, shade_expr[vec].c_str()); (void)hiprtcAddNameExpression(prog, shade_items_expr[vec].c_str()); }
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh)
             exprs.push_back("frr::k_raster_span<" + Ks + ", " + U + ", " + (cnt ? "true" : "false") + ", " + std::to_string(kSpanShapes[sh][0]) + ", " + std::to_string(kSpanShapes[sh][1]) + ">");
@@ -2133,7 +2219,7 @@ int frr_shader_register(frr_ctx *c, const char *hip_source, int vs_input_floats,
     us->geom = lowered(exprs[0]); us->clip = lowered(exprs[1]); us->geom_idx = lowered(geom_idx_expr); us->clip_idx = lowered(clip_idx_expr); us->sweep = lowered(sweep_expr); us->entries = lowered(entries_expr);
     for (int idx = 0; idx < 2; ++idx) { us->geom_inst[idx] = lowered(geom_inst_expr[idx]); us->clip_inst[idx] = lowered(clip_inst_expr[idx]); }
     us->geom_list = lowered(geom_list_expr); us->clip_list = lowered(clip_list_expr);
-    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) us->shade[vec] = lowered(shade_expr[vec]);
+    for (int vec = 0; vec < (shade_vec ? 2 : 1); ++vec) { us->shade[vec] = lowered(shade_expr[vec]); us->shade_items[vec] = lowered(shade_items_expr[vec]); }
     for (int cnt = 0; cnt < 2; ++cnt)
         for (int sh = 0; sh < 6; ++sh) us->span[cnt][sh] = lowered(exprs[2 + (size_t)cnt * 6 + sh]);
     size_t cs = 0;
@@ -2722,6 +2808,139 @@ int frr_shade_varyings_host(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32
     for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == Cmd::SHADE && c->log[k].shade_in == dev;
     if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
     return rc;
+}
+
+// ---- per-item materials (frr_shade_items): tables of frr_material, one entry per item of a pass ----------------------
+static int bad_material(frr_ctx *c, uint64_t k)
+{
+    return fail(c, FRR_ERR_INVALID, "materials: entry " + std::to_string(k) + " has a texture_slot outside 0 .. " + std::to_string(FRR_MAX_TEXTURES - 1) + " or reserved != 0");
+}
+static int materials_register(frr_ctx *c, Materials &&t, uint64_t n, uint32_t slots, int *materials_out)
+{
+    if (t.own) t.dev = t.own;
+    t.n = n; t.slots = slots; t.used = true;
+    *materials_out = slot_put(c->materials, std::move(t));
+    return FRR_OK;
+}
+int frr_materials_upload(frr_ctx *c, const frr_material *mats, uint64_t n, int *materials_out)
+{
+    if (!c || !materials_out) return fail(c, FRR_ERR_INVALID, "bad material table");
+    { const int rc = rule_rc(c, materials_rule(MATERIALS_UPLOAD, mats, n)); if (rc != FRR_OK) return rc; }
+    uint32_t slots = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        if (!material_ok(mats[k])) return bad_material(c, k);
+        slots |= 1u << mats[k].texture_slot;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    Materials t;
+    if (n) { const int rc = upload(c, t.own, mats, (size_t)n * sizeof(frr_material), "material table"); if (rc != FRR_OK) return rc; }
+    return materials_register(c, std::move(t), n, slots, materials_out);
+}
+int frr_materials_bind_device(frr_ctx *c, const void *dev_mats, uint64_t n, int *materials_out)
+{
+    if (!c || !materials_out) return fail(c, FRR_ERR_INVALID, "bad material table");
+    { const int rc = rule_rc(c, materials_rule(MATERIALS_BIND, dev_mats, n)); if (rc != FRR_OK) return rc; }
+    if (n > 0xFFFFFFFFull) return fail(c, FRR_ERR_UNSUPPORTED, "2^32 materials or more");
+    uint32_t cell_h[2] = {0xFFFFFFFFu, 0u};   // the first bad entry, the slots the table names
+    if (n) {   // one reduction on the caller's stream -- behind whatever wrote the table -- and the host waits for it (a set-up call)
+        HIP_TRY(c, hipSetDevice(c->device));
+        DevBuf<uint32_t> cell;
+        if (cell.reset(2) != hipSuccess) return nomem(c, "check cell");
+        hipError_t e = hipMemcpyAsync(cell.get(), cell_h, sizeof cell_h, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_materials_check, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 1024)), dim3(256), 0, c->stream, (const frr_material *)dev_mats, (uint32_t)n, cell.get());
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(cell_h, cell.get(), sizeof cell_h, hipMemcpyDeviceToHost, c->stream);
+        { const int rc = hip_rc(c, e == hipSuccess ? hipStreamSynchronize(c->stream) : e); if (rc != FRR_OK) return rc; }
+        if (cell_h[0] != 0xFFFFFFFFu) return bad_material(c, cell_h[0]);
+    }
+    Materials t; t.dev = (const frr_material *)dev_mats;
+    return materials_register(c, std::move(t), n, cell_h[1], materials_out);   // (the host wait above stands for a join of the ctx's private streams)
+}
+int frr_materials_free(frr_ctx *c, int materials)
+{
+    if (!c || !slot_ok(c->materials, materials)) return fail(c, FRR_ERR_INVALID, "bad material table id");
+    { int rc = finish(c); if (rc != FRR_OK) return rc; }   // nothing reads it any more, nothing will replay a shade over it
+    c->materials[materials] = Materials();
+    return FRR_OK;
+}
+
+// argument checks of frr_shade_items / frr_shade_items_host; *nothing: the call is valid and writes nothing
+static int shade_items_check(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t in_entries, int K, int materials, bool *nothing)
+{
+    if (!c) return FRR_ERR_INVALID;
+    int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
+    if (rc == FRR_OK) {   // (the texture of a lit shader is the materials' business: below)
+        const UserShader *us = ps_id >= FRR_SHADER_USER_BASE ? user_shader(ps_id) : nullptr;
+        rc = rule_rc(c, pixel_shader_rule(K_OF_BUFFER, ps_id, K, us ? us->K : USER_K_UNKNOWN, true));
+    }
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_VARYINGS_IN, buf, in_entries, K, x1, y0, y1));
+    if (rc != FRR_OK) return rc;
+    if (!slot_ok(c->materials, materials)) return fail(c, FRR_ERR_INVALID, "bad material table id");
+    const FrameState &f = c->fs;
+    if (f.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_shade_items before any geometry pass");
+    if ((rc = need_unfiltered_list(c, "frr_shade_items")) != FRR_OK) return rc;
+    const Materials &M = c->materials[materials];
+    uint32_t filled = 0;
+    for (int s = 0; s < FRR_MAX_TEXTURES; ++s) if (c->tex[s].dev) filled |= 1u << s;
+    int which = -1;
+    const Rule r = materials_rule(MATERIALS_SHADE, M.dev, M.n, f.geom.nitems, ps_id == FRR_PS_PHONG || ps_id == FRR_PS_BLINN, M.slots, filled, &which);
+    if (r.code != FRR_OK) return fail(c, r.code, which >= 0 ? std::string(r.msg) + ": slot " + std::to_string(which) : std::string(r.msg));
+    // frr_clear since the pass (the id target holds nothing of it, its tables are gone), a pass without inputs, no items
+    *nothing = f.draws == 0 || f.geom.read.ntris == 0 || f.geom.nitems == 0;
+    return FRR_OK;
+}
+static Cmd shade_items_cmd(const frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *dev_in, uint64_t in_entries, int K, int materials)
+{
+    Cmd cmd = new_cmd(c, Cmd::SHADE_ITEMS, x0, x1, y0, y1);
+    cmd.ps = ps_id; cmd.shade_in = dev_in; cmd.shade_entries = in_entries; cmd.shade_K = K;
+    cmd.mats = c->materials[materials].dev;
+    return cmd;
+}
+
+int frr_shade_items(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *dev_in_f32, uint64_t in_entries, int K, int materials)
+{
+    bool nothing = false;
+    const int rc = shade_items_check(c, ps_id, x0, x1, y0, y1, dev_in_f32, in_entries, K, materials, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return exec_cmd(c, shade_items_cmd(c, ps_id, x0, x1, y0, y1, (const float *)dev_in_f32, in_entries, K, materials));
+}
+
+int frr_shade_items_host(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *host_in, uint64_t in_entries, int K, int materials)
+{
+    bool nothing = false;
+    int rc = shade_items_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, materials, &nothing);
+    if (rc != FRR_OK || nothing) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // (the device copy and its lifetime: as in frr_shade_varyings_host)
+    const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
+    DevBuf<float> tmp;
+    if (K > 0) {
+        if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
+        HIP_TRY(c, hipMemcpy(tmp, host_in, (size_t)entries * (size_t)K * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const float *dev = tmp;
+    if (K > 0) c->shade_tmp.push_back(std::move(tmp));
+    rc = exec_cmd(c, shade_items_cmd(c, ps_id, x0, x1, y0, y1, dev, entries, K, materials));
+    bool logged = false;
+    for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == Cmd::SHADE_ITEMS && c->log[k].shade_in == dev;
+    if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
+    return rc;
+}
+
+int64_t frr_host_entry_items(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                             const uint32_t *bounds, uint64_t nitems, uint32_t *item_out)
+{
+    if (!ids || !item_out || !bounds || x0 < 0 || x1 <= x0 || y1 <= y0 || nitems >= 0xFFFFFFFFull) return -1;
+    if ((uint64_t)((int64_t)y1 - y0 - 1) * (uint64_t)x1 + (uint64_t)((int64_t)x1 - x0) > id_entries) return -1;   // the last entry the window reads
+    for (uint64_t k = 0; k < nitems; ++k) if (bounds[k] > bounds[k + 1]) return -1;
+    if (nitems == 0) {
+        for (int64_t ry = 0; ry < (int64_t)y1 - y0; ++ry) for (int64_t cx = 0; cx < (int64_t)x1 - x0; ++cx) item_out[(uint64_t)ry * (uint64_t)x1 + (uint64_t)cx] = VIS_NONE;
+        return 0;
+    }
+    return (int64_t)entry_items_host(ids, x0, x1, y0, y1, bounds, (uint32_t)nitems, item_out);
 }
 
 int frr_get_stats(frr_ctx *c, frr_stats *out)

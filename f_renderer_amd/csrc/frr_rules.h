@@ -139,4 +139,37 @@ inline Rule keep_rule(const void *keep, uint64_t keep_entries, uint64_t nitems)
     return RULE_OK;
 }
 
+// ---- the materials rule ------------------------------------------------------------------------------------------------
+// A table of frr_material (frr_materials_upload / frr_materials_bind_device) and its use by frr_shade_items*.
+// material_ok    one entry: texture_slot in 0 .. FRR_MAX_TEXTURES-1 and reserved == 0 -- the one test the host (upload) and
+//                the device (k_materials_check, at bind) share.  NaN and infinite values are not refused.
+// MATERIALS_UPLOAD / MATERIALS_BIND   the table's pointer: NULL only for n == 0; a device-bound table is read with
+//                16-byte loads, so a pointer that is not 16-byte aligned never passes -- a host array may lie anywhere.
+// MATERIALS_SHADE  the table against the pass at the call: at least one entry per item of the latest geometry pass (more
+//                are fine, the rest is ignored; `n` entries, `nitems` items), and -- lit: FRR_PS_PHONG / FRR_PS_BLINN, which
+//                sample the material's slot -- every slot the table names (`slots`, bit s: some entry has texture_slot s)
+//                holds a texture (`filled`, bit s: slot s does).  A user pixel shader samples an empty slot as zero
+//                (the kernel gives such a material a 1 x 1 texture of zeros: frr_shade.h, material_apply).
+// *which: the first slot a lit shader would miss (frr_api.hip names it in frr_last_error); untouched otherwise.
+FRR_RULE_HD inline bool material_ok(const frr_material &m) { return m.texture_slot >= 0 && m.texture_slot < FRR_MAX_TEXTURES && m.reserved == 0; }
+
+enum MaterialsUse { MATERIALS_UPLOAD, MATERIALS_BIND, MATERIALS_SHADE };
+
+inline Rule materials_rule(MaterialsUse use, const void *mats, uint64_t n, uint64_t nitems = 0, bool lit = false, uint32_t slots = 0, uint32_t filled = 0,
+                           int *which = nullptr)
+{
+    if (use == MATERIALS_SHADE) {
+        if (n < nitems) return {FRR_ERR_INVALID, "the material table has fewer entries than the latest geometry pass has items"};
+        const uint32_t missing = lit ? slots & ~filled : 0u;
+        if (missing) {
+            if (which) { int s = 0; while (!((missing >> s) & 1u)) ++s; *which = s; }
+            return {FRR_ERR_INVALID, "a material names a texture slot that holds no texture"};
+        }
+        return RULE_OK;
+    }
+    if (!mats && n > 0) return {FRR_ERR_INVALID, "material table is NULL"};
+    if (use == MATERIALS_BIND && ((uintptr_t)mats & 15u)) return {FRR_ERR_INVALID, "material table pointer must be 16-byte aligned"};
+    return RULE_OK;
+}
+
 } // namespace frr

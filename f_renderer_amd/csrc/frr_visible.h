@@ -17,9 +17,14 @@
 //                    boundaries of a pass of at most VIS_LDS_BINS items are searched in an LDS copy
 // The span logic (vis_*) also compiles for the host with no HIP at all: frr_host_visible_counts and tests/visible_host.cpp
 // run visible_counts_host, which walks the spans as the kernel does, lane by lane.
+// The search functions (vis_item_search .. vis_item_unit, vis_wave_min / vis_wave_max) are also what frr_shade_items finds a
+// pixel's item with (frr_shade.h: k_shade_items), so this file is part of the text embedded for user shaders: under hiprtc
+// only those functions remain, the kernels and the host walks of this command are left out.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
-#ifdef __HIPCC__
+#endif
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 #include "frr_kernels.h"
 #define FRR_VIS_HD FRR_HD
 #else
@@ -70,6 +75,7 @@ FRR_VIS_HD uint32_t vis_run_len(unsigned long long heads, int lane)
     return above ? (uint32_t)__builtin_ctzll(above) + 1u : (uint32_t)(VIS_SPAN - lane);
 }
 
+#ifndef __HIPCC_RTC__
 // The counts of a window of an id array on the host, span by span and lane by lane as k_visible takes them.  bounds: the
 // nunits + 1 item boundaries, or null: per triangle, the units are the ids 0 .. nunits.  Every entry of out is written.
 // Returns the number of adds (run heads that count for a unit).  The caller has checked the window against the array.
@@ -106,8 +112,47 @@ inline uint64_t visible_counts_host(const uint32_t *ids, int32_t x0, int32_t x1,
     return adds;
 }
 
-#ifdef __HIPCC__
+// The item of every entry of a window of an id array on the host, as k_shade_items (frr_shade.h) finds it: span by span the
+// smallest and largest in-pass id, the narrowed range, each lane's search -- and then the rounds of the span, one per
+// DISTINCT item its lanes hold, in the order the kernel takes them (the first remaining lane's item).  item_out[i] is written
+// for every entry i of the window: the item, or VIS_NONE (nothing drawn, another pass's id).  Returns the number of rounds.
+// bounds: the nitems + 1 boundaries, nitems >= 1.  The caller has checked the window against the arrays.
+inline uint64_t entry_items_host(const uint32_t *ids, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                                 const uint32_t *bounds, uint32_t nitems, uint32_t *item_out)
+{
+    const uint32_t b0 = bounds[0], bn = bounds[nitems];
+    const int64_t ww = (int64_t)x1 - x0, wh = (int64_t)y1 - y0;
+    uint64_t rounds = 0;
+    for (int64_t ry = 0; ry < wh; ++ry) {
+        for (int64_t c0 = 0; c0 < ww; c0 += VIS_SPAN) {
+            uint32_t id[VIS_SPAN], item[VIS_SPAN];
+            uint32_t mn = VIS_NONE, mx = 0u;
+            for (int l = 0; l < VIS_SPAN; ++l) {
+                id[l] = c0 + l < ww ? ids[(uint64_t)ry * (uint64_t)x1 + (uint64_t)(c0 + l)] : VIS_NONE;
+                if (vis_in_pass(id[l], b0, bn)) { mn = id[l] < mn ? id[l] : mn; mx = id[l] > mx ? id[l] : mx; }
+            }
+            VisRange r = {0u, 0u};
+            if (mn != VIS_NONE) r = vis_span_range(bounds, nitems, mn, mx);
+            for (int l = 0; l < VIS_SPAN; ++l) {
+                item[l] = mn == VIS_NONE ? VIS_NONE : vis_item_unit(bounds, r, id[l], vis_in_pass(id[l], b0, bn), nitems);
+                if (c0 + l < ww) item_out[(uint64_t)ry * (uint64_t)x1 + (uint64_t)(c0 + l)] = item[l];
+            }
+            unsigned long long left = 0ull;   // the lanes that still wait for their round
+            for (int l = 0; l < VIS_SPAN; ++l) if (item[l] != VIS_NONE) left |= 1ull << l;
+            while (left) {
+                const uint32_t k = item[__builtin_ctzll(left)];   // (readfirstlane of the remaining lanes)
+                for (int l = 0; l < VIS_SPAN; ++l) if (item[l] == k) left &= ~(1ull << l);
+                ++rounds;
+            }
+        }
+    }
+    return rounds;
+}
+#endif // !__HIPCC_RTC__
 
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+
+#ifndef __HIPCC_RTC__
 struct VisibleArgs {
     int32_t x0, x1, y0, y1;           // the window (depth index (cy - y0) * x1 + (cx - x0), renderer.rs:362; x0 >= 0)
     int32_t unit;                     // frr_visible_unit
@@ -142,6 +187,7 @@ __global__ __launch_bounds__(VIS_WG) void k_visible_prep(VisibleArgs a)
         if (i < nb) a.bounds[i] = tri_base + item_first_emission(a.item_first, a.stride, a.nitems, a.ntris, a.tinfo, a.block_prefix, n_emit, (uint32_t)i);
     }
 }
+#endif // !__HIPCC_RTC__
 
 __device__ __forceinline__ uint32_t vis_wave_min(uint32_t v)
 {
@@ -156,6 +202,7 @@ __device__ __forceinline__ uint32_t vis_wave_max(uint32_t v)
     return v;
 }
 
+#ifndef __HIPCC_RTC__
 // ITEM: per item (else per triangle).  LDS: the units fit VIS_LDS_BINS (the host decides: it is the same for all spans).
 // BLDS (ITEM only): the pass has at most VIS_LDS_BINS items, and the workgroup searches a copy of the boundaries in LDS -- a
 // search is a chain of dependent loads, a dozen for 4,096 items, and from global memory that chain is what a span costs.
@@ -218,6 +265,7 @@ template <bool ITEM, bool LDS, bool BLDS> __global__ __launch_bounds__(VIS_WG) v
         }
     }
 }
+#endif // !__HIPCC_RTC__
 
 #endif // __HIPCC__
 

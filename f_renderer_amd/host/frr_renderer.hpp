@@ -305,6 +305,7 @@ inline Model::Indexed Model::indexed_inputs() const
 struct Mesh { int id = -1; uint64_t ntris = 0; int vs = 0; };
 struct Lines { int id = -1; uint64_t nlines = 0; };   // a list of draw_line calls on the device
 struct Instances { int id = -1; uint64_t ninst = 0; };   // a table of model matrices on the device: one per instance of an instanced pass
+struct Materials { int id = -1; uint64_t n = 0; };        // a table of frr_material on the device: the pixel uniforms of each item of a pass (shade_items)
 struct DrawList { int id = -1; uint64_t nitems = 0; };   // (mesh, model matrix) items on the device: one list pass draws them all
 struct LineSegment { uint32_t x1, y1, x2, y2; };
 static_assert(sizeof(LineSegment) == 16, "LineSegment must be 4 packed u32");
@@ -382,6 +383,21 @@ public:
         return t;
     }
     void free_instances(Instances &t) { if (t.id >= 0) { check(frr_instances_free(ctx_, t.id)); t.id = -1; } }
+    // The pixel uniforms that change from object to object (phong.rs:34-47: ps_uniform.place per object), one frr_material per
+    // item of a pass: texture slot, ambient and specular strength, flat colour, u.user[0 .. FRR_MATERIAL_USER).
+    Materials upload_materials(const std::vector<frr_material> &mats)
+    {
+        Materials t; t.n = mats.size();
+        check(frr_materials_upload(ctx_, mats.empty() ? nullptr : mats.data(), t.n, &t.id));
+        return t;
+    }
+    Materials bind_materials_device(const void *dev_mats, uint64_t n)   // 16-byte aligned; checked on the device inside the call (a host wait)
+    {
+        Materials t; t.n = n;
+        check(frr_materials_bind_device(ctx_, dev_mats, n, &t.id));
+        return t;
+    }
+    void free_materials(Materials &t) { if (t.id >= 0) { check(frr_materials_free(ctx_, t.id)); t.id = -1; } }
     // The objects of a frame that do not share a mesh (phong.rs:319-359: body, face, hair), each under its own model matrix
     // (column-major like uniforms.model).  A snapshot of the meshes: freeing one of them kills the list.
     DrawList upload_draw_list(const std::vector<Mesh> &meshes, const std::vector<Mat4> &models)
@@ -585,6 +601,33 @@ public:
     void shade_varyings_host(int pixel_shader, const std::vector<float> &in, int num_varyings, uint32_t id_first = 0, uint32_t id_count = 0xFFFFFFFFu)
     {
         shade_varyings_host(pixel_shader, in, num_varyings, {0, (int32_t)width_}, {0, (int32_t)height_}, id_first, id_count);
+    }
+    // shade_varyings for all the items of the latest geometry pass at once, each under its own material: what one ranged
+    // shade_varyings per item of item_ranges() under that item's texture slot, strengths, flat colour and u.user[0 .. 8) leaves,
+    // byte for byte, in one pass over the window (include/frr.h: frr_shade_items).  Everything else in the uniforms is the call's.
+    void shade_items(int pixel_shader, const void *dev_in_f32, uint64_t entries, int num_varyings, const Materials &materials,
+                     std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        check(frr_shade_items(ctx_, pixel_shader, width_range.first, width_range.second, height_range.first, height_range.second, dev_in_f32, entries,
+                              num_varyings, materials.id));
+    }
+    void shade_items(int pixel_shader, const void *dev_in_f32, uint64_t entries, int num_varyings, const Materials &materials)
+    {
+        shade_items(pixel_shader, dev_in_f32, entries, num_varyings, materials, {0, (int32_t)width_}, {0, (int32_t)height_});
+    }
+    // the same from host memory, as shade_varyings_host takes it
+    void shade_items_host(int pixel_shader, const std::vector<float> &in, int num_varyings, const Materials &materials,
+                          std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        const int64_t rows = (int64_t)height_range.second - height_range.first;
+        const uint64_t window = rows > 0 && width_range.second > 0 ? (uint64_t)rows * (uint64_t)width_range.second : 0;
+        const uint64_t entries = num_varyings > 0 ? (uint64_t)in.size() / (uint64_t)num_varyings : window;
+        check(frr_shade_items_host(ctx_, pixel_shader, width_range.first, width_range.second, height_range.first, height_range.second,
+                                   in.empty() ? nullptr : in.data(), entries, num_varyings, materials.id));
+    }
+    void shade_items_host(int pixel_shader, const std::vector<float> &in, int num_varyings, const Materials &materials)
+    {
+        shade_items_host(pixel_shader, in, num_varyings, materials, {0, (int32_t)width_}, {0, (int32_t)height_});
     }
     frr_stats stats() { frr_stats s; check(frr_get_stats(ctx_, &s)); return s; }
     frr_ctx *raw() { return ctx_; }

@@ -23,6 +23,10 @@ from ._native import (CULL_NEG, CULL_NONE, CULL_POS, FrrError, PS_BLINN, PS_COLO
 
 SETUP_DTYPE = np.dtype([("spf", "<f4", (2,)), ("spi", "<i4", (2,)), ("rhw", "<f4"), ("ctx", "<f4", (N.MAX_VARYINGS,))])
 assert SETUP_DTYPE.itemsize == C.sizeof(N.SetupVertex)
+# frr_material as a NumPy record: a table is an array of these (Renderer.upload_materials)
+MATERIAL_DTYPE = np.dtype([("texture_slot", "<i4"), ("ambient_strength", "<f4"), ("specular_strength", "<f4"), ("reserved", "<i4"),
+                           ("flat_color", "<f4", (4,)), ("user", "<f4", (N.MATERIAL_USER,))])
+assert MATERIAL_DTYPE.itemsize == C.sizeof(N.Material) == 64
 
 _f32p = C.POINTER(C.c_float)
 
@@ -181,6 +185,19 @@ class Instances:
             self.id = None
 
 
+class Materials:
+    """A table of frr_material on the device (Renderer.upload_materials / bind_materials_device): the pixel uniforms of each
+    item of a pass, for Renderer.shade_items."""
+
+    def __init__(self, renderer, mat_id, n, keepalive=None):
+        self.renderer, self.id, self.n, self._keep = renderer, mat_id, n, keepalive
+
+    def free(self):
+        if self.id is not None:
+            self.renderer._check(N.lib().frr_materials_free(self.renderer._ctx, self.id))
+            self.id = None
+
+
 class DrawList:
     """A list of (mesh, model matrix) items on the device (Renderer.upload_draw_list): a snapshot of the meshes it names."""
 
@@ -218,6 +235,23 @@ def host_visible_counts(ids, width_range, height_range, bounds=None, units=None,
     if adds < 0:
         raise FrrError(N.FRR_ERR_INVALID, "host_visible_counts: bad window, array or boundaries")
     return out, int(adds)
+
+
+def host_entry_items(ids, width_range, height_range, bounds):
+    """The item of every entry of a host id array as frr_shade_items' kernel finds it (frr_host_entry_items): `ids` uint32,
+    entry (cy - y0) * x1 + (cx - x0); bounds: the nitems + 1 item boundaries.  Returns (items uint32, shaped like ids.reshape(-1):
+    the item, 0xFFFFFFFF where the id is not one of the pass's or the entry lies outside the window; rounds: the number of
+    (64-entry span, distinct item) pairs, what the kernel's loop over a span's items runs)."""
+    a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    b = np.ascontiguousarray(bounds, np.uint32).reshape(-1)
+    if b.size < 1:
+        raise FrrError(N.FRR_ERR_INVALID, "host_entry_items: nitems + 1 boundaries")
+    out = np.full(a.size, 0xFFFFFFFF, np.uint32)
+    rounds = N.lib().frr_host_entry_items(a.ctypes.data, a.size, int(width_range[0]), int(width_range[1]), int(height_range[0]), int(height_range[1]),
+                                          b.ctypes.data, b.size - 1, out.ctypes.data if out.size else None)
+    if rounds < 0:
+        raise FrrError(N.FRR_ERR_INVALID, "host_entry_items: bad window, array or boundaries")
+    return out, int(rounds)
 
 
 def host_instance_mvp(proj, view, model):
@@ -372,6 +406,35 @@ class Renderer:
         iid = C.c_int()
         self._check(self._lib.frr_instances_bind_device(self._ctx, C.c_void_p(ptr), ninst, C.byref(iid)))
         return Instances(self, iid.value, ninst, keepalive)
+
+    def upload_materials(self, materials):
+        """One frr_material per item of a pass -> device (frr_materials_upload).  materials: an array of MATERIAL_DTYPE, or a
+        sequence of dicts with any of texture_slot, ambient_strength, specular_strength, flat_color, user (up to
+        MATERIAL_USER floats), reserved; what a dict leaves out is 0 (flat_color: 1, 1, 1, 1)."""
+        if isinstance(materials, np.ndarray) and materials.dtype == MATERIAL_DTYPE:
+            a = np.ascontiguousarray(materials).reshape(-1)
+        else:
+            a = np.zeros(len(materials), MATERIAL_DTYPE)
+            a["flat_color"] = 1.0
+            for i, m in enumerate(materials):
+                for k, v in m.items():
+                    if k == "user":
+                        v = np.asarray(v, np.float32).reshape(-1)
+                        if v.size > N.MATERIAL_USER:
+                            raise FrrError(N.FRR_ERR_INVALID, "a material takes at most MATERIAL_USER user floats")
+                        a["user"][i, :v.size] = v
+                    else:
+                        a[k][i] = v
+        mid = C.c_int()
+        self._check(self._lib.frr_materials_upload(self._ctx, a.ctypes.data if a.size else None, a.size, C.byref(mid)))
+        return Materials(self, mid.value, int(a.size))
+
+    def bind_materials_device(self, ptr, n, keepalive=None):
+        """Same, for a table already in HBM (n records of MATERIAL_DTYPE, 16-byte aligned, e.g. a torch tensor's data_ptr());
+        checked on the device inside this call (a host wait).  After an in-place rewrite: frame_fence, rewrite, bind again."""
+        mid = C.c_int()
+        self._check(self._lib.frr_materials_bind_device(self._ctx, C.c_void_p(ptr), int(n), C.byref(mid)))
+        return Materials(self, mid.value, int(n), keepalive)
 
     def upload_lines(self, xyxy, rgba):
         """A list of FrameBuffer::draw_line calls (renderer.rs:540-588) -> device.  xyxy: uint32 [n,4] = x1, y1, x2, y2;
@@ -601,6 +664,24 @@ class Renderer:
             raise FrrError(N.FRR_ERR_INVALID, "geometry_num_varyings before geometry_processing")
         return k
 
+    def _varyings_in(self, who, buf, entries, K, wr, hr):
+        """The buffer argument of shade_varyings / shade_items: (host array?, pointer, entries, K, what keeps the pointer alive).
+        A NumPy array goes to the host entry point; entries defaults to (y1 - y0) * x1 (or the array's rows), K to the array's
+        columns, else to geometry_num_varyings()."""
+        window = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
+        if isinstance(buf, np.ndarray):
+            a = np.ascontiguousarray(buf, np.float32)
+            if K is None:
+                K = a.shape[-1] if a.ndim >= 2 else self.geometry_num_varyings()
+            if entries is None:
+                entries = a.size // K if K else window
+            if a.size < min(int(entries) * int(K), window * int(K)):
+                raise FrrError(N.FRR_ERR_INVALID, who + ": the array is smaller than entries * K")
+            return True, (a.ctypes.data if a.size else 0), entries, K, a
+        if K is None:
+            K = self.geometry_num_varyings()
+        return False, int(buf or 0), window if entries is None else entries, K, None
+
     def shade_varyings(self, pixel_shader, buf, entries=None, K=None, width_range=None, height_range=None, ids=(0, 0xFFFFFFFF)):
         """pixel_shader over a buffer of varyings into the colour target (frr_shade_varyings): every pixel of the window whose
         triangle id lies in ids = (first, count) -- id != 0xFFFFFFFF and id - first < count -- becomes
@@ -611,25 +692,22 @@ class Renderer:
         array's rows), K to the array's columns, else to geometry_num_varyings().  The uniforms are those of the call."""
         wr = width_range or (0, self.width)
         hr = height_range or (0, self.height)
-        host = isinstance(buf, np.ndarray)
-        if host:
-            a = np.ascontiguousarray(buf, np.float32)
-            if K is None:
-                K = a.shape[-1] if a.ndim >= 2 else self.geometry_num_varyings()
-            if entries is None:
-                entries = a.size // K if K else max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
-            need = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0) * int(K)
-            if a.size < min(int(entries) * int(K), need):
-                raise FrrError(N.FRR_ERR_INVALID, "shade_varyings: the array is smaller than entries * K")
-            ptr, fn = (a.ctypes.data if a.size else 0), self._lib.frr_shade_varyings_host
-        else:
-            if K is None:
-                K = self.geometry_num_varyings()
-            if entries is None:
-                entries = max(int(hr[1]) - int(hr[0]), 0) * max(int(wr[1]), 0)
-            ptr, fn = int(buf or 0), self._lib.frr_shade_varyings
+        host, ptr, entries, K, _keep = self._varyings_in("shade_varyings", buf, entries, K, wr, hr)
+        fn = self._lib.frr_shade_varyings_host if host else self._lib.frr_shade_varyings
         self._check(fn(self._ctx, int(pixel_shader), int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), C.c_void_p(ptr), int(entries), int(K),
                        int(ids[0]) & 0xFFFFFFFF, int(ids[1]) & 0xFFFFFFFF))
+
+    def shade_items(self, pixel_shader, buf, materials, entries=None, K=None, width_range=None, height_range=None):
+        """shade_varyings for all items of the latest geometry pass at once, each under its own material (frr_shade_items):
+        what `for k: set the uniforms' texture_slot / strengths / flat_color / user[:8] from materials[k];
+        shade_varyings(..., ids=(first[k], count[k]))` over item_ranges() leaves, byte for byte, in one pass over the window.
+        `buf`, entries and K as for shade_varyings; everything else in the uniforms is the call's."""
+        wr = width_range or (0, self.width)
+        hr = height_range or (0, self.height)
+        host, ptr, entries, K, _keep = self._varyings_in("shade_items", buf, entries, K, wr, hr)
+        fn = self._lib.frr_shade_items_host if host else self._lib.frr_shade_items
+        self._check(fn(self._ctx, int(pixel_shader), int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]), C.c_void_p(ptr), int(entries), int(K),
+                       -1 if materials.id is None else int(materials.id)))
 
     def visible_pixels(self, unit="item", out_ptr=None, entries=None, width_range=None, height_range=None):
         """How many entries of the window each unit owns in the triangle-id target (frr_visible_pixels): unit="item", the

@@ -577,6 +577,68 @@ int frr_shade_varyings_host(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int
                             const float *host_in, uint64_t in_entries, int K,
                             uint32_t id_first, uint32_t id_count);
 
+/* ---- per-item materials: one shade for all the items of a pass --------------------------------- */
+/* The reference gives every object its own ps_uniform.place, and so its own texture, inside one frame (phong.rs:34-47,
+ * 361-370).  A material is that for a list: the pixel uniforms that change from item to item, 64 bytes each, in a table on
+ * the device with one entry per item of a geometry pass.
+ * The items are those of the LATEST geometry pass, exactly the ones frr_geometry_item_ranges reports (id_first[k],
+ * id_count[k], nitems): the items of a list pass, the instances of an instanced pass, one item for a plain pass.
+ * frr_shade_items(ps_id, window, buffer, in_entries, K, materials) is BY DEFINITION this loop, in this order:
+ *   for k in 0 .. nitems:
+ *       u = the uniforms of the call, with uniforms.texture_slot (hence the texture frr::sample_2d and FRR_PS_PHONG /
+ *           FRR_PS_BLINN read), ambient_strength, specular_strength, flat_color and u.user[0 .. FRR_MATERIAL_USER) taken
+ *           from materials[k]
+ *       frr_shade_varyings(ps_id, window, buffer, in_entries, K, id_first[k], id_count[k])   under u
+ * so that:
+ * - the colour target is, byte for byte, what that loop of calls leaves: the same pixel shader and quantisation under the
+ *   same uniform values;
+ * - pixels whose id is not one of the latest pass's (nothing drawn, earlier passes of the frame) are untouched, and so are
+ *   depth, triangle ids and every field of frr_stats;
+ * - everything else in the uniforms is the call's: view_pos, light_pos, light_color, u.user[FRR_MATERIAL_USER ..), every
+ *   texture slot (frr::sample_2d_slot), and u.model / u.mvp, which a pixel shader sees as under frr_shade_varyings;
+ * - it is ordered, logged and replayed as frr_shade_varyings is -- a command that writes a target on the current frame's
+ *   stream, behind a pending frr_clear and the streams of pending frr_frame_wait calls, with no host wait, on a partitioned
+ *   ctx writing only the tile rows this rank owns -- AND as frr_visible_pixels is against the pass: behind the pass's
+ *   geometry, whose tables it reads on the device.  A replay shades with the uniforms of the call and reads the table again;
+ * - THE BUFFER, AND A DEVICE-BOUND TABLE, MUST STAY ALLOCATED AND UNCHANGED until the next synchronisation point or
+ *   frr_clear.
+ * An item's material covers exactly the item's ids.  The reference's loop switches its uniform at `i <= body_offset`
+ * (phong.rs:364-369), one triangle late; this command does NOT reproduce that off-by-one -- the ranged frr_shade_varyings
+ * calls of INTEGRATION.md section 1d stay the way to.
+ * Tables.  frr_materials_upload copies n materials (the host checks them); frr_materials_bind_device borrows device memory,
+ * 16-byte aligned, until frr_materials_free, and checks it with one small kernel on the ctx's stream and a host wait inside
+ * the call, as frr_lines_bind_device does (after an in-place rewrite: frr_frame_fence, rewrite, bind again).  A material with
+ * a texture_slot outside 0 .. FRR_MAX_TEXTURES-1 or with reserved != 0 is refused with FRR_ERR_INVALID, and frr_last_error
+ * names the first such entry; NaN and infinite values are the caller's business.  (The kernel clamps the slot anyway: a
+ * guard for the machine, not a defined result.)  n == 0 is a valid table.  frr_materials_free finishes what is in flight
+ * first, as frr_instances_free does.
+ * Errors of frr_shade_items, in this order.  The window, shader and buffer rules of frr_shade_varyings (the texture of a
+ * lit shader is asked of the table, below).  FRR_ERR_INVALID: an unknown or freed table id; a call before any geometry
+ * pass, or after a frr_draw* that filtered the setup list on a partitioned ctx (where frr_visible_pixels fails); a table
+ * with fewer entries than the pass has items (more are fine: the rest is ignored); with FRR_PS_PHONG / FRR_PS_BLINN, a slot
+ * some entry of the table names that holds no texture at the call (frr_last_error names the slot) -- for a user pixel
+ * shader an empty slot samples as zero: frr::sample_2d_slot as ever, and frr::sample_2d(u, ...) -- the material's own slot --
+ * because a material that names an empty slot is given a 1 x 1 texture of zeros (zero at every finite coordinate; a NaN or
+ * infinite coordinate gives NaN there as on any texture).  Under frr_shade_varyings frr::sample_2d of an empty
+ * uniforms.texture_slot stays undefined, as before.  After a frr_clear since the pass, for a pass without inputs and for nitems == 0:
+ * FRR_OK, nothing written.
+ * frr_shade_items_host: the buffer from host memory, as frr_shade_varyings_host takes it. */
+#define FRR_MATERIAL_USER 8
+typedef struct frr_material {          /* 64 bytes: four 16-byte loads */
+    int32_t texture_slot;              /* PSUniform.place, 0 .. FRR_MAX_TEXTURES-1 */
+    float   ambient_strength, specular_strength;
+    int32_t reserved;                  /* 0 */
+    float   flat_color[4];
+    float   user[FRR_MATERIAL_USER];   /* replaces u.user[0 .. FRR_MATERIAL_USER) */
+} frr_material;
+int frr_materials_upload(frr_ctx *ctx, const frr_material *mats, uint64_t n, int *materials_out);
+int frr_materials_bind_device(frr_ctx *ctx, const void *dev_mats, uint64_t n, int *materials_out);
+int frr_materials_free(frr_ctx *ctx, int materials);
+int frr_shade_items(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                    const void *dev_in_f32, uint64_t in_entries, int K, int materials);
+int frr_shade_items_host(frr_ctx *ctx, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                         const float *host_in, uint64_t in_entries, int K, int materials);
+
 /* ---- visible pixel counts --------------------------------------------------------------------- */
 /* Which objects of a pass ended up on screen, and with how many pixels, without reading the frame back: the triangle-id
  * target of a window as counts, on the device.  (The reference has no such query; every renderer with a batched draw has:
@@ -745,6 +807,14 @@ int64_t frr_host_list_item(const uint32_t *first, const uint32_t *ntris, uint64_
  * number of adds -- run heads that counted for a unit --, or -1 for a bad argument. */
 int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                                 const uint32_t *bounds, uint64_t nunits, uint32_t *out, uint64_t out_entries);
+/* host build of the per-entry item lookup of frr_shade_items (cf. frr_host_visible_counts): over the same kind of id array,
+ * window and nitems + 1 boundaries (never NULL), span by span and lane by lane as the kernel takes them -- the span's
+ * smallest and largest in-pass id, the narrowed range, each lane's search.  item_out has id_entries entries, addressed like
+ * ids: every entry of the window receives its item, or 0xFFFFFFFF where the id is not one of the pass's; entries outside
+ * the window are not written.  Returns the number of (span, distinct item) rounds -- a span shades once per distinct
+ * item its lanes hold --, or -1 for a bad argument.  nitems == 0: every entry of the window is 0xFFFFFFFF, 0 rounds. */
+int64_t frr_host_entry_items(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                             const uint32_t *bounds, uint64_t nitems, uint32_t *item_out);
 /* host build of the device's facing determinant (frr_set_cull; cf. frr_host_atan2f): d of the three clip positions
  * clip[0..3], clip[4..7], clip[8..11] (x, y, z, w each) */
 float frr_host_cull_det(const float clip[12]);

@@ -57,6 +57,18 @@ pub mod ffi {
         pub replays: u32,
     }
 
+    /// the pixel uniforms of one item of a pass (frr_shade_items): 64 bytes
+    #[repr(C)]
+    #[derive(Clone, Copy, Default, Debug)]
+    pub struct frr_material {
+        pub texture_slot: i32,
+        pub ambient_strength: f32,
+        pub specular_strength: f32,
+        pub reserved: i32,
+        pub flat_color: [f32; 4],
+        pub user: [f32; 8],
+    }
+
     #[repr(C)]
     #[derive(Clone, Copy, Default, Debug)]
     pub struct frr_xfer {
@@ -113,6 +125,13 @@ pub mod ffi {
         pub fn frr_visible_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
         pub fn frr_visible_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
         pub fn frr_host_list_item(first: *const u32, ntris: *const u32, nitems: u64, t: u32) -> i64;
+        // per-item materials: one shade of all the items of the latest geometry pass, each under its own frr_material
+        pub fn frr_materials_upload(ctx: *mut frr_ctx, mats: *const frr_material, n: u64, materials_out: *mut c_int) -> c_int;
+        pub fn frr_materials_bind_device(ctx: *mut frr_ctx, dev_mats: *const c_void, n: u64, materials_out: *mut c_int) -> c_int;
+        pub fn frr_materials_free(ctx: *mut frr_ctx, materials: c_int) -> c_int;
+        pub fn frr_shade_items(ctx: *mut frr_ctx, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_in_f32: *const c_void, in_entries: u64, k: c_int, materials: c_int) -> c_int;
+        pub fn frr_shade_items_host(ctx: *mut frr_ctx, ps_id: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_in: *const f32, in_entries: u64, k: c_int, materials: c_int) -> c_int;
+        pub fn frr_host_entry_items(ids: *const u32, id_entries: u64, x0: i32, x1: i32, y0: i32, y1: i32, bounds: *const u32, nitems: u64, item_out: *mut u32) -> i64;
         // face culling of the geometry passes issued from now on (0 none, 1 drop d < 0, 2 drop d > 0): set beside the uniforms
         pub fn frr_set_cull(ctx: *mut frr_ctx, mode: c_int) -> c_int;
         pub fn frr_host_cull_det(clip: *const f32) -> f32;
