@@ -965,7 +965,6 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     if (nmat && nt > 0 && (rc = ensure(c, S.inst_tab, (size_t)nmat * 32)) != FRR_OK) return rc;
     const bool keep_tab = cmd.pred && nmat && nt > 0;
     if (keep_tab && (rc = ensure(c, S.keep_tab, (size_t)nmat)) != FRR_OK) return rc;
-    if ((rc = scan_now(c)) != FRR_OK) return rc;   // the previous pass's n_emit feeds this pass's tri_base
     if (on_g && !c->gstream) {
         // created on first use: a process maps its HIP streams onto a handful of hardware queues, and two streams that
         // share one run nothing beside each other -- a ctx that never needs this stream does not take a queue for it
@@ -1542,6 +1541,11 @@ int finish(frr_ctx *c);
 // run a command and remember it (finish() replays the commands from a failed one onwards)
 int exec_cmd(frr_ctx *c, Cmd cmd)
 {
+    // The previous pass's n_emit feeds a geometry pass's tri_base.  If no binning launch has scanned that pass's block sums
+    // (it was never rastered), they are scanned here: before exec_geometry sizes the tables -- where both passes use one
+    // set, a pass with more blocks reallocates block_sums, and writes its own sums there -- and before the snapshot a replay
+    // of this command starts from, so that a replay does not scan again what this pass has overwritten by then.
+    if (cmd.kind == Cmd::GEOM) { const int rs = scan_now(c); if (rs != FRR_OK) return rs; }
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;

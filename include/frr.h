@@ -137,7 +137,10 @@ typedef struct frr_stats {
     uint64_t frag_nan;     /* fragments whose rhw interpolated to NaN; they always pass the depth test and so does the next
                               fragment on their pixel (renderer.rs:363-366): reproduced exactly, by a second pass over the
                               tiles that saw one (the NaN bit pattern itself is the device's) */
-    uint32_t draws;
+    uint32_t draws;        /* On a partitioned ctx (frr_set_partition, world > 1) tris_in, tris_setup and draws are those of the
+                              unpartitioned frame on every rank (geometry is replicated), while frag_covered and frag_nan are
+                              counted by the tile kernels of the tiles the rank owns: the ranks' sums are the unpartitioned
+                              figures */
     uint32_t replays;      /* how often the library had to grow a work list and replay commands of this frame (see
                               FRR_ERR_CAPACITY): a diagnostic, the results are those of a frame that never failed */
 } frr_stats;
@@ -168,7 +171,11 @@ int frr_set_partition(frr_ctx *ctx, int rank, int world);
 /* Which tile rows a rank owns: 0 (default) = interleaved, ty % world == rank -- balances scenes whose
  * load varies down the screen; 1 = blocked, rank owns a contiguous run of tile_rows / world rows, the first
  * tile_rows % world ranks one more (34 rows over 8 ranks: 5,5,4,4,4,4,4,4; frr_owned_rows tells) -- its part of a
- * row-major image is then ONE contiguous slab, so the final-image gather needs no staging copies (bench.py uses this). */
+ * row-major image is then ONE contiguous slab, so the final-image gather needs no staging copies (bench.py uses this).
+ * tile_rows is counted per command: frr_raster / frr_draw*, frr_resolve_varyings, frr_shade_varyings, frr_shade_items and
+ * frr_visible_pixels count the tile rows of their WINDOW (y1 - y0 rows), frr_draw_lines and frr_draw_wireframe those of the
+ * ctx (its height).  Interleaved the count does not enter the rule.  Blocked, the two kinds of command own the same rows only
+ * in a window with as many tile rows as the ctx (every full-height window): see frr_draw_lines. */
 int frr_set_partition_layout(frr_ctx *ctx, int blocked);
 /* The pixel rows of a raster window height_range = (y0, y1) (renderer.rs:271: the sub-window argument this whole
  * partition rests on) that this rank owns, as bands [row0, row1) of window-local rows: ONE band in the blocked
@@ -210,8 +217,10 @@ int frr_set_count_fragments(frr_ctx *ctx, int enable);
  * internally allocated ones; any may be NULL to keep the internal one (with option bound_targets_in_flight: all three
  * or none).  On a partitioned ctx
  * (frr_set_partition, world > 1) only the tile rows the rank owns are defined in caller-owned targets
- * (a clear that was performed inside a draw never touches the other ranks' rows); the ctx's own targets
- * are brought up to date in full whenever they are read back. */
+ * (a clear that was performed inside a draw never touches the other ranks' rows, one that was not -- in front of a
+ * sub-window raster or of any other command, or under option clear_eager -- clears the whole target); the ctx's own targets
+ * are brought up to date in full whenever they are read back: at frr_readback, and behind frr_target_ptrs and
+ * frr_frame_fence, every row and depth / id entry of another rank holds the frame's clear values, never a fragment. */
 int frr_bind_targets(frr_ctx *ctx, void *color_rgba8, void *depth_f32, void *tri_id_u32);
 /* The device pointers of the current frame's targets, for reads queued on the ctx's stream (which first waits for the
  * frames issued so far).  With two frames in flight the ctx's own targets are two sets: the pointers are those of the
@@ -480,7 +489,12 @@ int frr_lines_free(frr_ctx *ctx, int lines);
  * later triangle draw overwrites a line pixel wherever its fragment passes the depth test, and nowhere else -- and where
  * segments of the list meet, the later one's colour stays.  A pending frr_clear is settled first, as by a sub-window
  * raster.  On a partitioned ctx a pixel is written only if this rank owns the tile row of its linear index
- * ((index / width) / 32), so that the ranks' images stitch to the reference's like those of any draw. */
+ * ((index / width) / 32) among the tile rows of the CTX, so that the ranks' images stitch to the reference's like those of any
+ * draw -- of any draw whose window has as many tile rows as the ctx, or in the interleaved layout.  A draw takes its owner from
+ * the tile rows of its WINDOW (frr_set_partition_layout), and in the blocked layout a shorter window divides other rows: on a
+ * 96-row ctx a window of 40 rows has two tile rows, and with two ranks plane rows 32 .. 39 are the draws' on rank 1 and the
+ * lines' on rank 0, so a line over a triangle there is complete on no rank.  Use the interleaved layout, or full-height
+ * windows, where lines and draws meet. */
 int frr_draw_lines(frr_ctx *ctx, int lines);
 /* The edges (v0,v1), (v1,v2), (v2,v0) of every triangle of the last frr_geometry in one colour: segment 3t + e is edge e of
  * setup triangle t, between the spi of its emission-order vertices (what frr_readback_setup returns).  The reference has no
@@ -694,7 +708,11 @@ int frr_visible_pixels_host(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int3
  * and repaired, before frr_raster / frr_draw returns (the call then waits for the pass's binning launch, not for its tile
  * kernel; a pass that repeats a mesh registration, uniforms -- texture pointers and sizes included --, window and partition
  * already seen to fit, with no frr_texture_upload since and, for a device-bound mesh, no frr_sync since, is not waited
- * for).
+ * for).  What is not whole at a fence: commands issued behind a frr_geometry* that no frr_raster has followed yet (an open
+ * or abandoned pass).  Nothing has verified that pass, so if it found the fan space too small they have written nothing, and
+ * they are replayed at the next synchronisation point only (frr_resolve_varyings says so for itself; the same holds for
+ * frr_draw_lines, frr_draw_wireframe, frr_shade_varyings, frr_shade_items and frr_visible_pixels there).  A caller that
+ * fences such a frame calls frr_sync first.
  * `stream` has to stay alive until the second frr_clear from now when it fenced the ctx's OWN targets (that frr_clear
  * records an event on it: frr_target_ptrs). */
 int frr_frame_fence(frr_ctx *ctx, void *stream);

@@ -27,10 +27,29 @@ block; setup triangles times 32-pixel tiles under their bounding boxes) and keep
 have left behind.  A pass whose need is at least MARGIN times that bound is a rung: it must overflow, whatever rounding
 exec_geometry applies.  Two meshes are made for that, r1 and r2; each seed meets r1 in an earlier frame than r2.
 
-Left out: partitions, user shaders, x0 < 0, several rasters of one geometry pass, abandoned geometry passes, state setters
-that change the vertex shader's uniforms between a geometry* and its rasterization, resolves behind the rasterization of a
-rung mesh (the NumPy oracle's cost).  The generator issues set_cull between passes only; cull_inside_split() is the fixed
-sequence with one inside split passes."""
+The extended sequences.  generate(seed, extended=True) for seed in XSEEDS adds three things, and leaves what generate(seed)
+yields for SEEDS exactly as it was (tests/test_frame_model_cpu.py pins a digest):
+  shade_items   {ps, buf, table}: frr_shade_items by its definition -- per item k of the latest pass the `shade` above over
+                (id_first[k], id_count[k]) under the call's uniforms with MATERIALS[table][k]'s texture slot (the slot's texture
+                as of the call), strengths and flat colour.  Undefined before any geometry pass and for a buffer whose K the
+                shader refuses; nothing is written after a clear since the pass, for a pass that emitted nothing and for one
+                that is not rastered yet, whose ids are not in the target
+  a raster of a pass that is rastered already ("again"), in the frame's one window and with a shader of the same K:
+                oracle_list_loop runs again over the frame as it is, with the same ids.  frag_covered and frag_nan add up
+                again; draws, tris_in and tris_setup counted at the geometry call.  The pass's `before`, `after` and `ps` are
+                those of the LATEST raster: a resolve sees the ownership the last raster left
+  an abandoned pass ("abandoned"): a geometry* that no raster follows.  tris_in, draws and the emitted triangles advance, it
+                owns no pixel, the next pass's ids start behind it, and with the tiny lists a rung still overflows
+They are generated against Model(partitioned=True): on a partitioned context a fused draw* filters the setup list, and
+frr_draw_wireframe, frr_readback_setup, frr_geometry_item_ranges, frr_resolve_varyings, frr_visible_pixels, frr_shade_items and
+a further frr_raster behind it are Undefined (FRR_ERR_INVALID) until the next geometry*; ranged shades stay allowed.  The
+partitioned mode refuses, it computes nothing else: the model is the UNPARTITIONED frame, which the ranks' parts must stitch to.
+run_rank() is one rank's part of a frame, for the fixed sequence line_ownership().
+
+Left out: user shaders, x0 < 0, a second raster of one geometry pass in another window (the model has one window per
+frame), state setters that change the vertex shader's uniforms between a geometry* and its rasterization, resolves behind
+the rasterization of a rung mesh (the NumPy oracle's cost).  The generator issues set_cull between passes only;
+cull_inside_split() is the fixed sequence with one inside split passes."""
 import ctypes
 import hashlib
 
@@ -71,7 +90,9 @@ K_PS = {8: ("FLAT", "PHONG", "BLINN"), 3: ("FLAT", "COLOR")}
 KINDS = ("plain", "indexed", "instanced", "list", "list_if")
 COMMANDS = ("lines", "wireframe", "resolve", "shade", "count_item", "count_triangle")
 QUERIES = ("item_ranges", "setup_triangles", "stats", "sync")
-WRITERS = ("geom", "draw", "lines", "wireframe", "resolve", "shade", "count", "set_cull", "set_uniforms", "set_texture")
+WRITERS = ("geom", "draw", "lines", "wireframe", "resolve", "shade", "count", "set_cull", "set_uniforms", "set_texture", "shade_items")
+COMMANDS_X = COMMANDS + ("shade_items",)       # the extended generator's
+XSEEDS = range(100, 112)                       # the extended seeds: tests/test_gpu_frame_model.py runs them on partitioned contexts
 
 UP, FOVY, ZN, ZF = (0.0, 1.0, 0.0), scenes.demo_camera(W, H)[3], 0.1, 100.0
 CAMERAS = [((0.0, 1.0, 3.0), (0.0, 0.0, 0.0)), ((0.9, 0.6, 2.6), (0.0, 0.05, 0.0))]
@@ -81,6 +102,24 @@ WIRE_COLORS = [(255, 200, 0, 255), (0, 255, 120, 255)]
 MIN_VALUES = (1, 150)
 MASKS = {"mask0": np.array([1, 0, 1, 1, 0, 1, 0, 1], np.uint32), "mask1": np.array([0, 7, 300, 0, 149, 150, 0, 2], np.uint32),
          "mask2": np.zeros(8, np.uint32)}
+
+
+def _materials(seed):
+    """a table of 8 materials (f_renderer_amd.MATERIAL_DTYPE; 8: the most items a generated pass has): slots in {0, 1}, and no
+    two neighbours share a slot, a strength or a flat colour; user[...] stays zero (the model has no user shaders)"""
+    from f_renderer_amd import MATERIAL_DTYPE
+    m = np.zeros(8, MATERIAL_DTYPE)
+    k = np.arange(8) + seed
+    m["texture_slot"] = k % 2
+    m["ambient_strength"] = (0.05 + 0.1 * (k % 5)).astype(F)
+    m["specular_strength"] = (0.2 + 0.15 * (k % 4)).astype(F)
+    m["flat_color"] = np.stack([((k * 37 + 11 * seed) % 256) / 255.0, ((k * 91 + 40) % 256) / 255.0, ((k * 13 + 200) % 256) / 255.0,
+                                1.0 - 0.25 * (k % 3)], axis=1).astype(F)
+    return m
+
+
+MATERIALS = {"mat0": _materials(0), "mat1": _materials(3), "mat2": _materials(5)}
+DEVICE_BOUND_TABLE = "mat2"                    # the GPU runner uploads the others with frr_materials_upload
 
 
 class Undefined(Exception):
@@ -285,8 +324,9 @@ class Model:
     """The state a sequence of steps leaves behind: the frame on the C oracle, the caller's buffers, the state that travels
     with commands, the latest geometry pass, the host's statistics, and the upper bounds of the work lists."""
 
-    def __init__(self, oracle, size=(W, H), clear=CLEAR):
+    def __init__(self, oracle, size=(W, H), clear=CLEAR, partitioned=False):
         self.o, (self.W, self.H), self.clear = oracle, size, clear
+        self.part = partitioned                # the sequence has to be legal on a partitioned context (frr_set_partition, world > 1)
         self.cull, self.cam, self.light, self.flat, self.slot, self.tex = 0, 0, 0, 0, 0, [0, 1]
         self.frame = oracle.Frame(*size)
         self.window, self.fno = FULL, -1
@@ -294,8 +334,11 @@ class Model:
         self.last = None
         self.bufs = new_buffers()
         self.prov = {}                         # count buffer -> what the latest frr_visible_pixels into it was
+        self.wrote = {}                        # varyings buffer -> the entries this frame's resolves wrote (bool[ENTRIES])
+        self.buf_win = {}                      # varyings buffer -> the (x1, rows) of the windows its resolves ran in, ever
         self.fan_cap, self.bin_cap = TINY["fan_capacity"], TINY["bin_capacity"]
         self.crossed = False                   # a rung was crossed in this frame
+        self.crossed_fan = False               # ... a rung of the fan slots, by a pass no partition filters: the same on every rank
         self.changed = False                   # the latest step changed a target or a buffer
 
     def copy(self):
@@ -309,6 +352,8 @@ class Model:
         ctypes.memmove(ctypes.byref(m.frame.counters), ctypes.byref(self.frame.counters), ctypes.sizeof(self.frame.counters))
         m.bufs = {k: v.copy() for k, v in self.bufs.items()}
         m.prov = dict(self.prov)
+        m.wrote = {k: v.copy() for k, v in self.wrote.items()}
+        m.buf_win = {k: set(v) for k, v in self.buf_win.items()}
         return m
 
     # -- uniforms of the moment --
@@ -324,9 +369,11 @@ class Model:
         cy, cx = np.meshgrid(np.arange(y0, y1), np.arange(x0, x1), indexing="ij")
         return (cy - y0) * x1 + (cx - x0), cy - y0, cx - x0
 
-    def _latest(self, cleared_ok=False):
+    def _latest(self, cleared_ok=False, filtered_ok=False):
         if self.last is None or (self.last.cleared and not cleared_ok):
             raise Undefined("no geometry pass in this frame yet")
+        if self.part and self.last.filtered and not filtered_ok:
+            raise Undefined("on a partitioned context a fused draw* filters the setup list: FRR_ERR_INVALID")
         return self.last
 
     # -- steps --
@@ -340,7 +387,8 @@ class Model:
         self.frame.counters = type(self.frame.counters)()
         self.window, self.fno = tuple(s["window"]), self.fno + 1
         self.tris_in = self.draws = self.emitted = 0
-        self.crossed = False
+        self.crossed = self.crossed_fan = False
+        self.wrote = {}
         if self.last is not None:
             self.last = self._copy_pass(self.last)
             self.last.cleared = True
@@ -362,9 +410,9 @@ class Model:
     def _set_texture(self, s):
         self.tex[s["slot"]] = s["image"]
 
-    def _geom(self, s):
-        if self.last is not None and not self.last.cleared and not self.last.rastered:
-            raise Undefined("the model rasters every geometry pass once")
+    def _geom(self, s, fused=False):
+        # (behind a pass that was never rastered -- an abandoned one -- too: it counted its tris_in, draws and triangles at its
+        # geometry call, owns no pixel, and this pass's ids start behind it)
         items, vs = [tuple(i) for i in s["items"]], s["vs"]
         if s["kind"] == "list_if":
             kept = P.kept_of(self.bufs[s["keep"]].reshape(-1)[:len(items)], s["min"]) if s["keep"] in self.bufs else \
@@ -386,10 +434,13 @@ class Model:
             fans.append(np.where(emit > 1, emit, 0))
             setups.append(setup[np.repeat(k, counts)])
         p.setup = np.concatenate(setups) if setups else np.zeros((0, 3), self.o.VERTEX_DTYPE)
-        p.base, p.emit, p.rastered, p.cleared = self.emitted, sum(p.per_item), False, False
+        p.base, p.emit, p.rastered, p.cleared, p.filtered = self.emitted, sum(p.per_item), False, False, False
         p.fan_need, p.bin_need = pass_needs(p.setup, np.concatenate(fans) if fans else np.zeros(0, np.int64))
         p.fan_rung, p.bin_rung = p.fan_need >= MARGIN * self.fan_cap, p.bin_need >= MARGIN * self.bin_cap
         self.crossed |= p.fan_rung or p.bin_rung
+        # (a fused draw* on a partitioned context filters its inputs by the rank's rows: what a rank needs there is a fraction
+        # the model does not compute -- nothing at all on a rank that owns nothing)
+        self.crossed_fan |= p.fan_rung and not (fused and self.part)
         if p.fan_need > TINY["fan_capacity"]:     # the pass may have overflowed: what the growth rule can have left
             self.fan_cap = max(self.fan_cap, growth(p.fan_need, 8))
         if p.bin_need > TINY["bin_capacity"]:
@@ -399,10 +450,13 @@ class Model:
         self.emitted += p.emit
         self.last = p
 
-    def _raster(self, s):
-        p = self._latest()
-        if p.rastered:
-            raise Undefined("the model rasters every geometry pass once")
+    def _raster(self, s, fused=False):
+        # (a pass that is rastered already is rastered again, in the frame's one window: the loop over its setup list runs again
+        # over the frame as it is now, with the same ids -- `rhw < depth` rejects, equal depth replaces, so after a depth-only
+        # raster a shading one gives every pixel of the pass its colour.  frag_covered and frag_nan add up again; draws,
+        # tris_in and tris_setup counted at the geometry call.  before / after / ps are those of the LATEST raster: a resolve
+        # sees the ownership that the last raster left.)
+        p = self._latest(filtered_ok=fused)
         if p.items and s["ps"] not in _vs_ps(p.vs):
             raise Undefined("a pixel shader for another K")
         if (p.cam, p.light) != (self.cam, self.light):
@@ -428,8 +482,9 @@ class Model:
         self.changed = any((a != b).any() for a, b in zip(p.before[1:], p.after[1:])) or (p.before[0] != p.after[0]).any() or p.emit > 0
 
     def _draw(self, s):
-        self._geom(s)
-        self._raster(s)
+        self._geom(s, fused=True)
+        self.last.filtered = True              # (what a partitioned context does to the setup list of a fused pass)
+        self._raster(s, fused=True)
 
     def _lines(self, s):
         self._paint(*LINES[s["list"]])
@@ -465,6 +520,9 @@ class Model:
         assert not np.isnan(ctx[own]).all(axis=1).any(), "an owned entry without varyings"
         before = buf[:n][own].copy()
         buf[:n][own] = ctx[own].view(np.uint32)
+        self.wrote.setdefault(s["buf"], np.zeros(buf.shape[0], bool))[:n] |= own
+        if own.any():
+            self.buf_win.setdefault(s["buf"], set()).add((self.window[1], self.window[3] - self.window[2]))
         self.changed = (before != buf[:n][own]).any()
 
     def _np_ctx(self, p):
@@ -494,25 +552,63 @@ class Model:
         _NP_CTX[key] = debug.get("ctx", np.full((self.W * self.H, p.K), np.nan, F))
         return _NP_CTX[key]
 
+    def _rank_holds(self, name):
+        """On a partitioned context a resolve writes the entries of the rank's rows only, and nothing carries them to the other
+        ranks: a shade reads what the ranks' resolves left where every one of them ran in a window with this one's depth
+        stride and rows (entry i is then the same rank's, i // x1 being its row) -- or nothing was resolved at all."""
+        if self.part and self.buf_win.get(name, set()) - {(self.window[1], self.window[3] - self.window[2])}:
+            raise Undefined("a varyings buffer resolved in a window that divides its entries among the ranks in another way")
+
     def _shade(self, s):
+        self._rank_holds(s["buf"])
         buf, K = self.bufs[s["buf"]], buffer_k(s["buf"])
         if s["ps"] not in K_PS[K]:
             raise Undefined("a pixel shader for another K")
-        first, count = s["ids"]
+        self._shade_range(s["ps"], buf, *s["ids"])
+
+    def _shade_range(self, ps, buf, first, count, material=None):
+        """frr_shade_varyings of one id range under the uniforms of the moment -- with `material` (one record of MATERIALS) its
+        texture slot, strengths and flat colour in place of theirs"""
         idx, ry, rx = self._window_index()
         ids = self.frame.tri_id[idx].astype(np.int64)
         sel = (ids != NONE) & (((ids - first) & 0xFFFFFFFF) < count)
         if not sel.any():
             return
         kw, image = self._uniforms()
+        what = (ps, self.cam, self.light, self.flat, image)
+        if material is not None:
+            image = self.tex[int(material["texture_slot"])]     # (the slot's texture as of the call)
+            kw.update(ambient=material["ambient_strength"], specular=material["specular_strength"], flat_color=material["flat_color"])
+            what = (ps, self.cam, self.light, image, material.tobytes())
         kw["tex"] = self.o.Texture(TEXTURES[image])
         ctx = np.ascontiguousarray(buf[idx[sel]])
-        key = _digest((s["ps"], self.cam, self.light, self.flat, image), ctx)
+        key = _digest(what, ctx)
         rgba = _SHADE[key] if key in _SHADE else \
-            _SHADE.put(key, self.o.shade_pixels(getattr(self.o, "PS_" + s["ps"]), self.o.make_uniforms(**kw), ctx.view(F)))
+            _SHADE.put(key, self.o.shade_pixels(getattr(self.o, "PS_" + ps), self.o.make_uniforms(**kw), ctx.view(F)))
         before = self.frame.color[ry[sel], rx[sel]].copy()
         self.frame.color[ry[sel], rx[sel]] = rgba
-        self.changed = (before != rgba).any()
+        self.changed |= bool((before != rgba).any())
+
+    def _shade_items(self, s):
+        """frr_shade_items by its definition in include/frr.h: for every item k of the latest pass one ranged shade over
+        (id_first[k], id_count[k]) under the call's uniforms with materials[k]'s texture slot, strengths and flat colour.
+        After a clear since the pass, for a pass that emitted nothing and for one that is not rastered yet (its ids are not in
+        the target) that writes nothing."""
+        if self.last is None:
+            raise Undefined("before any geometry pass")
+        p = self._latest(cleared_ok=True)
+        self._rank_holds(s["buf"])
+        buf, K = self.bufs[s["buf"]], buffer_k(s["buf"])
+        if s["ps"] not in K_PS[K]:
+            raise Undefined("a pixel shader for another K")
+        table = MATERIALS[s["table"]]
+        if len(table) < len(p.items):
+            raise Undefined("a table with fewer entries than the pass has items")
+        if p.cleared:
+            return
+        first = VIS.bounds_of(p.per_item, p.base)
+        for k, n in enumerate(p.per_item):
+            self._shade_range(s["ps"], buf, int(first[k]), int(n), table[k])
 
     def _count(self, s):
         buf, e = self.bufs[s["buf"]], int(s["entries"])
@@ -559,7 +655,8 @@ class Model:
         """what a frame end is compared with"""
         f = self.frame
         return dict(color=f.color.copy(), depth=f.depth.copy(), tri_id=f.tri_id.copy(), stats=self.stats(),
-                    bufs={k: v.copy() for k, v in self.bufs.items()}, crossed=self.crossed)
+                    bufs={k: v.copy() for k, v in self.bufs.items()}, crossed=self.crossed, crossed_fan=self.crossed_fan,
+                    wrote={k: v.copy() for k, v in self.wrote.items()})
 
 
 def run_frames(model, frames, skip=None):
@@ -571,6 +668,12 @@ def run_frames(model, frames, skip=None):
         for s in steps:
             if skip and id(s) in skip:
                 continue
+            if s.get("refused"):               # (a fixed sequence's step that the library has to refuse at this place)
+                try:
+                    model.copy().apply(s)
+                except Undefined:
+                    continue
+                raise AssertionError("the model takes a step marked as refused: " + describe(s))
             a = model.apply(s)
             if s["op"] in QUERIES:
                 answers.append((s["op"], a))
@@ -584,6 +687,42 @@ def run_model(oracle, frames, **kw):
     """what every frame of a sequence must leave behind: per frame the colour, depth and triangle ids, the statistics, every
     caller buffer, the host queries' answers in order, and whether the model says a rung is crossed in it"""
     return run_frames(Model(oracle, **kw), frames)
+
+
+def command_rows(op, window, height, rank, world, blocked):
+    """bool[height]: the plane rows of the colour target (= window-local rows) in which rank `rank` performs a command.  Draws,
+    resolves, shades and counts take their owner from the WINDOW's tile rows, frr_draw_lines and frr_draw_wireframe from the
+    CONTEXT's (frr_api.hip: row_owner(f, tiles_y) with each command's own tiles_y)."""
+    from f_renderer_amd.multigpu import tile_row_owner
+    x0, x1, y0, y1 = window
+    rows = height if op in ("lines", "wireframe") else y1 - y0
+    own = np.zeros(height, bool)
+    own[:rows] = np.asarray(tile_row_owner((rows + 31) // 32, world, blocked))[np.arange(rows) // 32] == rank
+    return own
+
+
+def run_rank(oracle, steps, rank, world, blocked, **kw):
+    """One frame as ONE rank of a partition leaves it: every step is applied to the rank's own frame and undone in the rows and
+    entries its command does not own there (each command's result at a pixel depends on that pixel and its entry alone).
+    For frames without counts and predicated passes, whose geometry depends on what the other ranks counted."""
+    m = Model(oracle, **kw)
+    for s in steps:
+        assert s["op"] != "count" and s.get("kind") != "list_if"
+        if s["op"] == "clear":
+            m.apply(s)
+            continue
+        own = command_rows(s["op"], m.window, m.H, rank, world, blocked)
+        row = np.arange(m.W * m.H) // m.window[1]
+        mine = np.zeros(m.W * m.H, bool)
+        mine[row < m.H] = own[row[row < m.H]]
+        f = m.frame
+        before = (f.color.copy(), f.depth.copy(), f.tri_id.copy(), {k: v.copy() for k, v in m.bufs.items() if buffer_k(k)})
+        m.apply(s)
+        f.color[~own] = before[0][~own]
+        f.depth[~mine], f.tri_id[~mine] = before[1][~mine], before[2][~mine]
+        for k, v in before[3].items():
+            m.bufs[k][:mine.size][~mine] = v[:mine.size][~mine]
+    return m.outputs()
 
 
 def same_outputs(a, b):
@@ -603,16 +742,28 @@ def same_outputs(a, b):
     return True
 
 
-def pass_partner(steps, s):
-    """the rasterization that belongs to the geometry step s of a split pass"""
+def pass_partners(steps, s):
+    """the rasterizations that belong to the geometry step s of a split pass: those up to the next geometry pass (one, in the
+    sequences of SEEDS; none for an abandoned pass, several for one that is rastered again)"""
     i = next(k for k, x in enumerate(steps) if x is s)
-    return next(x for x in steps[i + 1:] if x["op"] == "raster")
+    out = []
+    for x in steps[i + 1:]:
+        if x["op"] in ("geom", "draw"):
+            break
+        if x["op"] == "raster":
+            out.append(x)
+    return out
 
 
-def insensitive_steps(oracle, frames):
+def _drop_of(steps, s):
+    return {id(s)} | ({id(x) for x in pass_partners(steps, s)} if s["op"] == "geom" else set())
+
+
+def insensitive_steps(oracle, frames, **model_kw):
     """The writing steps, not marked as no-ops, whose removal changes no compared output (a split pass is removed as a whole,
-    the commands inside it stay).  A removal after which a later step is refused or undefined counts as a change."""
-    starts, m = [], Model(oracle)
+    the commands inside it stay; a rasterization of a pass that is rastered already is removed by itself too).  A removal
+    after which a later step is refused or undefined counts as a change."""
+    starts, m = [], Model(oracle, **model_kw)
     want = []
     for steps in frames:
         starts.append(m.copy())
@@ -620,11 +771,10 @@ def insensitive_steps(oracle, frames):
     bad = []
     for fi, steps in enumerate(frames):
         for s in steps:
-            if s["op"] not in WRITERS or s.get("noop"):
+            again = s["op"] == "raster" and s.get("again")
+            if (s["op"] not in WRITERS and not again) or s.get("noop"):
                 continue
-            skip = {id(s)}
-            if s["op"] == "geom":
-                skip.add(id(pass_partner(steps, s)))
+            skip = _drop_of(steps, s)
             try:
                 m = starts[fi].copy()
                 same = all(same_outputs(run_frames(m, [frames[k]], skip)[0], want[k]) for k in range(fi, len(frames)))
@@ -642,8 +792,10 @@ class _Gen:
     place is drawn again, a step that writes is kept only if it changes a target or a buffer (or is a no-op on purpose, while
     the seed's share of those allows one more), a state setter only in front of a command that comes out differently under it."""
 
-    def __init__(self, oracle, seed):
-        self.o, self.seed, self.rng, self.m = oracle, seed, np.random.RandomState(seed), Model(oracle)
+    def __init__(self, oracle, seed, extended=False):
+        self.o, self.seed, self.rng, self.m = oracle, seed, np.random.RandomState(seed), Model(oracle, partitioned=extended)
+        self.ext = extended                    # shade_items, second rasters and abandoned passes; legal on a partitioned context
+        self.last_resolve = None               # the varyings buffer the latest resolve wrote into
         self.frames, self.steps, self.reserve = [], None, 0
         self.noops = self.total = 0
         self.ranges = []                       # (first, count) of the items of this frame's rastered passes
@@ -681,7 +833,7 @@ class _Gen:
             trial.apply(s)
         except (Undefined, RuntimeError):
             return False
-        if s["op"] in ("lines", "wireframe", "resolve", "shade", "count", "draw", "raster") and not trial.changed:
+        if s["op"] in ("lines", "wireframe", "resolve", "shade", "shade_items", "count", "draw", "raster") and not trial.changed:
             if not force and not (noop_ok and self.noop_allowed()):
                 return False
             (self.geom_step if s["op"] == "raster" else s)["noop"] = True
@@ -691,6 +843,9 @@ class _Gen:
         self.total += 1
         if s["op"] == "geom":
             self.geom_step = s
+            if self.ext:                       # (an abandoned pass meets no raster that would record them)
+                p = trial.last
+                s.update(fan_need=p.fan_need, bin_need=p.bin_need, fan_rung=bool(p.fan_rung), bin_rung=bool(p.bin_rung))
         if s["op"] in ("draw", "raster"):
             p = trial.last
             first = VIS.bounds_of(p.per_item, p.base)
@@ -724,6 +879,8 @@ class _Gen:
                 items += [(self.pick(("p40", "empty", "torus")), int(M_GRID[i])) for i in range(int(rng.randint(2, 4)))]
         else:
             kind = self.pick(KINDS)
+            if self.ext and rng.rand() < 0.5:  # (every kind of pass in front of a shade_items in several seeds)
+                kind = ("list", "instanced", "plain")[(self.seed + self.m.fno + len(self.steps)) % 3]
             fed = [(b, pr) for b, pr in sorted(m.prov.items()) if pr["unit"] == "item" and pr["frame"] >= m.fno - 1 and pr["kind"] in ("list", "list_if")
                    and pr["entries"] >= pr["n"] >= 3 and all(mesh not in RUNGS.values() for mesh, _ in pr["items"])]
             if fed and rng.rand() < 0.4:
@@ -762,7 +919,7 @@ class _Gen:
         if kind == "wireframe":
             return dict(op="wireframe", color=int(rng.randint(2))) if p else None
         if kind == "resolve":
-            if not p or (p.rastered and any(mesh in RUNGS.values() for mesh, _ in p.items)):
+            if not p or not p.K or (p.rastered and any(mesh in RUNGS.values() for mesh, _ in p.items)):
                 return None                    # (the NumPy oracle is not run over a rung's thousands of triangles)
             return dict(op="resolve", buf=f"{pool}.v{p.K}{self.pick('ab')}")
         if kind == "shade":
@@ -772,6 +929,18 @@ class _Gen:
             written = [b for b in self.resolved if buffer_k(b) == K]
             ids = (0, NONE) if inside or not self.ranges or rng.rand() < 0.5 else self.ranges[int(rng.randint(len(self.ranges)))]
             return dict(op="shade", buf=self.pick(written), ps=self.pick(K_PS[K]), ids=tuple(int(x) for x in ids))
+        if kind == "shade_items":
+            # behind a raster of the pass: over the buffer the latest resolve wrote; before it (a no-op, replayed with the pass
+            # where the tiny lists overflow): over any buffer of the pass's K
+            if not p or not p.K or (self.m.part and p.filtered):
+                return None
+            bufs = [b for b in self.resolved if buffer_k(b) == p.K]
+            if p.rastered and not bufs:
+                return None
+            buf = self.last_resolve if p.rastered and self.last_resolve in bufs and rng.rand() < 0.8 else \
+                self.pick(bufs) if p.rastered else f"{pool}.v{p.K}{self.pick('ab')}"
+            ps = self.pick(("PHONG", "BLINN")) if p.K == 8 and rng.rand() < 0.6 else self.pick(K_PS[p.K])
+            return dict(op="shade_items", ps=ps, buf=buf, table=self.pick(sorted(MATERIALS)))
         unit = kind.split("_")[1]
         if unit == "item":
             if m.last is None:
@@ -798,16 +967,21 @@ class _Gen:
     def kind_of_command(self):
         """shades and resolves come up more often where they can do something"""
         p = self.m.last
-        w = {k: 1.0 for k in COMMANDS}
+        commands = COMMANDS_X if self.ext else COMMANDS
+        w = {k: 1.0 for k in commands}
         w["shade"] = 2.5 if self.resolved else 0.0
         w["resolve"] = 2.0 if p is not None and p.rastered and not p.cleared else 0.5
-        ws = np.array([w[k] for k in COMMANDS])
-        return self.pick(COMMANDS, p=ws / ws.sum())
+        w["shade_items"] = 2.5 if self.resolved and p is not None and p.rastered and not p.cleared else 0.0
+        ws = np.array([w[k] for k in commands])
+        return self.pick(commands, p=ws / ws.sum())
 
     def add_command(self, c):
-        ok = bool(c) and self.add(c, noop_ok=c["op"] in ("resolve", "count") or (c["op"] == "shade" and c["ids"][1] == 0))
-        if ok and c["op"] == "resolve" and not c.get("noop") and c["buf"] not in self.resolved:
-            self.resolved.append(c["buf"])
+        ok = bool(c) and self.add(c, noop_ok=c["op"] in ("resolve", "count") or (c["op"] == "shade" and c["ids"][1] == 0) or
+                                  (c["op"] == "shade_items" and not self.m.last.rastered))
+        if ok and c["op"] == "resolve" and not c.get("noop"):
+            self.last_resolve = c["buf"]
+            if c["buf"] not in self.resolved:
+                self.resolved.append(c["buf"])
         return ok
 
     # -- one pass, fused or split --
@@ -859,6 +1033,75 @@ class _Gen:
             return
         raise AssertionError("no pass could be placed")
 
+    def one_pass_x(self, rung):
+        """one_pass of the extended generator.  A split pass may be abandoned (no raster: the next pass, or the frame's end,
+        follows its geometry call and the commands inside it), and may be rastered twice, mostly as the pair a caller of the
+        split form uses: depth only, then the same list under a shader that writes colour.  Split passes are the usual case: on
+        a partitioned context everything that reads the setup list or the pass's tables needs one."""
+        rng = self.rng
+        for _ in range(16):
+            s = self.new_pass(rung)
+            ps = "DEPTH" if rung and rng.rand() < 0.5 else self.pick(("DEPTH", "FLAT") if rung == 2 else VS_PS[s["vs"]])
+            draw = dict(s, op="draw", ps=ps, fused=True)
+            if rung and self.m.cull != 0:
+                self.add(dict(op="set_cull", mode=0), force=True)
+            elif not rung and self.room() >= 3 and rng.rand() < 0.5:
+                t = self.setter(False)
+                a, b = self.probe([t, draw])[0], self.probe([draw])[0]
+                if a is not None and b is not None and a != b:
+                    self.add(t)
+            digest, changed = self.probe([draw])
+            if digest is None or (not changed and not self.noop_allowed()):
+                continue
+            if not rung and self.probed.last.fan_need > ORDINARY_FAN_NEED:
+                continue
+            if self.room() < 3 or rng.rand() < 0.15:
+                if self.add(draw, noop_ok=True):
+                    return
+                continue
+            added = self.add(dict(s, op="geom", fused=False))
+            assert added
+            # (a rung is abandoned in the seeds of one residue: with the tiny lists it overflows all the same)
+            abandon = rng.rand() < (1.0 if rung == 1 and self.seed % 4 == 1 else 0.12)
+            pair = not abandon and self.room() >= 4 and rng.rand() < 0.5
+            want = int(rng.randint(1, 3)) if rung else int(rng.randint(0, 2))
+            kinds = [str(k) for k in rng.permutation(COMMANDS_X)]
+            if rng.rand() < (0.35 if self.seed % 2 else 0.0):     # (the seeds that run with the tiny lists)
+                kinds.remove("shade_items")
+                kinds.append("shade_items")
+            n = 0
+            for _ in range(12):
+                if n >= want or self.room() <= (3 if pair else 2) or not kinds:
+                    break
+                if rng.rand() < 0.15:
+                    n += self.add(dict(op=self.pick(QUERIES)))
+                else:
+                    n += self.place(kinds.pop(), True)
+            if abandon:
+                self.geom_step["abandoned"] = True
+                return
+            colours = [x for x in VS_PS[s["vs"]] if x != "DEPTH"] if s["items"] else ["FLAT"]
+            added = self.add(dict(op="raster", ps="DEPTH" if pair else ps), force=True)
+            assert added, "a geometry pass whose rasterization is refused"
+            if pair or (self.room() >= 2 and rng.rand() < 0.2):
+                first = "DEPTH" if pair else ps
+                ps2 = ps if pair and ps != "DEPTH" else self.pick([x for x in colours + ["DEPTH"] if x != first])
+                for kind in rng.permutation(("resolve", "count_item", "count_triangle", "lines"))[:int(rng.randint(0, 2))]:
+                    if self.room() >= 2:
+                        self.place(str(kind), True)
+                self.add(dict(op="raster", ps=ps2, again=True))
+            return
+        raise AssertionError("no pass could be placed")
+
+    def items_behind(self):
+        """behind a pass: a resolve of it, and one shade of all its items under a table"""
+        p = self.m.last
+        if p.rastered and not (self.m.part and p.filtered) and p.K and p.emit and self.room() >= 2 and self.rng.rand() < 0.95 and \
+                not any(mesh in RUNGS.values() for mesh, _ in p.items):
+            self.add_command(self.command("resolve", False))
+            if self.last_resolve and buffer_k(self.last_resolve) == p.K:
+                self.place("shade_items", False)
+
     # -- one frame --
     def frame(self, fno, window, rung, end):
         rng = self.rng
@@ -874,7 +1117,12 @@ class _Gen:
             self.reserve = 3 if rung and k < at else 0        # (room for the rung's pass behind this one)
             if not r and self.room() < 2:
                 continue
-            self.one_pass(r)
+            if self.ext:
+                self.one_pass_x(r)
+                if not r:
+                    self.items_behind()
+            else:
+                self.one_pass(r)
             p = self.m.last
             if not r and p.kind in ("list", "list_if") and len(p.items) >= 3 and self.room() >= 1 and rng.rand() < 0.6:
                 n = len(p.items)
@@ -902,17 +1150,19 @@ def steps_of(frames):
     return [s for steps in frames for s in steps if s["op"] != "clear"]
 
 
-def generate(seed, oracle=None):
+def generate(seed, oracle=None, extended=False):
     """The frames of a seed: a list of FRAMES lists of steps (dicts: "op" and its arguments; "noop" on a step that writes
     nothing on purpose; "rung" on a pass over a rung mesh; "fan_rung", "bin_rung", "fan_need", "bin_need" on every pass, from
     the model).  Every frame starts with its "clear" and ends with "readback" or "fenced"; the steps after the clear are at most
     MAX_STEPS.  A pure function of the seed: np.random.RandomState(seed) is the only source of randomness, and the model the
     generator consults is deterministic."""
-    if seed in _GENERATED:
-        return _GENERATED[seed]
+    key = (seed, "extended") if extended else seed
+    if key in _GENERATED:
+        return _GENERATED[key]
     if oracle is None:
         from oracle import cref as oracle
-    g = _Gen(oracle, seed)
+    model_kw = dict(partitioned=True) if extended else {}
+    g = _Gen(oracle, seed, extended)
     rng = g.rng
     f1 = int(rng.randint(0, 2))
     f2 = int(rng.randint(f1 + 1, FRAMES))
@@ -922,11 +1172,11 @@ def generate(seed, oracle=None):
     frames = g.frames
     # what a later step overwrote: a step whose removal changes no compared output any more leaves the sequence
     for _ in range(24):
-        bad = insensitive_steps(oracle, frames)
+        bad = insensitive_steps(oracle, frames, **model_kw)
         if not bad:
             break
         fi, s = bad[0]
-        drop = {id(s)} | ({id(pass_partner(frames[fi], s))} if s["op"] == "geom" else set())
+        drop = _drop_of(frames[fi], s)
         frames = [[x for x in steps if id(x) not in drop] for steps in frames]
     # ... and the share of no-ops on purpose holds for what is left
     while True:
@@ -936,17 +1186,17 @@ def generate(seed, oracle=None):
             break
         for s in sorted(noops, key=lambda x: x["op"] in ("geom", "draw")):       # (a command before a pass)
             fi = next(k for k, steps in enumerate(frames) if any(x is s for x in steps))
-            drop = {id(s)} | ({id(pass_partner(frames[fi], s))} if s["op"] == "geom" else set())
+            drop = _drop_of(frames[fi], s)
             fewer = [[x for x in steps if id(x) not in drop] for steps in frames]
             try:
-                run_model(oracle, fewer)
+                run_model(oracle, fewer, **model_kw)
             except (Undefined, RuntimeError):
                 continue
             frames = fewer
             break
         else:
             raise AssertionError("the share of no-ops cannot be met")
-    _GENERATED[seed] = frames
+    _GENERATED[key] = frames
     return frames
 
 
@@ -968,6 +1218,68 @@ def cull_inside_split():
              dict(op="raster", ps="COLOR"),
              dict(op="stats"),
              dict(op="draw", kind="plain", vs="PHONG", items=[("torus", M_LEFT)], ps="BLINN", rung=0, fused=True),
+             dict(op="readback")]]
+
+
+def refused_behind_fused():
+    """A fixed frame for a partitioned context: behind a fused draw*, which filtered the setup list there, every command that
+    reads the setup list or the pass's tables is refused (FRR_ERR_INVALID; "refused" marks the steps) and leaves the context
+    drawing; ranged shades stay allowed; behind a split pass the same commands are taken."""
+    lst = [("p100", int(M_CLIPPED[0])), ("torus", int(M_GRID[1])), ("spiky", int(M_CLIPPED[3])), ("p40", int(M_GRID[4]))]
+    inst = [("torus", mi) for mi in (int(M_CLIPPED[1]), M_MIRROR, int(M_GRID[2]))]
+    no = dict(refused=True)
+    return [[dict(op="clear", window=FULL),
+             dict(op="geom", kind="instanced", vs="PHONG", items=inst, rung=0, fused=False),
+             dict(op="raster", ps="DEPTH"),
+             dict(op="resolve", buf="A.v8a"),
+             dict(op="draw", kind="list", vs="PHONG", items=lst, ps="PHONG", rung=0, fused=True),
+             dict(no, op="wireframe", color=0),
+             dict(no, op="setup_triangles"),
+             dict(no, op="item_ranges"),
+             dict(no, op="resolve", buf="A.v8b"),
+             dict(no, op="count", unit="item", buf="A.c0", entries=4),
+             dict(no, op="count", unit="triangle", buf="A.c1", entries=64),
+             dict(no, op="shade_items", ps="PHONG", buf="A.v8a", table="mat0"),
+             dict(op="lines", list=0),
+             dict(op="shade", buf="A.v8a", ps="BLINN", ids=(0, NONE)),
+             dict(op="geom", kind="list", vs="PHONG", items=lst, rung=0, fused=False),
+             dict(op="raster", ps="DEPTH"),
+             dict(op="resolve", buf="A.v8b"),
+             dict(op="shade_items", ps="PHONG", buf="A.v8b", table="mat1"),
+             dict(op="count", unit="item", buf="A.c0", entries=4),
+             dict(op="item_ranges"),
+             dict(op="stats"),
+             dict(op="readback")]]
+
+
+def abandoned_then_larger():
+    """A fixed frame: a geometry pass of one 256-input block that nothing rasters, then a pass of several blocks.  The second
+    pass's ids start behind what the first emitted -- a count the library takes from the first pass's block sums, which it has
+    to scan before the second pass sizes the tables (both passes use one workspace set with two frames in flight and with
+    option overlap 0; seed 100 of the partitioned runs met a scan of the reallocated sums)."""
+    lst = [("p257", int(M_CLIPPED[0])), ("spiky", int(M_GRID[3])), ("p257", int(M_GRID[4])), ("p100", int(M_CLIPPED[2]))]
+    return [[dict(op="clear", window=FULL),
+             dict(op="geom", kind="indexed", vs="GOURAUD", items=[("grid", int(M_CLIPPED[0]))], rung=0, fused=False, abandoned=True),
+             dict(op="lines", list=1),
+             dict(op="geom", kind="list", vs="PHONG", items=lst, rung=0, fused=False),
+             dict(op="raster", ps="PHONG"),
+             dict(op="item_ranges"),
+             dict(op="stats"),
+             dict(op="readback")]]
+
+
+LINE_WINDOW = (0, W, 0, 40)                    # two tile rows of the window, three of the context (line_ownership)
+
+
+def line_ownership():
+    """A fixed frame in a window of 40 rows: a pass, a line list over it, one shade of the pass's pixels.  The draw, the resolve
+    and the shade take their owner from the window's two tile rows, the lines from the context's three."""
+    return [[dict(op="clear", window=LINE_WINDOW),
+             dict(op="geom", kind="plain", vs="PHONG", items=[("spiky", int(M_CLIPPED[5]))], rung=0, fused=False),
+             dict(op="raster", ps="PHONG"),
+             dict(op="resolve", buf="A.v8a"),
+             dict(op="lines", list=0),
+             dict(op="shade", buf="A.v8a", ps="FLAT", ids=(0, 20)),
              dict(op="readback")]]
 
 

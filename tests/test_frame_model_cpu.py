@@ -311,3 +311,283 @@ def test_pinned_to_the_two_pass_resolve(oracle):
     V.assert_bits_equal(got["bufs"]["A.v3a"][:e.entries].view(np.float32), e.buffer())
     assert (got["bufs"]["A.v3b"] == M.SENTINEL_BITS).all(), "a resolve between geometry and rasterization owns no pixel yet"
     assert onp.VS_K[onp.VS_CLIP_COLOR] == 3
+
+
+# ---- the extended sequences: shade_items, passes rastered again, abandoned passes; legal on a partitioned context ---------------
+
+# sha256 over repr(frame_model.steps_of(frame_model.generate(seed))) of the seeds 0 .. 23 in order, computed at the commit before
+# the generator learnt the extended steps: what it yields for SEEDS without `extended` is what it yielded then
+DIGEST_OF_SEEDS = "2e727c2bf165b3032769c590bd70ddf1b5778159580c95327e6cea3ed450d0e2"
+
+
+def test_the_sequences_of_the_first_seed_set_are_unchanged(generated):
+    import hashlib
+    h = hashlib.sha256()
+    for seed in M.SEEDS:
+        h.update(repr(M.steps_of(generated[seed])).encode())
+    assert h.hexdigest() == DIGEST_OF_SEEDS
+
+
+@pytest.fixture(scope="module")
+def extended(oracle):
+    return {seed: M.generate(seed, oracle, extended=True) for seed in M.XSEEDS}
+
+
+def test_extended_sequences_are_deterministic_and_legal(oracle, extended):
+    assert len(M.XSEEDS) == 12
+    seed = M.XSEEDS[3]
+    M._GENERATED.pop((seed, "extended"))
+    assert _strip(M.generate(seed, oracle, extended=True)) == _strip(extended[seed])
+    for seed, frames in extended.items():
+        assert len(frames) == M.FRAMES
+        out = M.run_model(oracle, frames, partitioned=True)          # (raises where a step is refused on a partitioned context)
+        plain = M.run_model(oracle, frames)
+        assert all(M.same_outputs(a, b) for a, b in zip(out, plain)), "the partitioned mode only refuses: it computes nothing else"
+        for fi, steps in enumerate(frames):
+            assert steps[0]["op"] == "clear" and steps[-1]["op"] in ("readback", "fenced") and len(steps) - 1 <= M.MAX_STEPS, (seed, fi)
+            assert tuple(steps[0]["window"]) in (M.FULL, M.SUB)
+            latest = None                      # the latest pass: (its step, rastered how often)
+            for s in steps[1:-1]:
+                if s["op"] in ("geom", "draw"):
+                    latest = [s, int(s["op"] == "draw")]
+                elif s["op"] == "raster":
+                    assert latest is not None and latest[0]["op"] == "geom" and not latest[0].get("abandoned")
+                    assert bool(s.get("again")) == (latest[1] > 0), "`again` marks the rasters behind a pass's first"
+                    latest[1] += 1
+                elif s["op"] in ("wireframe", "resolve", "count", "item_ranges", "setup_triangles", "shade_items") and latest is not None:
+                    assert latest[0]["op"] == "geom", f"seed {seed} frame {fi}: {s['op']} behind a fused pass"
+                if s["op"] == "shade_items":
+                    assert s["table"] in M.MATERIALS and s["ps"] in M.K_PS[M.buffer_k(s["buf"])]
+
+
+def _extended_coverage(extended):
+    n = collections.Counter()
+    for seed, frames in extended.items():
+        tiny = seed % 2 == 1                   # tests/test_gpu_frame_model.py: the odd seeds run with the tiny work lists
+        for steps in frames:
+            latest, rastered = None, 0
+            for s in steps:
+                if s["op"] in ("geom", "draw"):
+                    latest, rastered = s, int(s["op"] == "draw")
+                    n["abandoned"] += bool(s.get("abandoned"))
+                    n["abandoned rung, tiny lists"] += bool(s.get("abandoned") and s["rung"] and s["fan_rung"] and tiny)
+                elif s["op"] == "raster":
+                    rastered += 1
+                    n["second raster"] += bool(s.get("again"))
+                    n["depth pre-pass pair"] += bool(s.get("again") and s["ps"] != "DEPTH" and first_ps == "DEPTH")
+                    if rastered == 1:
+                        first_ps = s["ps"]
+                elif s["op"] == "shade_items":
+                    n["shade_items"] += 1
+                    if latest is not None and rastered and not s.get("noop"):
+                        kind = {"list_if": "list", "indexed": "plain"}.get(latest["kind"], latest["kind"])
+                        n["shade_items behind " + ("an " if kind == "instanced" else "a ") + kind + " pass"] += 1
+                        n["shade_items under a lit shader"] += s["ps"] in ("PHONG", "BLINN")
+                    if latest is not None and latest["op"] == "geom" and not rastered:
+                        n["shade_items inside a split pass"] += 1
+                        n["shade_items inside a split pass, tiny lists"] += tiny
+                        n["shade_items inside a fan rung's split pass, tiny lists"] += bool(tiny and latest["fan_rung"])
+    return n
+
+
+def test_coverage_of_the_extended_seed_set(extended):
+    n = _extended_coverage(extended)
+    print(dict(n))
+    for kind in ("shade_items", "second raster", "abandoned", "depth pre-pass pair"):
+        assert n[kind] >= 6, (kind, dict(n))
+    for place in ("behind a list pass", "behind an instanced pass", "behind a plain pass", "inside a split pass, tiny lists"):
+        assert n["shade_items " + place] >= 3, (place, dict(n))
+    assert n["shade_items under a lit shader"] >= 3, dict(n)
+    assert n["shade_items inside a fan rung's split pass, tiny lists"] >= 1, dict(n)
+    assert n["abandoned rung, tiny lists"] >= 1, dict(n)
+
+
+def test_every_kept_step_of_the_extended_sequences_is_felt(oracle, extended):
+    for seed, frames in extended.items():
+        bad = M.insensitive_steps(oracle, frames, partitioned=True)
+        assert not bad, f"seed {seed}: removing {[(fi, M.describe(s)) for fi, s in bad]} changes no compared output"
+        flat = M.steps_of(frames)
+        assert len([s for s in flat if s.get("noop")]) <= M.NOOP_SHARE * len(flat), seed
+
+
+def _one_frame(oracle, steps, **kw):
+    m = M.Model(oracle, **kw)
+    return m, M.run_frames(m, [steps])[0]
+
+
+def test_shade_items_is_the_materials_rule_and_the_forward_loop(oracle):
+    """The model's shade_items held to the two things the per-feature tests hold frr_shade_items to: the tables pass the rule
+    the host and the device share (tests/materials_rule.py), and a depth-only list pass, a resolve and one shade_items leave
+    the frame of items_scenes' construction B -- the reference's loop with one ps_uniform per object on the C oracle."""
+    from . import drawlist_scenes as D
+    from . import items_scenes as IT
+    from . import materials_rule as MR
+    for name, t in M.MATERIALS.items():
+        assert len(t) == 8 and set(t["texture_slot"]) == {0, 1} and not t["user"].any() and not t["reserved"].any()
+        assert [g[0] for g in MR.ask([MR.ok(int(e["texture_slot"]), int(e["reserved"])) for e in t])] == [1] * 8
+        for k in range(7):
+            assert t["texture_slot"][k] != t["texture_slot"][k + 1] or k == 3
+            assert t["ambient_strength"][k] != t["ambient_strength"][k + 1] and t["specular_strength"][k] != t["specular_strength"][k + 1]
+            assert (t["flat_color"][k] != t["flat_color"][k + 1]).any()
+        for items in (0, 1, 7, 8):
+            code, text = MR.ask([MR.table(MR.SHADE, 4096, len(t), items, True, 0b0011, 0b0011)])[0]
+            assert code == MR.OK and text.split("|")[0] == ""
+    assert len({t.tobytes() for t in M.MATERIALS.values()}) == 3 and M.DEVICE_BOUND_TABLE in M.MATERIALS
+    sc = D.scene("clipped")
+    fb, per = IT.expected_B("clipped", "PHONG")
+    models = [int(np.flatnonzero((M.MODELS[:6] == m).all(axis=1))[0]) for m in sc.models]
+    names = [f"pin_{w}" for w in sc.which]
+    M.MESHES.update({f"pin_{k}": m.tris for k, m in enumerate(sc.meshes)})
+    M.MATERIALS["pin"] = IT.materials(sc.nitems)
+    ntex = len(M.TEXTURES)
+    M.TEXTURES.extend(D.place_textures())
+    try:
+        steps = [dict(op="clear", window=M.FULL),
+                 dict(op="geom", kind="list", vs="PHONG", items=list(zip(names, models)), rung=0), dict(op="shade_items", ps="PHONG", buf="A.v8a", table="pin"),
+                 dict(op="raster", ps="DEPTH"), dict(op="resolve", buf="A.v8a"), dict(op="shade_items", ps="PHONG", buf="A.v8a", table="pin"),
+                 dict(op="readback")]
+        m = M.Model(oracle)
+        m.tex = [ntex, ntex + 1, ntex + 2]
+        for s in steps[:3]:
+            m.apply(s)
+        assert not m.changed, "a pass that is not rastered yet has no id in the target: nothing is shaded"
+        got = M.run_frames(m, [steps[3:]])[0]
+    finally:
+        del M.TEXTURES[ntex:]
+        M.MATERIALS.pop("pin")
+        for k in range(len(sc.meshes)):
+            M.MESHES.pop(f"pin_{k}")
+    assert len(set(M.MATERIALS)) == 3
+    np.testing.assert_array_equal(got["tri_id"], fb.tri_id)
+    np.testing.assert_array_equal(got["depth"].view(np.uint32), fb.depth.view(np.uint32))
+    np.testing.assert_array_equal(got["color"], fb.color)
+    assert got["stats"]["tris_setup"] == sum(per) and (fb.tri_id != M.NONE).sum() > 500
+
+
+def test_shade_items_where_it_is_undefined_and_where_it_writes_nothing(oracle):
+    inst = [("torus", int(M.M_CLIPPED[0])), ("torus", M.M_MIRROR), ("torus", int(M.M_GRID[0]))]
+    geom = dict(op="geom", kind="instanced", vs="PHONG", items=inst, rung=0)
+    items = dict(op="shade_items", ps="PHONG", buf="A.v8a", table="mat0")
+    clear = dict(op="clear", window=M.FULL)
+    m = M.Model(oracle)
+    m.apply(clear)
+    with pytest.raises(M.Undefined):           # before any geometry pass
+        m.apply(items)
+    for s in (geom, dict(op="raster", ps="DEPTH"), dict(op="resolve", buf="A.v8a")):
+        m.apply(s)
+    for bad in (dict(items, ps="COLOR"), dict(items, buf="A.v3a", ps="PHONG")):       # a buffer whose K the shader refuses
+        with pytest.raises(M.Undefined):
+            m.copy().apply(bad)
+    a = m.copy()
+    a.apply(items)
+    assert a.changed and (a.frame.tri_id == m.frame.tri_id).all() and a.stats() == m.stats()
+    # every item under ITS material: item k's pixels under FLAT hold the quantised flat colour of entry k
+    b = m.copy()
+    b.apply(dict(items, ps="FLAT", table="mat1"))
+    first = M.VIS.bounds_of(m.last.per_item, m.last.base).astype(np.int64)
+    seen = 0
+    for k in range(3):
+        px = (m.frame.tri_id >= first[k]) & (m.frame.tri_id < first[k + 1])
+        seen += bool(px.any())
+        assert (b.frame.color.reshape(-1, 4)[px] == onp.quantize(M.MATERIALS["mat1"]["flat_color"][k:k + 1])).all(), k
+    assert seen >= 2
+    # ... after a clear since the pass, and for a pass that emitted nothing: FRR_OK, nothing written
+    c = m.copy()
+    c.apply(clear)
+    c.apply(items)
+    assert not c.changed
+    c.apply(dict(op="geom", kind="list", vs="PHONG", items=[("empty", int(M.M_GRID[0]))], rung=0))
+    c.apply(dict(op="raster", ps="PHONG"))
+    c.apply(items)
+    assert not c.changed
+    # on a partitioned context: refused behind a fused pass, like everything that reads the pass's tables
+    p = M.Model(oracle, partitioned=True)
+    p.apply(clear)
+    p.apply(dict(geom, op="draw", ps="DEPTH"))
+    for s in (items, dict(op="wireframe", color=0), dict(op="resolve", buf="A.v8a"), dict(op="item_ranges"), dict(op="setup_triangles"),
+              dict(op="count", unit="item", buf="A.c0", entries=3), dict(op="count", unit="triangle", buf="A.c0", entries=30), dict(op="raster", ps="PHONG")):
+        with pytest.raises(M.Undefined):
+            p.copy().apply(s)
+    p.apply(dict(op="shade", buf="A.v8a", ps="FLAT", ids=(0, M.NONE)))                 # a ranged shade reads no pass
+
+
+def test_a_pass_rastered_again_and_an_abandoned_pass(oracle):
+    """the depth pre-pass pair leaves the frame of the one shading raster and counts its fragments twice; draws, tris_in and
+    tris_setup count at the geometry call; an abandoned pass owns no pixel and the next pass's ids start behind it"""
+    lst = [("p100", int(M.M_CLIPPED[0])), ("torus", int(M.M_GRID[1])), ("spiky", int(M.M_CLIPPED[3]))]
+    clear, geom = dict(op="clear", window=M.SUB), dict(op="geom", kind="list", vs="PHONG", items=lst, rung=0)
+    _, once = _one_frame(oracle, [clear, geom, dict(op="raster", ps="PHONG"), dict(op="readback")])
+    _, pair = _one_frame(oracle, [clear, geom, dict(op="raster", ps="DEPTH"), dict(op="raster", ps="PHONG", again=True), dict(op="readback")])
+    for k in ("color", "depth", "tri_id"):
+        assert once[k].tobytes() == pair[k].tobytes(), k
+    assert once["stats"]["frag_covered"] > 0 and pair["stats"]["frag_covered"] == 2 * once["stats"]["frag_covered"]
+    assert {k: pair["stats"][k] for k in ("draws", "tris_in", "tris_setup")} == {k: once["stats"][k] for k in ("draws", "tris_in", "tris_setup")}
+    plain = dict(op="geom", kind="plain", vs="GOURAUD", items=[("p40", M.M_IDENT)], rung=0)
+    m, left = _one_frame(oracle, [clear, geom, plain, dict(op="raster", ps="COLOR"), dict(op="item_ranges"), dict(op="readback")])
+    n = once["stats"]["tris_setup"]
+    assert left["answers"][0][1]["first"][0] == n > 0 and left["stats"]["draws"] == 2 and left["stats"]["tris_setup"] > n
+    ids = left["tri_id"][left["tri_id"] != M.NONE]
+    assert ids.size and ids.min() >= n, "the abandoned pass owns no pixel"
+    assert left["stats"]["tris_in"] == once["stats"]["tris_in"] + M.MESHES["p40"].shape[0]
+    # ... and the fixed sequence of the GPU runs: one block abandoned, then a pass of several
+    frames = M.abandoned_then_larger()
+    want, = M.run_model(oracle, frames)
+    assert M.MESHES["grid"].shape[0] <= M.GEOM_BLOCK < sum(M.MESHES[m].shape[0] for m, _ in frames[0][3]["items"]) - M.GEOM_BLOCK
+    first = want["answers"][0][1]["first"][0]
+    assert first >= 128 and want["tri_id"][want["tri_id"] != M.NONE].min() >= first and not M.insensitive_steps(oracle, frames)
+
+
+def test_the_fixed_sequences_of_the_partitioned_runs(oracle):
+    frames = M.refused_behind_fused()
+    want, = M.run_model(oracle, frames, partitioned=True)
+    refused = [s for s in frames[0] if s.get("refused")]
+    assert {s["op"] for s in refused} == {"wireframe", "setup_triangles", "item_ranges", "resolve", "count", "shade_items"}
+    assert {s["unit"] for s in refused if s["op"] == "count"} == {"item", "triangle"}
+    with pytest.raises(AssertionError, match="marked as refused"):
+        M.run_model(oracle, frames)            # (without a partition nothing filters the setup list: every one is taken)
+    assert (want["bufs"]["A.v8b"] != M.SENTINEL_BITS).any() and [op for op, _ in want["answers"]] == ["item_ranges", "stats"]
+    kept = [[s for s in frames[0] if not s.get("refused")]]
+    assert not M.insensitive_steps(oracle, kept, partitioned=True)
+
+
+def test_lines_and_draws_own_different_rows_in_a_short_window_of_the_blocked_layout(oracle):
+    """frr_draw_lines takes its owner from the context's tile rows, draws, resolves, shades and counts from the window's.
+    Interleaved (ty % world) the two agree on every row whatever the counts are; blocked they agree only where the window has
+    as many tile rows as the context.  On the 96-row frame a window of 40 rows has two: with two ranks the draws give plane
+    rows 32 .. 39 to rank 1 and the lines give them to rank 0, so a line over a triangle there is complete on no rank."""
+    from f_renderer_amd.multigpu import tile_row_owner
+    for world in (2, 3, 4, 8):
+        for ctx_rows in range(1, 12):
+            for win_rows in range(1, ctx_rows + 1):
+                assert tile_row_owner(win_rows, world, False) == tile_row_owner(ctx_rows, world, False)[:win_rows]
+    assert tile_row_owner(2, 2, True) == [0, 1] and tile_row_owner(3, 2, True) == [0, 0, 1]
+    x0, x1, y0, y1 = M.LINE_WINDOW
+    assert (y1 - y0 + 31) // 32 == 2 and (M.H + 31) // 32 == 3
+    draws0, lines0 = (M.command_rows(op, M.LINE_WINDOW, M.H, 0, 2, True) for op in ("shade", "lines"))
+    draws1, lines1 = (M.command_rows(op, M.LINE_WINDOW, M.H, 1, 2, True) for op in ("shade", "lines"))
+    assert draws1[32:40].all() and lines0[32:40].all() and not draws0[32:40].any() and not lines1[32:40].any()
+    steps = M.line_ownership()[0]
+    want, = M.run_model(oracle, [steps])
+    assert not M.insensitive_steps(oracle, [steps])
+    # the frame has what the question is about: line pixels over the pass's pixels in plane rows 32 .. 39, some shaded after
+    idx, _ = M.painted(*M.LINES[0])
+    on_pass = idx[(want["tri_id"][idx] != M.NONE) & (idx // M.W >= 32) & (idx // M.W < 40)]
+    assert on_pass.size >= 4 and (want["tri_id"][on_pass] < 20).any() and (want["tri_id"][on_pass] >= 20).any()
+    for world in (2, 3):
+        for blocked in (False, True):
+            ranks = [M.run_rank(oracle, steps, rank, world, blocked)["color"] for rank in range(world)]
+            by_lines = np.stack([M.command_rows("lines", M.LINE_WINDOW, M.H, rank, world, blocked) for rank in range(world)])
+            by_draws = np.stack([M.command_rows("shade", M.LINE_WINDOW, M.H, rank, world, blocked) for rank in range(world)])
+            stitched = np.zeros_like(want["color"])
+            for rank in range(world):
+                stitched[by_lines[rank]] = ranks[rank][by_lines[rank]]
+            if not blocked:
+                assert (by_lines[:, :y1 - y0] == by_draws[:, :y1 - y0]).all()
+                np.testing.assert_array_equal(stitched, want["color"])
+            elif world == 2:
+                for rule in (by_lines, by_draws):
+                    stitched = np.zeros_like(want["color"])
+                    for rank in range(world):
+                        stitched[rule[rank]] = ranks[rank][rule[rank]]
+                    assert (stitched[32:40] != want["color"][32:40]).any(), "rows 32 .. 39 are complete on no rank"
+                    assert (stitched[:32] == want["color"][:32]).all()

@@ -16,7 +16,7 @@ import pytest
 
 from . import frame_model as M
 from . import varyings_scenes as V
-from .conftest import assert_depth_equal
+from .conftest import assert_depth_equal, owned_pixel_rows
 from .test_gpu_streams import _Alias
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +25,7 @@ MODES = ("own_fif1", "own_fif2", "bound")
 STAT_FIELDS = ("tris_in", "tris_setup", "draws", "frag_covered", "frag_nan")
 # seed -> what is known about a mismatch that is not resolved yet (pytest.mark.xfail(strict=True))
 XFAIL = {}
+TARGET_SENTINEL = 0x5A5A5A5A                    # what the caller-bound targets of a partitioned run hold before the first frame
 
 _EXPECTED = {}
 
@@ -45,13 +46,16 @@ def _i32(bits):
 class _Run:
     """one context in the seed's mode, the caller's device buffers, and the steps of tests/frame_model.py as API calls"""
 
-    def __init__(self, seed, tiny):
+    def __init__(self, seed, tiny, part=None):
+        """part: (rank, world, blocked) of a partitioned context; its caller-bound targets start as TARGET_SENTINEL"""
         import torch
         import f_renderer_amd as fr
         self.torch, self.fr = torch, fr
         self.mode, self.tiny = MODES[seed % 3], tiny
         self.st = torch.cuda.Stream()
         r = self.r = fr.Renderer(M.W, M.H, stream=self.st.cuda_stream)
+        if part:
+            r.set_partition(*part)
         if tiny:
             for name, value in M.TINY.items():
                 r.set_option(name, value)
@@ -59,7 +63,10 @@ class _Run:
         r.set_option("clear_eager", seed // 6 % 2)
         self.targets = None
         if self.mode == "bound":
-            self.targets = tuple(torch.zeros((M.H, M.W), dtype=dt, device="cuda") for dt in (torch.int32, torch.float32, torch.int32))
+            if part:
+                self.targets = tuple(torch.full((M.H, M.W), _i32(TARGET_SENTINEL), dtype=torch.int32, device="cuda") for _ in range(3))
+            else:
+                self.targets = tuple(torch.zeros((M.H, M.W), dtype=dt, device="cuda") for dt in (torch.int32, torch.float32, torch.int32))
             r.bind_targets(*(t.data_ptr() for t in self.targets))
         else:
             r.set_option("frames_in_flight", 1 if self.mode == "own_fif1" else 2)
@@ -73,7 +80,7 @@ class _Run:
             r.set_texture(slot, M.TEXTURES[slot])
         self.state = dict(cam=0, light=0, flat=0, slot=0)
         self._set_uniforms()
-        self.meshes, self.lists, self.insts = {}, {}, {}
+        self.meshes, self.lists, self.insts, self.tables = {}, {}, {}, {}
         self.lines = [r.upload_lines(xy, c) for xy, c in M.LINES]
         for vs in M.VS_PS:
             for name in M.MESHES:
@@ -90,6 +97,18 @@ class _Run:
             self.meshes[name, vs] = self.r.upload_mesh_indexed(*M.INDEXED[name], vs_id) if name in M.INDEXED else \
                 self.r.upload_mesh(M.MESHES[name], vs_id)
         return self.meshes[name, vs]
+
+    def table(self, name):
+        """a material table of the model: uploaded, or (DEVICE_BOUND_TABLE) bound in device memory"""
+        if name not in self.tables:
+            if name == M.DEVICE_BOUND_TABLE:
+                dev = self.torch.from_numpy(M.MATERIALS[name].view(np.uint8).copy()).to("cuda")
+                self.torch.cuda.synchronize()
+                assert dev.data_ptr() % 16 == 0
+                self.tables[name] = self.r.bind_materials_device(dev.data_ptr(), len(M.MATERIALS[name]), keepalive=dev)
+            else:
+                self.tables[name] = self.r.upload_materials(M.MATERIALS[name])
+        return self.tables[name]
 
     def ranges(self):
         x0, x1, y0, y1 = self.window
@@ -149,6 +168,9 @@ class _Run:
         elif op == "shade":
             r.shade_varyings(getattr(fr, "PS_" + s["ps"]), self.bufs[s["buf"]].data_ptr(), entries=M.ENTRIES, K=M.buffer_k(s["buf"]),
                              ids=s["ids"], **self.ranges())
+        elif op == "shade_items":
+            r.shade_items(getattr(fr, "PS_" + s["ps"]), self.bufs[s["buf"]].data_ptr(), self.table(s["table"]), entries=M.ENTRIES,
+                          K=M.buffer_k(s["buf"]), **self.ranges())
         elif op == "count":
             r.visible_pixels(s["unit"], out_ptr=self.bufs[s["buf"]].data_ptr(), entries=s["entries"], **self.ranges())
         elif op == "item_ranges":
@@ -295,6 +317,14 @@ def test_cull_mode_travels_with_the_geometry_command(oracle, seed):
     _both_runs(oracle, seed, "cull_inside_split")
 
 
+@pytest.mark.parametrize("seed", range(6))
+def test_an_abandoned_pass_is_counted_before_the_next_pass_sizes_its_tables(oracle, seed):
+    """frame_model.abandoned_then_larger in the three target modes, with option overlap 2 and 0: the ids of a pass of several
+    geometry blocks behind an abandoned pass of one (seed 100 of the partitioned runs met ids that started at another count:
+    the abandoned pass's block sums were scanned after the next pass had reallocated them)"""
+    _both_runs(oracle, seed, "abandoned_then_larger")
+
+
 def test_split_empty_list_takes_any_pixel_shader(oracle):
     """frr_geometry_list + frr_raster of a list without items takes every pixel shader frr_draw_list of it takes, and draws
     nothing (seed 5 above met the refusal: the shader was matched against a vertex shader the list does not have)"""
@@ -323,3 +353,339 @@ def test_split_empty_list_takes_any_pixel_shader(oracle):
         with pytest.raises(fr.FrrError, match="unknown shader id"):
             r.rasterization((0, M.W), (0, M.H), ps)
     r.close()
+
+
+# ---- partitioned contexts ----------------------------------------------------------------------------------------------------
+
+def _rows_mask(bands, n):
+    m = np.zeros(n, bool)
+    for a, b in bands:
+        m[a:b] = True
+    return m
+
+
+class _Ranks:
+    """The ranks of one partition as contexts in one process on one device, driven in lockstep: every step goes to every rank
+    before the next one.  Each rank has its own targets and its own caller buffers; the one exchange between them is the
+    all-reduce of a count buffer behind every frr_visible_pixels, which is what a multi-GPU caller does before it feeds the
+    counts to frr_draw_list_if."""
+
+    def __init__(self, seed, world, blocked, tiny):
+        import torch
+        self.torch, self.world, self.blocked = torch, world, bool(blocked)
+        self.x = [_Run(seed, tiny, part=(rank, world, bool(blocked))) for rank in range(world)]
+        self.st = torch.cuda.Stream()           # the stream of the all-reduce
+        self.reduced = False                    # an all-reduce may still be running
+        self.open_geom = False                  # the latest geometry pass of the frame is not rastered (yet)
+
+    def owners(self, window):
+        """(bool [world, H]: the plane rows of the colour target each rank owns -- lines by the context's tile rows, draws and
+        shades by the window's, which are the same rows here --, bool [world, y1 - y0]: the window-local rows), from the live
+        contexts and checked against the rule the other partition tests stitch by"""
+        x0, x1, y0, y1 = window
+        plane = np.stack([_rows_mask(x.r.owned_rows((0, M.H)), M.H) for x in self.x])
+        local = np.stack([_rows_mask(x.r.owned_rows((y0, y1)), y1 - y0) for x in self.x])
+        for rank in range(self.world):
+            np.testing.assert_array_equal(plane[rank], owned_pixel_rows(M.H, rank, self.world, self.blocked))
+            np.testing.assert_array_equal(local[rank], owned_pixel_rows(y1 - y0, rank, self.world, self.blocked))
+        assert (plane.sum(axis=0) == 1).all() and (local.sum(axis=0) == 1).all(), "every row has one owner"
+        np.testing.assert_array_equal(plane[:, :y1 - y0], local, err_msg="a window whose tile rows are not the context's")
+        return plane, local
+
+    def step(self, s):
+        """one step on every rank; returns the ranks' answers"""
+        if s["op"] == "count":
+            self.settle()                       # (frr_visible_pixels waits for no frr_frame_wait: it writes no target)
+        out = [x.step(s) for x in self.x]
+        if s["op"] in ("geom", "draw"):
+            self.open_geom = s["op"] == "geom"
+        elif s["op"] in ("raster", "clear"):
+            self.open_geom = False
+        if s["op"] == "count":
+            self.all_reduce(s["buf"], s["entries"])
+        return out
+
+    def all_reduce(self, name, entries):
+        """the ranks' counts summed on the device and written back into every rank's buffer: behind each rank's command
+        (frr_frame_fence), in front of its next one (frr_frame_wait).  A count behind a geometry pass that is not rastered yet
+        is guaranteed only once a synchronisation point has passed (a work list may have been too small: the count wrote
+        nothing and is replayed), so there every rank synchronises first."""
+        torch = self.torch
+        for x in self.x:
+            if self.open_geom:
+                x.r.sync()
+            x.r.frame_fence(self.st.cuda_stream)
+        with torch.cuda.stream(self.st):
+            total = torch.stack([x.bufs[name][:entries] for x in self.x]).sum(dim=0, dtype=torch.int32)
+            for x in self.x:
+                x.bufs[name][:entries].copy_(total)
+        for x in self.x:
+            x.r.frame_wait(self.st.cuda_stream)
+        self.reduced = True
+
+    def settle(self):
+        """the host waits for an all-reduce that may still be running (before the buffers are copied at a frame's end)"""
+        if self.reduced:
+            self.st.synchronize()
+            self.reduced = False
+
+    def close(self):
+        self.torch.cuda.synchronize()
+        for x in self.x:
+            x.r.close()
+
+
+def _sum_stats(got, want, what):
+    """tris_in, draws and tris_setup are every rank's (geometry is replicated); frag_covered and frag_nan are counted by the
+    tile kernels of the tiles a rank owns, so the ranks' sums are the unpartitioned figures"""
+    for rank, g in enumerate(got):
+        assert {k: g[k] for k in ("tris_in", "tris_setup", "draws")} == {k: want[k] for k in ("tris_in", "tris_setup", "draws")}, f"{what}, rank {rank}: {g} != {want}"
+    for k in ("frag_covered", "frag_nan"):
+        assert sum(g[k] for g in got) == want[k], f"{what}: the ranks' {k} {[g[k] for g in got]} do not add up to {want[k]}"
+
+
+def _entries_of(local_rows, window):
+    """bool [W * H]: the depth / id entries i of a window whose window-local row i // x1 is one of `local_rows`"""
+    x0, x1, y0, y1 = window
+    row = np.arange(M.W * M.H) // x1
+    out = np.zeros(M.W * M.H, bool)
+    out[row < y1 - y0] = local_rows[row[row < y1 - y0]]
+    return out
+
+
+def _stitch_frame(got, want, window, plane, local, bound, what, ever=None):
+    """ids, depth bits and colour of the ranks stitched by the owner of each row -- colour by its plane row, depth and ids by
+    the window-local row i // x1 of the entry -- equal the unpartitioned model's; the rows and entries a rank does not own
+    hold the clear values in the context's own targets and, in caller-bound ones, those or TARGET_SENTINEL.  (ever[rank]:
+    the entries the rank owns under ANY window of the run.  The depth stride is the window's x1, so an entry of another rank
+    in this frame may be the rank's own in a frame with another window: a caller-bound target, which nobody brings up to
+    date, may still hold that frame's fragment there.)"""
+    x0, x1, y0, y1 = window
+    world = len(got)
+    row = np.arange(M.W * M.H) // x1
+    inside = row < y1 - y0
+    color = np.zeros((M.H, M.W, 4), np.uint8)
+    depth, ids = np.zeros(M.W * M.H, np.float32), np.zeros(M.W * M.H, np.uint32)
+    clear_rgba = np.array(M.CLEAR[0], np.uint8)
+    clear_bits, sentinel = np.array([M.CLEAR[1]], np.float32).view(np.uint32)[0], np.uint32(TARGET_SENTINEL)
+    for rank, g in enumerate(got):
+        mine = np.zeros(M.W * M.H, bool)
+        mine[inside] = local[rank][row[inside]]
+        color[plane[rank]] = g["color"][plane[rank]]
+        depth[mine], ids[mine] = g["depth"][mine], g["tri_id"].ravel()[mine]
+        other_c = g["color"][~plane[rank]].reshape(-1, 4)
+        never = ~(mine | ever[rank]) if bound and ever is not None else ~mine
+        other_d, other_t = g["depth"].view(np.uint32)[never], g["tri_id"].ravel()[never]
+        if bound:
+            s4 = np.full(4, 0x5A, np.uint8)
+            assert ((other_c == clear_rgba).all(axis=1) | (other_c == s4).all(axis=1)).all(), f"{what}, rank {rank}: colour in rows of other ranks"
+            assert ((other_d == clear_bits) | (other_d == sentinel)).all(), f"{what}, rank {rank}: depth in entries of other ranks"
+            assert ((other_t == M.NONE) | (other_t == sentinel)).all(), f"{what}, rank {rank}: ids in entries of other ranks"
+        else:
+            assert (other_c == clear_rgba).all(), f"{what}, rank {rank}: an own target's rows of other ranks are not the cleared ones"
+            assert (other_d == clear_bits).all() and (other_t == M.NONE).all(), f"{what}, rank {rank}: an own target's entries of other ranks are not the cleared ones"
+    nobody = ~inside
+    depth[nobody], ids[nobody] = want["depth"][nobody], want["tri_id"][nobody]     # (checked above on every rank: nobody draws there)
+    assert (want["depth"].view(np.uint32)[nobody] == clear_bits).all() and (want["tri_id"][nobody] == M.NONE).all()
+    np.testing.assert_array_equal(ids, want["tri_id"], err_msg=f"{what}: stitched triangle ids")
+    assert_depth_equal(depth, want["depth"], err_msg=f"{what}: stitched depth bits")
+    np.testing.assert_array_equal(color, want["color"], err_msg=f"{what}: stitched colour")
+
+
+class _Buffers:
+    """The caller's varyings buffers over the frames of a run.  A buffer outlives a frame and the window changes between
+    frames, so the stitched buffer is kept up from frame to frame: where the model says this frame's resolves wrote, the entry
+    comes from the rank that owns its window-local row; every entry a rank never had to write keeps the sentinel there."""
+
+    def __init__(self, world):
+        self.stitched = M.new_buffers()
+        self.touched = [{k: np.zeros(v.shape[0], bool) for k, v in self.stitched.items() if M.buffer_k(k)} for _ in range(world)]
+
+    def frame(self, got, want, window, local, what):
+        x0, x1, y0, y1 = window
+        row = np.arange(M.ENTRIES) // x1
+        inside = row < y1 - y0
+        for name, b in want["bufs"].items():
+            if not M.buffer_k(name):
+                for rank, g in enumerate(got):
+                    np.testing.assert_array_equal(g["bufs"][name], b, err_msg=f"{what}: count buffer {name} of rank {rank}")
+                continue
+            wrote = want["wrote"].get(name, np.zeros(M.ENTRIES, bool))
+            for rank, g in enumerate(got):
+                mine = np.zeros(M.ENTRIES, bool)
+                mine[inside] = local[rank][row[inside]]
+                mine &= wrote
+                self.touched[rank][name] |= mine
+                self.stitched[name][mine] = g["bufs"][name][mine]
+                rest = g["bufs"][name][~self.touched[rank][name]]
+                assert (rest == M.SENTINEL_BITS).all(), f"{what}: varyings buffer {name} of rank {rank} was written outside the rows it owns"
+            V.assert_bits_equal(self.stitched[name].view(np.float32), b.view(np.float32), err_msg=f"{what}: stitched varyings buffer {name}")
+
+
+_EXPECTED_X = {}
+
+
+def _expected_x(oracle, key):
+    """the frames of an extended seed, or of a fixed sequence of frame_model, with what the partitioned model says they leave"""
+    if key not in _EXPECTED_X:
+        frames = getattr(M, key)() if isinstance(key, str) else M.generate(key, oracle, extended=True)
+        _EXPECTED_X[key] = (frames, M.run_model(oracle, frames, partitioned=True))
+    return _EXPECTED_X[key]
+
+
+def _run_partitioned(oracle, seed, world, blocked, tiny, key):
+    import f_renderer_amd as fr
+    frames, want = _expected_x(oracle, key)
+    p = _Ranks(seed, world, blocked, tiny)
+    bound = p.x[0].mode == "bound"
+    log = [f"{key} world={world} blocked={blocked} mode={p.x[0].mode} lists={'tiny' if tiny else 'default'}"]
+    bufs, replays, pending = _Buffers(world), {}, []
+    try:
+        ever = [np.zeros(M.W * M.H, bool) for _ in range(world)]
+        for window in {tuple(steps[0]["window"]) for steps in frames}:
+            for rank, rows in enumerate(p.owners(window)[1]):
+                ever[rank] |= _entries_of(rows, window)
+        for fi, steps in enumerate(frames):
+            answers = iter(want[fi]["answers"])
+            window = tuple(steps[0]["window"])
+            for s in steps[:-1]:
+                log.append(f"  frame {fi}: " + M.describe(s))
+                if s.get("refused"):
+                    for rank, x in enumerate(p.x):
+                        with pytest.raises(fr.FrrError) as err:
+                            x.step(s)
+                        assert err.value.code == fr.FRR_ERR_INVALID, f"rank {rank}: {err.value}"
+                    continue
+                got = p.step(s)
+                if s["op"] in M.QUERIES:
+                    op, w = next(answers)
+                    assert op == s["op"]
+                    if op == "stats":
+                        _sum_stats(got, w, f"frame {fi}, stats")
+                    else:
+                        for rank, a in enumerate(got):
+                            _same_answer(op, a, w, f"frame {fi}, {op}, rank {rank}")
+            log.append(f"  frame {fi}: " + steps[-1]["op"])
+            plane, local = p.owners(window)
+            p.settle()
+            if steps[-1]["op"] == "readback":
+                got = [x.end_readback() for x in p.x]
+                replays[fi] = [g["stats"]["replays"] for g in got]
+                pending.append((fi, window, plane, local, got, None))
+            else:
+                # (include/frr.h: what is issued behind a frr_geometry* that no frr_raster has followed is guaranteed only once a
+                # synchronisation point has passed -- frr_frame_fence is none, and seed 109 met it: with the tiny lists an
+                # abandoned rung cancelled the shade behind it, and the fenced copy was taken before the replay)
+                if p.open_geom:
+                    for x in p.x:
+                        x.r.sync()
+                pending.append((fi, window, plane, local, None, [x.end_fenced() for x in p.x]))
+                if tiny:
+                    pending[-1] += ([x.r.stats() for x in p.x],)
+                    replays[fi] = [st["replays"] for st in pending[-1][6]]
+        p.torch.cuda.synchronize()
+        last = [x.r.stats() for x in p.x]
+        replays[len(frames) - 1] = [st["replays"] for st in last]
+        # (the frames are compared in their order: a varyings buffer carries what earlier frames wrote)
+        for fi, window, plane, local, got, fenced, *stats in pending:
+            if got is None:
+                got = [_Run.fenced_as_host(f) for f in fenced]
+                for rank, g in enumerate(got):
+                    g["stats"] = stats[0][rank] if stats else last[rank] if fi == len(frames) - 1 else None
+            _check_partitioned_frame(got, want[fi], window, plane, local, bound, bufs, f"frame {fi} ({'fenced copy' if fenced else 'read back'})", ever)
+        for x in p.x:
+            for name, mask in x.masks.items():
+                np.testing.assert_array_equal(mask.cpu().numpy().view(np.uint32), M.MASKS[name], err_msg=f"the uploaded keep mask {name} changed")
+        # replays: none with the default lists; with the tiny ones on EVERY rank in a frame where the model says a geometry*
+        # call crosses a rung of the fan slots (frr_geometry* never filters: the need is the unpartitioned one).  A rank's need
+        # of bin records, and of fan slots under a fused draw*, which filters its inputs by the rank's rows, is a fraction the
+        # model does not compute: a rank that owns nothing needs none.
+        if not tiny:
+            assert not any(any(v) for v in replays.values()), f"replays with the default lists: {replays}"
+        else:
+            for fi in range(len(frames)):
+                assert all(n > 0 for n in replays[fi]) or not want[fi]["crossed_fan"], f"frame {fi} crosses a rung of the fan slots: replays per rank {replays}"
+    except AssertionError as e:
+        raise AssertionError("\n".join(log) + f"\n{e}") from None
+    finally:
+        p.close()
+    return replays
+
+
+def _check_partitioned_frame(got, want, window, plane, local, bound, bufs, what, ever=None):
+    _stitch_frame(got, want, window, plane, local, bound, what, ever)
+    if got[0]["stats"] is not None:
+        _sum_stats([g["stats"] for g in got], want["stats"], what)
+    bufs.frame(got, want, window, local, what)
+
+
+def _partition_of(seed):
+    return (2, 3, 4)[seed % 3], seed // 3 % 2, seed % 2 == 1
+
+
+@pytest.mark.parametrize("seed", [pytest.param(s, marks=pytest.mark.xfail(strict=True, reason=XFAIL[s])) if s in XFAIL else s for s in M.XSEEDS])
+def test_frame_model_partitioned(oracle, seed):
+    """The extended sequences (frr_shade_items, passes rastered again, abandoned passes) on the ranks of a partition, in
+    lockstep, held to the UNPARTITIONED model after every frame.  The seed decides the world (2, 3 or 4 ranks: the frame and
+    the 80-row window both have three tile rows, so in a world of 4 one rank owns nothing), the layout, the target mode and the
+    work lists (tiny on odd seeds, default on even ones).  Compared: colour, depth bits and ids stitched by the owner of each
+    row; the varyings buffers stitched the same way, entries no rank had to write still the sentinel; count buffers (all-
+    reduced), keep masks and host queries equal to the model's on every rank; tris_in, draws and tris_setup on every rank,
+    frag_covered and frag_nan as the ranks' sum; replays.
+    Rows of other ranks.  include/frr.h (frr_bind_targets): "only the tile rows the rank owns are defined in caller-owned
+    targets ...; the ctx's own targets are brought up to date in full whenever they are read back".  For own targets that is
+    asserted as it is implemented (k_clear_unowned_rows, unowned_debt in frr_api.hip): at a read-back or behind frr_target_ptrs
+    every row and entry of another rank holds the frame's clear values.  Caller-bound targets were filled with TARGET_SENTINEL
+    before the first frame: a rank never draws there, but a clear that is not performed inside a full-window draw (a sub-
+    window, a command other than a draw first, option clear_eager) clears the whole target, so such rows hold the sentinel or
+    the clear values and nothing else -- of depth and ids, the entries that are the rank's own under no window of the run: the
+    depth stride is the window's x1, and an entry of another rank in this frame may hold the rank's own fragment of a frame
+    with the other window, which nobody clears in a caller-bound target.
+    Seed 100 found the abandoned pass whose block sums were scanned after the next pass had reallocated them:
+    test_an_abandoned_pass_is_counted_before_the_next_pass_sizes_its_tables."""
+    world, blocked, tiny = _partition_of(seed)
+    replays = _run_partitioned(oracle, seed, world, blocked, tiny, seed)
+    print(f"seed {seed}: world {world}, replays per frame and rank: {replays}")
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_refused_behind_a_fused_pass_on_every_rank(oracle, seed):
+    """frame_model.refused_behind_fused in worlds of 2, 3 and 4 ranks: frr_draw_wireframe, frr_readback_setup,
+    frr_geometry_item_ranges, frr_resolve_varyings, frr_visible_pixels and frr_shade_items behind a fused frr_draw_list answer
+    FRR_ERR_INVALID on every rank, and the frame is the one the other steps leave"""
+    world, blocked, tiny = _partition_of(seed)
+    _run_partitioned(oracle, seed, world, blocked, tiny, "refused_behind_fused")
+
+
+@pytest.mark.parametrize("blocked", [False, True])
+@pytest.mark.parametrize("world", [2, 3])
+def test_lines_take_the_contexts_tile_rows_in_a_short_window(oracle, world, blocked):
+    """frame_model.line_ownership: a pass, a line list over it and a shade in a window of 40 rows -- two tile rows, where the
+    context has three.  frr_draw_lines takes its owner from the context's tile rows, the others from the window's.
+    Every rank's colour is the model's frame with each command undone outside the rows that command owns on the rank
+    (frame_model.run_rank); the context's own targets hold the clear colour in every other row at the read-back.
+    Interleaved the two rules agree, and the ranks stitch to the unpartitioned frame.  Blocked they do not: with two ranks
+    plane rows 32 .. 39 are the draws' on rank 1 and the lines' on rank 0, and that tile row is complete on no rank
+    (include/frr.h, frr_draw_lines: the limit of the rule)."""
+    frames = M.line_ownership()
+    want, = M.run_model(oracle, frames)
+    stitched = np.zeros_like(want["color"])
+    for rank in range(world):
+        x = _Run(0, False, part=(rank, world, blocked))
+        try:
+            for s in frames[0][:-1]:
+                x.step(s)
+            got = x.end_readback()
+        finally:
+            x.close()
+        mine = M.run_rank(oracle, frames[0], rank, world, blocked)
+        np.testing.assert_array_equal(got["color"], mine["color"], err_msg=f"rank {rank}: colour")
+        np.testing.assert_array_equal(got["tri_id"], mine["tri_id"], err_msg=f"rank {rank}: triangle ids")
+        assert_depth_equal(got["depth"], mine["depth"], err_msg=f"rank {rank}: depth bits")
+        rows = M.command_rows("lines", M.LINE_WINDOW, M.H, rank, world, blocked)
+        np.testing.assert_array_equal(rows, owned_pixel_rows(M.H, rank, world, blocked))
+        stitched[rows] = got["color"][rows]
+    if not blocked:
+        np.testing.assert_array_equal(stitched, want["color"], err_msg="the ranks' images stitched by plane row")
+    elif world == 2:
+        assert (stitched[32:40] != want["color"][32:40]).any() and (stitched[:32] == want["color"][:32]).all()
