@@ -28,6 +28,12 @@
 //   --materials with --list --deferred gives every object a material of its own -- texture slots 0, 1, 2 in turn (the diffuse
 //       texture, and it with its first / its second channel inverted) and a flat colour in turn -- and shades the whole list
 //       with ONE pass over the frame (shade_items_host): phong.rs:361-370, a ps_uniform per object, for a list
+//   --occlusion with --list draws the mesh once more, unscaled, as an occluder in front of the right part of the grid, and then
+//       runs the occlusion loop of INTEGRATION.md 1f with no host wait in between: the objects' bounding boxes as a proxy list,
+//       queried against the occluder's depth (query_pixels: nothing is drawn), the objects whose box passed somewhere drawn
+//       (draw_list_if on the counts), what ended up on screen counted (visible_pixels).  It prints per item the proxy's count,
+//       the object's own count and its visible pixels, how many items were skipped, and whether colour and depth equal the
+//       frame that draws every object
 //   --cull neg|pos anywhere among them drops the input triangles whose clip-space determinant is negative / positive before
 //       they are set up (set_cull): on a closed mesh, the faces that look away from the camera
 //   phong_headless --dump-assets <model.obj> <diffuse.tga> <mesh_out.f32> <tex_out.rgba>
@@ -55,12 +61,12 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false, materials = false;
+    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false, materials = false, occlusion = false;
     for (int i = 1; i < argc; ++i)
         if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible" || std::string(argv[i]) == "--reuse" ||
-            std::string(argv[i]) == "--materials") {
+            std::string(argv[i]) == "--materials" || std::string(argv[i]) == "--occlusion") {
             (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : std::string(argv[i]) == "--reuse" ? reuse :
-             std::string(argv[i]) == "--materials" ? materials : deferred) = true;
+             std::string(argv[i]) == "--materials" ? materials : std::string(argv[i]) == "--occlusion" ? occlusion : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -83,6 +89,7 @@ int main(int argc, char **argv)
     if (visible && !list && instances < 0) { std::cerr << "--visible goes with --list or --instances N\n"; return 2; }
     if (reuse && (!list || !visible || wireframe || deferred)) { std::cerr << "--reuse goes with --list --visible (and without --wireframe / --deferred)\n"; return 2; }
     if (materials && (!list || !deferred)) { std::cerr << "--materials goes with --list --deferred\n"; return 2; }
+    if (occlusion && (!list || visible || reuse || wireframe || deferred)) { std::cerr << "--occlusion goes with --list (and without --visible / --reuse / --wireframe / --deferred)\n"; return 2; }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
         if (argc < 6) { std::cerr << "usage: phong_headless --dump-assets model.obj diffuse.tga mesh_out.f32 tex_out.rgba\n"; return 2; }
@@ -105,7 +112,9 @@ int main(int argc, char **argv)
                      "        --cull neg|pos: drop the inputs whose clip-space determinant has that sign;\n"
                      "        --visible (with --list or --instances N): print the pixels every item owns on screen;\n"
                      "        --reuse (with --list --visible): a second frame by draw_list_if on the first one's counts;\n"
-                     "        --materials (with --list --deferred): a texture slot and a flat colour per object, one shade_items)\n";
+                     "        --materials (with --list --deferred): a texture slot and a flat colour per object, one shade_items;\n"
+                     "        --occlusion (with --list): an occluder in front of part of the list, box proxies queried against its depth\n"
+                     "        (query_pixels), and only the objects whose proxy passed drawn (draw_list_if))\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -163,6 +172,70 @@ int main(int argc, char **argv)
                 m[14] = -0.25f * (float)(i % 3);
             }
         } else if (list) models.assign(1, model);
+        if (occlusion) {
+            // An occluder in front of part of the list; then, with no host wait in between: the box proxies of all objects queried
+            // against its depth, the objects whose proxy passed drawn, what ended up on screen counted (with
+            // nothing known from a frame before).  The frame must equal the one that draws every object.
+            const uint64_t n = models.size();
+            float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
+            auto grow = [&](const frr::VSInput &v) { for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], v.pos[k]); hi[k] = std::max(hi[k], v.pos[k]); } };
+            for (const auto &t : vin) for (const auto &v : t) grow(v);
+            for (const auto &v : indexed.vertices) grow(v);
+            const float inflate = 0.02f;   // about a pixel's worth: the box is conservative only up to the snap to integer pixels
+            for (int k = 0; k < 3; ++k) { lo[k] -= inflate; hi[k] += inflate; }
+            static const int quads[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {0, 4, 5, 1}, {2, 3, 7, 6}, {0, 2, 6, 4}, {1, 5, 7, 3}};   // corner i: bit k picks hi
+            std::vector<std::array<frr::VSInput, 3>> box(12);
+            std::memset(box.data(), 0, box.size() * sizeof(box[0]));
+            for (int q = 0; q < 6; ++q)
+                for (int h = 0; h < 2; ++h)
+                    for (int v = 0; v < 3; ++v) {
+                        const int corner = quads[q][h == 0 ? v : (v == 0 ? 0 : v + 1)];
+                        for (int k = 0; k < 3; ++k) box[(size_t)(2 * q + h)][(size_t)v].pos[k] = (corner >> k) & 1 ? hi[k] : lo[k];
+                    }
+            const frr::Mesh box_mesh = renderer.upload_mesh(box, FRR_VS_PHONG);
+            const frr::DrawList objects = renderer.upload_draw_list(std::vector<frr::Mesh>((size_t)n, mesh), models);
+            const frr::DrawList proxies = renderer.upload_draw_list(std::vector<frr::Mesh>((size_t)n, box_mesh), models);
+            frr::Mat4 occluder = frr::set_identity();
+            occluder[12] = 0.9f; occluder[13] = -0.1f; occluder[14] = 1.0f;   // the mesh itself, unscaled, in front of the right part of the grid
+            auto draw_occluder = [&] {
+                std::memcpy(renderer.uniforms.model, occluder.data(), 64); renderer.set_uniforms();
+                renderer.draw(mesh, FRR_PS_PHONG);
+                std::memcpy(renderer.uniforms.model, model.data(), 64); renderer.set_uniforms();
+            };
+            frr::FrameBuffer all = frr::FrameBuffer::create(W, H);
+            std::vector<float> all_depth, depth;
+            draw_occluder();
+            renderer.draw_list(objects, FRR_PS_PHONG);                                          // the frame that draws everything
+            renderer.read_frame_buffer(all);
+            renderer.read_depth(all_depth);
+            uint32_t *dev = nullptr;
+            if (hipMalloc((void **)&dev, (size_t)(n ? n : 1) * 3 * sizeof(uint32_t)) != 0) { std::cerr << "hipMalloc failed\n"; return 1; }
+            uint32_t *q_box = dev, *q_own = dev + n, *vis = dev + 2 * n;
+            renderer.clear({30, 30, 30, 255}, 0.0f);
+            draw_occluder();
+            renderer.geometry_list(proxies);
+            renderer.query_pixels(FRR_PER_ITEM, q_box, n);                                      // would the box be visible against what is there?
+            renderer.geometry_list(objects);
+            renderer.query_pixels(FRR_PER_ITEM, q_own, n);                                      // (the objects themselves, for the print below)
+            renderer.draw_list_if(objects, q_box, n, FRR_PS_PHONG);                             // keep[i] >= 1: the proxy passed somewhere
+            renderer.visible_pixels(FRR_PER_ITEM, vis, n);
+            renderer.read_frame_buffer(frame_buffer);                                           // (the first host wait of the loop)
+            renderer.read_depth(depth);
+            std::vector<uint32_t> host((size_t)n * 3, 0u);
+            if (n && hipMemcpy(host.data(), dev, host.size() * sizeof(uint32_t), 2 /* device to host */) != 0) { std::cerr << "hipMemcpy failed\n"; return 1; }
+            size_t skipped = 0;
+            for (size_t k = 0; k < (size_t)n; ++k) {
+                std::printf("item %zu: proxy count %u, own count %u, visible pixels %u\n", k, host[k], host[(size_t)n + k], host[2 * (size_t)n + k]);
+                skipped += host[k] == 0u;
+                if (host[k] == 0u && host[(size_t)n + k] != 0u) { std::cerr << "item " << k << ": its proxy is hidden, the object is not\n"; return 3; }
+            }
+            const bool same_colour = frame_buffer.get_data() == all.get_data();
+            const bool same_depth = depth.size() == all_depth.size() && std::memcmp(depth.data(), all_depth.data(), depth.size() * sizeof(float)) == 0;
+            std::printf("occlusion: skipped %zu of %zu items, colour equal: %s, depth equal: %s\n", skipped, (size_t)n, same_colour ? "yes" : "no", same_depth ? "yes" : "no");
+            (void)hipFree(dev);
+            std::ofstream(out_rgba, std::ios::binary).write(reinterpret_cast<const char *>(frame_buffer.get_data().data()), frame_buffer.get_size());
+            return 0;
+        }
         frr::DrawList items;
         if (list) {
             items = renderer.upload_draw_list(std::vector<frr::Mesh>(models.size(), mesh), models);

@@ -8,6 +8,7 @@
 #include "frr_varyings.h"
 #include "frr_shade.h"
 #include "frr_visible.h"
+#include "frr_query.h"
 #include "frr_own.h"
 
 #include <math.h>
@@ -282,6 +283,9 @@ struct Cmd {
     const frr_material *mats = nullptr;
     // VISIBLE (frr_visible_pixels): the window in x0 .. y1, the unit and the caller's buffer
     int vis_unit = 0; uint32_t *vis_out = nullptr; uint64_t vis_entries = 0;
+    // frr_query_pixels: a RASTER command that counts instead of drawing (exec_raster), with VISIBLE's unit and buffer -- or, where
+    // there is nothing to rasterize, a VISIBLE command that only zeroes the buffer
+    bool query = false;
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
@@ -1044,6 +1048,84 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_query_pixels behind exec_raster's binning: k_visible_prep zeroes the caller's buffer and builds the item boundaries,
+// k_query (frr_query.h) counts in the tile kernel's place.  No target is written, so the launches take the frame's stream as
+// exec_visible does: pending frr_frame_wait events are not their business, the caller's buffer is fenced like a target.
+int list_item_first(frr_ctx *c, const uint32_t **item_first);
+template <bool ITEM, bool HIST> void launch_query_nw(hipStream_t ts, uint32_t grid, int nw, const RasterArgs &a, const QueryArgs &qa, int win_safe)
+{
+    if (nw == LIGHT_NW) hipLaunchKernelGGL((k_query<ITEM, HIST, LIGHT_NW>), dim3(grid), dim3(LIGHT_NW * 64), 0, ts, a, qa, win_safe);
+    else if (nw == 4) hipLaunchKernelGGL((k_query<ITEM, HIST, 4>), dim3(grid), dim3(256), 0, ts, a, qa, win_safe);
+    else if (nw == 6) hipLaunchKernelGGL((k_query<ITEM, HIST, 6>), dim3(grid), dim3(384), 0, ts, a, qa, win_safe);
+    else if (nw == 8) hipLaunchKernelGGL((k_query<ITEM, HIST, 8>), dim3(grid), dim3(512), 0, ts, a, qa, win_safe);
+    else hipLaunchKernelGGL((k_query<ITEM, HIST, 16>), dim3(grid), dim3(1024), 0, ts, a, qa, win_safe);
+}
+// What the two count commands (frr_visible_pixels, frr_query_pixels) share in front of their counting kernel: the arguments of
+// k_visible_prep -- the window, the unit, the caller's buffer, the pass's id tables and, `bounds`: per item with something to
+// count, the boundary table of the stream the command runs on -- and its launch (the zeros, the boundaries).
+int count_args(frr_ctx *c, const Cmd &cmd, hipStream_t ts, uint32_t ntris, bool bounds, const uint32_t *item_first, VisibleArgs *out)
+{
+    const FrameState &f = c->fs;
+    const GeomSet &S = c->gset[f.geom.set];
+    const int64_t wh = (int64_t)cmd.y1 - cmd.y0;
+    VisibleArgs a;
+    memset(&a, 0, sizeof a);
+    a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
+    a.unit = cmd.vis_unit;
+    a.ntris = ntris;
+    a.tinfo = S.tinfo; a.block_prefix = S.block_prefix;
+    if (bounds) {
+        DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
+        const int rc = ensure(c, tab, (size_t)f.geom.nitems + 1);
+        if (rc != FRR_OK) return rc;
+        a.nitems = (uint32_t)f.geom.nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom.stride; a.bounds = tab;
+    }
+    a.gpar = f.gpar(); a.lane = f.lane;
+    a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    a.tri_id = f.bound.tri_id; a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
+    *out = a;
+    return FRR_OK;
+}
+void launch_count_prep(hipStream_t ts, const VisibleArgs &a)
+{
+    const uint64_t pn = std::max<uint64_t>(a.out_entries, (uint64_t)a.nitems + 1);
+    hipLaunchKernelGGL(k_visible_prep, dim3((uint32_t)std::min<uint64_t>((pn + VIS_WG - 1) / VIS_WG, 2048)), dim3(VIS_WG), 0, ts, a);
+}
+
+int launch_query(frr_ctx *c, Cmd &cmd, const RasterArgs &a, uint32_t grid, const SpanShape sh, GeomSet &S, BinSet &B)
+{
+    FrameState &f = c->fs;
+    int rc;
+    const bool item = cmd.vis_unit == FRR_PER_ITEM;
+    const uint32_t *item_first = nullptr;
+    if (item && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
+    hipStream_t ts = tstream_of(c);
+    frame_stream_dirty(c, ts);
+    VisibleArgs v;
+    if ((rc = count_args(c, cmd, ts, (uint32_t)f.geom.read.ntris, item, item_first, &v)) != FRR_OK) return rc;
+    {
+        ProfScope p(c, KID_VISIBLE, ts);
+        launch_count_prep(ts, v);
+    }
+    QueryArgs qa;
+    qa.unit = cmd.vis_unit; qa.nitems = v.nitems; qa.bounds = v.bounds; qa.out = cmd.vis_out; qa.out_entries = cmd.vis_entries;
+    qa.sweep_all = c->raster_sweep ? 1 : 0;
+    const int win_safe = a.x0 >= -SPAN_SAFE && a.y0 >= -SPAN_SAFE && a.x1 <= SPAN_SAFE && a.y1 <= SPAN_SAFE;
+    // per item the units that fit take the LDS histogram (option visible_lds_bins lowers the threshold: the test hook)
+    const uint32_t cap = c->visible_lds_bins ? c->visible_lds_bins : VIS_LDS_BINS;
+    const bool hist = item && std::min<uint64_t>(f.geom.nitems, cmd.vis_entries) <= cap;
+    if (grid) {
+        ProfScope p(c, KID_RASTER, ts);
+        const int nw = c->raster_sweep ? 4 : sh.nw;
+        if (item && hist) launch_query_nw<true, true>(ts, grid, nw, a, qa, win_safe);
+        else if (item) launch_query_nw<true, false>(ts, grid, nw, a, qa, win_safe);
+        else launch_query_nw<false, false>(ts, grid, nw, a, qa, win_safe);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return tile_launched(c, ts, S, B);
+}
+
 // Loop B (phong.rs:361-381): binning + tile kernel over the latest geometry pass, window (x0,x1) x (y0,y1)
 int exec_raster(frr_ctx *c, Cmd &cmd)
 {
@@ -1056,7 +1138,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
     bool fuse = false;
     if (f.clear.pending) {
         const bool full = x0 == 0 && y0 == 0 && x1 == (int32_t)c->W && y1 == (int32_t)c->H;
-        if (full && !c->raster_sweep) fuse = true; // the tile kernel performs the clear
+        if (full && !c->raster_sweep && !cmd.query) fuse = true; // the tile kernel performs the clear (a query writes no target: never)
         else { int rcs = settle_targets(c); if (rcs != FRR_OK) return rcs; }
     }
     GeomSet &S = c->gset[f.geom.set];
@@ -1151,12 +1233,12 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         {
             ProfScope p(c, KID_BIN_SEG, gs);
             hipLaunchKernelGGL(k_bin_seg, dim3(G + extra), dim3(BIN_WG), lds, gs, a, ltiles, B.bin_matrix, stage_cap,
-                               f.geom.fan_cap, S.block_sums, S.block_prefix, f.geom.nblocks, do_scan, perm_seed);
+                               f.geom.fan_cap, S.block_sums, S.block_prefix, f.geom.nblocks, do_scan | (cmd.query ? 2 : 0), perm_seed);
         }
         // The tile kernel launched below writes every tile's cost -- unless the pass is cancelled (a list overflowed): then
         // the costs stay what an earlier pass (or the zeroing above) left, and the replay of the pass writes them.  Any values
         // give a permutation (build_tile_perm); only how well it orders depends on them.
-        B.cost_known = record; B.cost_key = okey;
+        if (!cmd.query) { B.cost_known = record; B.cost_key = okey; }   // (a query's kernel records no costs: what the set holds stays what it was)
         if (ordered) ++c->ordered_passes;
         f.geom.scan_pending = false;
         f.bpars[f.lane] = q; f.bset = bi;
@@ -1168,7 +1250,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         if ((rc = scan_now(c)) != FRR_OK) return rc;
         const uint32_t bin_grid = (uint32_t)std::min<uint64_t>((f.geom.read.ntris + f.geom.fan_cap + 255) / 256, 2048);
         { ProfScope p(c, KID_BIN_COUNT, gs); hipLaunchKernelGGL(k_bin<false>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom.fan_cap); }
-        { ProfScope p(c, KID_TILE_SCAN, gs); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, gs, a, ntiles); }
+        { ProfScope p(c, KID_TILE_SCAN, gs); if (cmd.query) hipLaunchKernelGGL(k_tile_scan_uncounted, dim3(1), dim3(1024), 0, gs, a, ntiles); else hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, gs, a, ntiles); }
         { ProfScope p(c, KID_BIN_FILL, gs); hipLaunchKernelGGL(k_bin<true>, dim3(bin_grid), dim3(256), 0, gs, a, f.geom.fan_cap); }
     }
     cmd.par = q; cmd.set = bi; cmd.lane = f.lane;
@@ -1184,6 +1266,7 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
         }
     }
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // the tile kernel runs on the targets' stream, after the binning
+    if (cmd.query) return launch_query(c, cmd, a, grid, sh, S, B);
     // frr_frame_wait: the targets' next writer follows what those streams held (a replay re-issues an earlier write: it
     // waits too, but leaves the waits to the write they were asked for)
     hipStream_t ts;
@@ -1374,30 +1457,17 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
     const bool item = cmd.vis_unit == FRR_PER_ITEM;
     const bool cleared = f.draws == 0;   // frr_clear since the pass: the id target holds nothing of it, and its tables are gone
     const uint32_t *item_first = nullptr;
-    if (item && !cleared && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
+    if (item && !cleared && !cmd.query && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
     if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     hipStream_t ts = tstream_of(c);
     // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
     frame_stream_dirty(c, ts);
-    // the units the histogram can meet: decides the path, and whether there is anything to count at all
-    const uint64_t bound = cleared ? 0 : item ? std::min<uint64_t>(f.geom.nitems, cmd.vis_entries) : cmd.vis_entries;
-    const GeomSet &S = c->gset[f.geom.set];
+    // the units the histogram can meet: decides the path, and whether there is anything to count at all (a frr_query_pixels
+    // with nothing to rasterize is this command with nothing to count: the zeros alone)
+    const uint64_t bound = cleared || cmd.query ? 0 : item ? std::min<uint64_t>(f.geom.nitems, cmd.vis_entries) : cmd.vis_entries;
     const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
     VisibleArgs a;
-    memset(&a, 0, sizeof a);
-    a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
-    a.unit = cmd.vis_unit;
-    a.ntris = cleared ? 0u : (uint32_t)f.geom.read.ntris;
-    a.tinfo = S.tinfo; a.block_prefix = S.block_prefix;
-    if (item && bound > 0) {
-        DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
-        if ((rc = ensure(c, tab, (size_t)f.geom.nitems + 1)) != FRR_OK) return rc;
-        a.nitems = (uint32_t)f.geom.nitems; a.item_first = item_first; a.stride = (uint32_t)f.geom.stride; a.bounds = tab;
-    }
-    a.gpar = f.gpar(); a.lane = f.lane;
-    a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
-    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
-    a.tri_id = f.bound.tri_id; a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
+    if ((rc = count_args(c, cmd, ts, cleared ? 0u : (uint32_t)f.geom.read.ntris, item && bound > 0, item_first, &a)) != FRR_OK) return rc;
     const uint32_t cap = c->visible_lds_bins ? c->visible_lds_bins : VIS_LDS_BINS;
     const bool lds = bound <= cap;
     // rows per workgroup: a span is a chain of dependent loads, so what counts is waves in flight -- as many workgroups as
@@ -1406,8 +1476,7 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
     a.rows = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(std::max<uint64_t>((16 + spr - 1) / spr, (uint64_t)(wh + 2047) / 2048), (uint64_t)wh), 1);
     {
         ProfScope p(c, KID_VISIBLE, ts);
-        const uint64_t pn = std::max<uint64_t>(cmd.vis_entries, (uint64_t)a.nitems + 1);
-        hipLaunchKernelGGL(k_visible_prep, dim3((uint32_t)std::min<uint64_t>((pn + VIS_WG - 1) / VIS_WG, 2048)), dim3(VIS_WG), 0, ts, a);
+        launch_count_prep(ts, a);
         if (bound > 0) {
             const dim3 grid((uint32_t)((wh + a.rows - 1) / a.rows)), block(VIS_WG);
             const bool blds = item && a.nitems <= VIS_LDS_BINS;   // the boundaries fit LDS too
@@ -2709,16 +2778,20 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     return host_round_trip(c, new_cmd(c, Cmd::VARY, x0, x1, y0, y1), &Cmd::vary_out, tmp, host_inout, bytes, "varyings");
 }
 
-// argument checks of frr_visible_pixels / frr_visible_pixels_host
-static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
+// argument checks of the count commands, `who`: frr_visible_pixels / frr_visible_pixels_host, frr_query_pixels / frr_query_pixels_host
+static int count_check(frr_ctx *c, const char *who, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
 {
     if (!c) return FRR_ERR_INVALID;
     if (unit != FRR_PER_ITEM && unit != FRR_PER_TRIANGLE) return fail(c, FRR_ERR_INVALID, "unknown frr_visible_unit");
-    if (c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, "frr_visible_pixels before any geometry pass");
+    if (c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, std::string(who) + " before any geometry pass");
     int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
-    if (rc == FRR_OK) rc = need_unfiltered_list(c, "frr_visible_pixels");
+    if (rc == FRR_OK) rc = need_unfiltered_list(c, who);
     if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, buf, out_entries, 0, x1, y0, y1));
     return rc;
+}
+static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
+{
+    return count_check(c, "frr_visible_pixels", unit, x0, x1, y0, y1, buf, out_entries);
 }
 static Cmd visible_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
 {
@@ -2751,6 +2824,53 @@ int frr_visible_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_
     }
     return FRR_OK;
 }
+
+// frr_query_pixels / frr_query_pixels_host: the argument checks are frr_visible_pixels'
+static int query_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
+{
+    int rc = count_check(c, "frr_query_pixels", unit, x0, x1, y0, y1, buf, out_entries);
+    const uint32_t *item_first;   // (a list freed since the pass: refused here, before anything is launched)
+    if (rc == FRR_OK && unit == FRR_PER_ITEM && c->fs.draws != 0) rc = list_item_first(c, &item_first);
+    return rc;
+}
+// the command: a raster command that counts, or -- a frr_clear since the pass, a pass without triangles or without items:
+// nothing to rasterize -- the count command that zeroes the buffer and counts nothing
+static Cmd query_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
+{
+    const FrameState &f = c->fs;
+    const bool nothing = f.draws == 0 || f.geom.read.ntris == 0 || (unit == FRR_PER_ITEM && f.geom.nitems == 0);
+    Cmd cmd = new_cmd(c, nothing ? Cmd::VISIBLE : Cmd::RASTER, x0, x1, y0, y1);
+    cmd.query = true; cmd.ps = FRR_PS_DEPTH; cmd.count_frags = false;
+    cmd.vis_unit = unit; cmd.vis_out = dev_out; cmd.vis_entries = out_entries;
+    return cmd;
+}
+
+int frr_query_pixels(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_u32, uint64_t out_entries)
+{
+    const int rc = query_check(c, unit, x0, x1, y0, y1, dev_out_u32, out_entries);
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return exec_cmd(c, query_cmd(c, unit, x0, x1, y0, y1, (uint32_t *)dev_out_u32, out_entries));
+}
+
+int frr_query_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *host_out, uint64_t out_entries, uint64_t *nunits)
+{
+    int rc = query_check(c, unit, x0, x1, y0, y1, host_out, out_entries);
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint32_t> tmp;
+    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
+    rc = host_round_trip(c, query_cmd(c, unit, x0, x1, y0, y1, nullptr, out_entries), &Cmd::vis_out, tmp, host_out, (size_t)out_entries * sizeof(uint32_t), "counts");
+    if (rc != FRR_OK) return rc;
+    if (nunits) {
+        const FrameState &f = c->fs;
+        const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
+        *nunits = unit == FRR_PER_ITEM ? f.geom.nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom.read.ntris ? gt.n_emit : 0u);
+    }
+    return FRR_OK;
+}
+
+int frr_host_fragment_passes(float rhw, float depth) { return fragment_passes(rhw, depth) ? 1 : 0; }
 
 int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                                 const uint32_t *bounds, uint64_t nunits, uint32_t *out, uint64_t out_entries)

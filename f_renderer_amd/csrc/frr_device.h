@@ -335,7 +335,9 @@ __device__ __forceinline__ void totals_for_frame(Counters *cnt, Lane &L, uint32_
 // the binning launch's bookkeeping (one thread).  The OTHER table belongs to the previous raster pass, whose binning has
 // drained (same stream): its total is folded and zeroed for the pass after this one.  (Its ent_cursor may still be in use
 // by that pass's tile kernel on the other stream: every pass zeroes its OWN before its tile kernel starts.)
-__device__ __forceinline__ void bin_bookkeeping(Counters *cnt, int lane, int bpar, uint32_t frame_no)
+// counted = false: the binning of a frr_query_pixels, whose entries are no part of frr_stats::bin_entries -- its table belongs to
+// no frame, so neither the fold above nor frr_get_stats takes its total.
+__device__ __forceinline__ void bin_bookkeeping(Counters *cnt, int lane, int bpar, uint32_t frame_no, bool counted = true)
 {
     Lane &L = cnt->lane[lane];
     totals_for_frame(cnt, L, frame_no);
@@ -344,7 +346,7 @@ __device__ __forceinline__ void bin_bookkeeping(Counters *cnt, int lane, int bpa
     o.seg_total = 0ull;
     o.frame_no = SEQ_NONE;
     L.btab[bpar].ent_cursor = 0u;
-    L.btab[bpar].frame_no = frame_no;
+    L.btab[bpar].frame_no = counted ? frame_no : SEQ_NONE;
 }
 
 // ---- glam pieces used by the shader table -------------------------------------

@@ -1035,7 +1035,9 @@ __global__ __launch_bounds__(256) void k_bin(RasterArgs a, uint32_t fan_cap)
 
 // exclusive scan of the tile counts (single workgroup); zeroes the counts for the next draw and
 // the fill cursors; publishes bin_total and the bin-capacity overflow flag.
-__global__ __launch_bounds__(1024) void k_tile_scan(RasterArgs a, uint32_t ntiles)
+// (counted = false: the binning of a frr_query_pixels, whose entries are no part of frr_stats::bin_entries -- k_tile_scan_uncounted,
+// a kernel of its own so that the draw path launches what it always launched)
+__device__ __forceinline__ void tile_scan(const RasterArgs &a, uint32_t ntiles, bool counted)
 {
     __shared__ uint32_t s_w[16];
     __shared__ uint32_t s_carry;
@@ -1065,9 +1067,11 @@ __global__ __launch_bounds__(1024) void k_tile_scan(RasterArgs a, uint32_t ntile
         L.bin_total = total;
         totals_for_frame(a.cnt, L, a.frame_no);
         if (total > a.bin_cap) seq_fail(a.cnt, a.seq, a.epoch, 2u);
-        else L.tot_bin_entries += total;
+        else if (counted) L.tot_bin_entries += total;
     }
 }
+__global__ __launch_bounds__(1024) void k_tile_scan(RasterArgs a, uint32_t ntiles) { tile_scan(a, ntiles, true); }
+__global__ __launch_bounds__(1024) void k_tile_scan_uncounted(RasterArgs a, uint32_t ntiles) { tile_scan(a, ntiles, false); }
 
 // ---------------------------------------------------------------------------------------------
 // Heavy-first tile order (option tile_order).  The tile kernel's blocks are dealt round-robin to the 8 XCDs and
@@ -1140,9 +1144,11 @@ __device__ __forceinline__ void build_tile_perm(const uint32_t *cost, uint32_t *
 // ---------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(BIN_WG) void k_bin_seg(RasterArgs a, uint32_t ntiles, uint32_t *__restrict__ seg,
-                                                    uint32_t stage_cap, uint32_t fan_cap, const uint32_t *block_sums, uint32_t *block_prefix, uint32_t nblocks, int do_scan,
+                                                    uint32_t stage_cap, uint32_t fan_cap, const uint32_t *block_sums, uint32_t *block_prefix, uint32_t nblocks, int scan_flags,
                                                     uint32_t perm_seed)
 {
+    const int do_scan = scan_flags & 1;            // bit 0: scan the geometry kernel's block sums; bit 1: the entries are not counted (bin_bookkeeping)
+    const bool counted = (scan_flags & 2) == 0;
     const uint32_t first_bad = seq_first_bad(a.cnt);   // (tested once the histogram is zeroed: nothing is written before)
     extern __shared__ __attribute__((aligned(16))) uint32_t s_hist[]; // [ntiles], then the staging records
     uint4 *s_stage = reinterpret_cast<uint4 *>(s_hist + ((ntiles + 3u) & ~3u));
@@ -1161,7 +1167,7 @@ __global__ __launch_bounds__(BIN_WG) void k_bin_seg(RasterArgs a, uint32_t ntile
         if (a.tile_perm) build_tile_perm(a.tile_cost, a.tile_perm, ntiles, perm_seed, s_hist);
         return;
     }
-    if (g == 0 && threadIdx.x == 0) bin_bookkeeping(a.cnt, a.lane, a.bpar, a.frame_no);
+    if (g == 0 && threadIdx.x == 0) bin_bookkeeping(a.cnt, a.lane, a.bpar, a.frame_no, counted);
     __syncthreads();
     // a workgroup's chunk: a range of geometry blocks (their dense entries) and a range of the used fan entries
     const FanMap fm = fan_map(&a.cnt->lane[a.lane].gtab[a.gpar], fan_cap);

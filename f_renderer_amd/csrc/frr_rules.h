@@ -132,6 +132,11 @@ inline Rule buffer_rule(BufferUse use, const void *buf, uint64_t entries, int K,
 #endif
 FRR_RULE_HD inline bool item_kept(uint32_t value, uint32_t min_value) { return value >= min_value; }
 
+// ---- the depth test ----------------------------------------------------------------------------------------------------
+// A fragment passes iff `rhw < depth` is false (renderer.rs:363): a tie passes, and so does everything where either side is
+// NaN.  The one comparison frr_query_pixels' kernel (frr_query.h) and the CPU test share.
+FRR_RULE_HD inline bool fragment_passes(float rhw, float depth) { return !(rhw < depth); }
+
 inline Rule keep_rule(const void *keep, uint64_t keep_entries, uint64_t nitems)
 {
     if ((!keep && nitems > 0) || ((uintptr_t)keep & 3u)) return {FRR_ERR_INVALID, "keep buffer is NULL or not 4-byte aligned"};

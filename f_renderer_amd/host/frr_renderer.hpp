@@ -530,6 +530,26 @@ public:
         return out;
     }
     std::vector<uint32_t> visible_pixels(int unit) { return visible_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // The occlusion query (include/frr.h: frr_query_pixels): how many fragments of each unit of the latest geometry pass would
+    // pass the depth test against the depth target as it stands -- nothing is drawn.  Device memory of `entries` u32, every one
+    // written; a command on the frame's stream, no host wait.  The buffer is a keep buffer for draw_list_if as it is: that
+    // pass is already ordered behind the query.
+    void query_pixels(int unit, void *dev_out_u32, uint64_t entries, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        check(frr_query_pixels(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, dev_out_u32, entries));
+    }
+    void query_pixels(int unit, void *dev_out_u32, uint64_t entries) { query_pixels(unit, dev_out_u32, entries, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // the same on the host (a synchronisation point): the counts of all n units
+    std::vector<uint32_t> query_pixels(int unit, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        uint64_t n = 0;
+        uint32_t probe = 0;   // (one entry is enough to ask for n)
+        check(frr_query_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, &probe, 1, &n));
+        std::vector<uint32_t> out((size_t)n, probe);
+        if (n > 1) check(frr_query_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, out.data(), n, &n));
+        return out;
+    }
+    std::vector<uint32_t> query_pixels(int unit) { return query_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream
     // waits for every frame issued so far; frame_wait -- the next write of the frame targets waits for what the stream holds now

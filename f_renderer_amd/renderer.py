@@ -738,6 +738,32 @@ class Renderer:
             self._check(self._lib.frr_visible_pixels_host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
         return out
 
+    def query_pixels(self, unit="item", window=None, out_ptr=None, entries=None):
+        """The occlusion query (frr_query_pixels): how many fragments of each unit of the latest geometry pass -- unit="item"
+        or "triangle", as for visible_pixels -- would pass the depth test against the depth target as it stands, in
+        window = (x0, x1, y0, y1) (default: the frame).  Nothing is drawn.  With `out_ptr` (device memory of `entries`
+        uint32) it is a command on the frame's stream with no host wait and returns nothing: the buffer can be the keep
+        buffer of a later draw_list_if as it is.  Without `out_ptr` it is the host form (a synchronisation point) and
+        returns a uint32 array of the n counts, or of `entries` of them."""
+        u = {"item": N.PER_ITEM, "triangle": N.PER_TRIANGLE}.get(unit, unit)
+        win = tuple(int(v) for v in (window or (0, self.width, 0, self.height)))
+        if out_ptr is not None:
+            if entries is None:
+                raise FrrError(N.FRR_ERR_INVALID, "query_pixels: the device form needs the buffer's entries")
+            self._check(self._lib.frr_query_pixels(self._ctx, int(u), *win, C.c_void_p(out_ptr), int(entries)))
+            return None
+        n = C.c_uint64()
+        if entries is None:   # n first (one entry is enough to ask), then the counts
+            probe = np.zeros(1, np.uint32)
+            self._check(self._lib.frr_query_pixels_host(self._ctx, int(u), *win, probe.ctypes.data, 1, C.byref(n)))
+            entries = int(n.value)
+            if entries <= 1:
+                return probe[:entries]
+        out = np.zeros(int(entries), np.uint32)
+        if out.size:
+            self._check(self._lib.frr_query_pixels_host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
     def frame_fence(self, stream=None):
         """`stream` (a hipStream_t handle, e.g. torch's stream.cuda_stream; None = the ctx's stream) waits for every frame
         issued so far -- no host wait (frr_frame_fence; option bound_targets_in_flight)."""

@@ -158,6 +158,27 @@ def checker_texture(size=1024, cell=32):
     return np.ascontiguousarray(np.stack([r, g, b, a], axis=2))
 
 
+def box_proxy(tris, inflate=0.0):
+    """The 12 triangles of the object-space bounding box of a pos3/uv2/normal3 mesh [n, 3, 8], in the same layout (uv and
+    normal zero), grown by `inflate` on every side: the cheap stand-in of an item for an occlusion query
+    (Renderer.query_pixels).  A proxy list is the item list with each mesh replaced by its box, under the same matrices.
+    The box is conservative only up to the vertex snap to integer pixels and the rounding of rhw: inflate it by about a
+    pixel's worth.  An empty mesh has no box: [0, 3, 8]."""
+    t = np.asarray(tris, np.float32).reshape(-1, 3, 8)
+    if t.shape[0] == 0:
+        return np.zeros((0, 3, 8), np.float32)
+    p = t[:, :, :3].reshape(-1, 3)
+    lo = p.min(axis=0) - np.float32(inflate)
+    hi = p.max(axis=0) + np.float32(inflate)
+    c = np.array([[(hi if (i >> k) & 1 else lo)[k] for k in range(3)] for i in range(8)], np.float32)   # corner i: bit k picks hi
+    quads = ((0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3))
+    out = np.zeros((12, 3, 8), np.float32)
+    for q, (a, b, d, e) in enumerate(quads):
+        out[2 * q, :, :3] = c[[a, b, d]]
+        out[2 * q + 1, :, :3] = c[[a, d, e]]
+    return out
+
+
 def demo_camera(width, height):
     """(eye, at, up, fovy, aspect, zn, zf): camera of SURVEY §8d config 2/3, projection as phong.rs:164."""
     return (0.0, 1.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), math.pi * 0.25, float(width) / float(height), 0.1, 100.0

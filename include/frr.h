@@ -699,6 +699,57 @@ int frr_visible_pixels(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y
 int frr_visible_pixels_host(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                             uint32_t *host_out, uint64_t out_entries, uint64_t *nunits);
 
+/* ---- occlusion queries ------------------------------------------------------------------------- */
+/* Would the triangles of a pass be visible against the depth that is there now?  Loop B (renderer.rs:269-384) over the
+ * triangles of the LATEST geometry pass with every store taken out: the fragments that pass the depth test are counted,
+ * nothing is drawn.  (frr_visible_pixels counts what a draw left behind; this asks before anything is drawn -- of a cheap
+ * proxy of an object, or of the object itself -- and its counts are a keep buffer for frr_draw_list_if.)
+ *   fragment  Setup triangle t of the pass has a fragment at pixel (cx, cy) of the window under exactly the conditions of the
+ *             reference, and of frr_raster of the same pass in the same window: inside the triangle's box clamped to the
+ *             window (:285-298), accepted by the three wrapping-i32 edge tests with the top-left rule (:329-341), and
+ *             a + b + c != 0 (:351-354).
+ *   test      The fragment passes iff `rhw < depth[i]` is false (:363), i = (cy - y0) * x1 + (cx - x0), rhw that of :360 in the
+ *             tile kernel's arithmetic, depth[i] the current frame's depth target at the command's place in the stream.  A
+ *             NaN rhw passes, a NaN depth lets everything pass, rhw == depth passes.
+ * The query's own fragments store nothing, so EVERY fragment meets the same stored value -- unlike the reference's loop, where
+ * an earlier triangle of the pass raises the depth for a later one.  Said the other way round: the count of triangle t is the
+ * number of entries rasterization(t) ALONE changes on a copy of the depth buffer.
+ * Units, n and the every-entry-is-written rule are frr_visible_pixels': FRR_PER_ITEM out[k] = the sum over the triangles of
+ * item k of the latest pass (the items frr_geometry_item_ranges reports); FRR_PER_TRIANGLE out[e] for the frame-global
+ * emission index e, indices below the pass's first id get 0.  Unit k < min(n, out_entries) gets its count, entries at and
+ * beyond n get 0, a unit >= out_entries is counted nowhere.
+ * Colour, depth and ids are untouched, and so is every field of frr_stats (frag_covered and frag_nan are not counted) except
+ * `replays`, where a replay happens.  The counts are sums of integers: two runs give the same bytes.
+ * frr_query_pixels: a command on the current frame's stream like frr_visible_pixels: behind the draws issued so far and in
+ * front of those issued after it; it settles a pending frr_clear first (and is never fused with it), reads the current target
+ * set (own or caller-bound, one or two frames in flight) and waits for nothing on the host beyond what frr_raster waits for.
+ * The caller orders its own reads of dev_out_u32 with frr_frame_fence or frr_sync; a later frr_draw_list_if / frr_geometry_list_if
+ * of this ctx that names the buffer is already ordered behind it (the keep buffer is read behind every command issued on the
+ * ctx so far).
+ * Work lists.  The query bins its triangles exactly as frr_raster of the same pass in the same window does: it is logged,
+ * verified inside the call and replayed by frr_raster's rules, and shares the proof of that raster signature (a pass behind a
+ * *_list_if geometry is never taken as proven).  A replay zeroes and counts again; behind a failed command the query writes
+ * nothing, not even the zeros, so dev_out_u32 stays allocated until the next synchronisation point or frr_clear.  It closes
+ * an open pass in the sense of the frr_frame_fence comment.
+ * frr_geometry*; frr_query_pixels; frr_raster on one pass is valid: the raster draws what frr_draw* would have drawn.  A pass
+ * that is only queried is an ordinary geometry pass that nothing rasterized (its ids, tris_in and tris_setup are taken).
+ * On a partitioned ctx only the tile rows this rank owns are counted, so the ranks' counts add up to the unpartitioned ones;
+ * after a frr_draw* that filtered the setup list the call fails with FRR_ERR_INVALID, where frr_visible_pixels fails.
+ * After a frr_clear since the pass, for an empty pass and for a pass without items: FRR_OK and zeros.
+ * Option "visible_lds_bins" is this command's test hook too: per item, more units than v add to global memory directly
+ * instead of through the LDS histogram (per triangle the adds always go to global memory, one per tile and triangle).
+ * frr_query_pixels_host: the same through a temporary device buffer into host memory; a synchronisation point.  *nunits
+ * (optional) receives n.
+ * Errors: those of frr_visible_pixels -- FRR_ERR_UNSUPPORTED for x0 < 0 (one triangle could hit an entry twice), FRR_ERR_INVALID
+ * for the other window rules, an unknown unit, a NULL or not 4-byte-aligned buffer with out_entries > 0, a call before any
+ * geometry pass.  A refused call leaves the ctx drawing.  out_entries == 0 (after these checks): FRR_OK, nothing happens. */
+int frr_query_pixels(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                     void *dev_out_u32, uint64_t out_entries);
+int frr_query_pixels_host(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                          uint32_t *host_out, uint64_t out_entries, uint64_t *nunits);
+/* host build of the query's depth test (cf. frr_host_list_item): 1 iff a fragment of that rhw passes against that depth */
+int frr_host_fragment_passes(float rhw, float depth);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to

@@ -124,6 +124,8 @@ pub mod ffi {
         // unit: 0 = FRR_PER_ITEM, 1 = FRR_PER_TRIANGLE
         pub fn frr_visible_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
         pub fn frr_visible_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
+        pub fn frr_query_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
+        pub fn frr_query_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
         pub fn frr_host_list_item(first: *const u32, ntris: *const u32, nitems: u64, t: u32) -> i64;
         // per-item materials: one shade of all the items of the latest geometry pass, each under its own frr_material
         pub fn frr_materials_upload(ctx: *mut frr_ctx, mats: *const frr_material, n: u64, materials_out: *mut c_int) -> c_int;
@@ -247,6 +249,25 @@ impl Renderer {
     /// `dev_out` is device memory of `entries` u32 that stays allocated until the next synchronisation point or `clear`.
     pub unsafe fn visible_pixels_device(&mut self, per_triangle: bool, width_range: (i32, i32), height_range: (i32, i32), dev_out: *mut c_void, entries: u64) -> Result<(), Error> {
         self.check(ffi::frr_visible_pixels(self.ctx, per_triangle as c_int, width_range.0, width_range.1, height_range.0, height_range.1, dev_out, entries))
+    }
+
+    /// frr_query_pixels_host: the occlusion query -- how many fragments of each unit of the latest geometry pass would pass the
+    /// depth test against the depth target as it stands; nothing is drawn.  Every entry of `out` is written; returns the number
+    /// of units n.  A synchronisation point.
+    pub fn query_pixels(&mut self, per_triangle: bool, width_range: (i32, i32), height_range: (i32, i32), out: &mut [u32]) -> Result<u64, Error> {
+        let mut n = 0u64;
+        self.check(unsafe {
+            ffi::frr_query_pixels_host(self.ctx, per_triangle as c_int, width_range.0, width_range.1, height_range.0, height_range.1,
+                                       out.as_mut_ptr(), out.len() as u64, &mut n)
+        })?;
+        Ok(n)
+    }
+    /// frr_query_pixels: the same into device memory, as a command on the frame's stream with no host wait; the buffer can be
+    /// the keep buffer of a later predicated list pass as it is.
+    /// # Safety
+    /// `dev_out` is device memory of `entries` u32 that stays allocated until the next synchronisation point or `clear`.
+    pub unsafe fn query_pixels_device(&mut self, per_triangle: bool, width_range: (i32, i32), height_range: (i32, i32), dev_out: *mut c_void, entries: u64) -> Result<(), Error> {
+        self.check(ffi::frr_query_pixels(self.ctx, per_triangle as c_int, width_range.0, width_range.1, height_range.0, height_range.1, dev_out, entries))
     }
 
     /// `Vec<[VSInput;3]>` (phong.rs:187-205) -> device
