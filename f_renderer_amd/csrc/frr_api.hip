@@ -259,6 +259,11 @@ struct FrameState {
 
 struct Cmd {
     enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE, SHADE_ITEMS } kind;
+    // GEOM and RASTER own device tables (GeomTab / BinTab), which finish() resets before it replays them.  The other five run
+    // behind a geometry pass, own none, and are replayed by running them again; what tells them apart is two traits -- does the
+    // command read the latest pass's tables (VARY, VISIBLE, SHADE_ITEMS, a wireframe LINES), and does it write a target
+    // (LINES, SHADE, SHADE_ITEMS): cmd_settle / cmd_stream / cmd_done
+    bool owns_table() const { return kind == GEOM || kind == RASTER; }
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
     DevUniforms duni;          // uniforms at the time of the call
@@ -346,7 +351,7 @@ struct frr_ctx {
     uint32_t join_epoch = 1, joined_g = 0;   // (joined_g: gstream's; a frame stream's is FrameStream::joined)
     // command log since the last synchronisation point / frr_clear (finish(): replay)
     std::vector<Cmd> log;
-    // frr_shade_varyings_host: the device copies of the callers' buffers, one per logged command that reads one (Cmd::shade_in
+    // shade_from_host (frr_shade_varyings_host, frr_shade_items_host): the device copies of the callers' buffers, one per logged command that reads one (Cmd::shade_in
     // is a view of it); freed whenever the log is (drop_log)
     std::vector<DevBuf<float>> shade_tmp;
     uint32_t next_seq = 1, epoch = 1;
@@ -838,16 +843,6 @@ void frame_stream_dirty(frr_ctx *c, hipStream_t ts)
 }
 // which of the buffers kept per stream that can carry target work (frr_ctx::line_owner, vis_bounds) goes with `ts`
 int stream_slot(const frr_ctx *c, hipStream_t ts) { return ts == c->stream ? 0 : ts == c->tstream[0].st ? 1 : 2; }
-// the command has read the tables of the latest geometry pass on `ts`: the next pass in this lane, which zeroes the fan
-// cursors and may overwrite the workspace, waits for it (frr_ctx::wire_reader); finish() finds the tables it read in cmd
-void tables_read(frr_ctx *c, Cmd &cmd, hipStream_t ts)
-{
-    const FrameState &f = c->fs;
-    ReaderFence &wr = c->wire_reader[f.lane];
-    wr.pending = true; wr.stream = ts; wr.recorded = false;
-    cmd.par = f.gpar(); cmd.set = f.geom.set; cmd.lane = f.lane;
-}
-
 // Every launch that writes the frame targets goes on the stream this returns (*ts, the targets' stream).  The write follows
 // every stream of a pending frr_frame_wait, and its stream, if a frame stream, is dirty until fence_stream joins it.
 // `consume`: the write was issued after the latest frr_frame_wait (the one the waits are for), so later writes follow it
@@ -910,6 +905,46 @@ int settle(frr_ctx *c)
     HIP_TRY(c, hipSetDevice(c->device));
     { int rcs = scan_now(c); if (rcs != FRR_OK) return rcs; }   // n_emit of the latest pass (statistics, setup read-back)
     return settle_targets(c);
+}
+
+// ---- what the commands that own no device table share (Cmd::owns_table) ---------------------------------------------
+// Each runs behind a geometry pass, cannot fail on the device, and is replayed by running it again in its place: behind a
+// failed command it writes nothing (seq_cancelled).  Two traits say how it is ordered.  reads_pass: it reads the tables of
+// the latest geometry pass, on the device (no host wait).  writes_target: it writes a frame target.  An executor calls
+// cmd_settle and cmd_stream, launches on the stream it was given, and calls cmd_done; its host-only steps that can refuse
+// stand where they stood among these.
+
+// What the command looks at is there: n_emit and the block prefix of the pass (a fan space that was too small is flagged
+// here, before the tables are read: the command is then cancelled, and replayed), and the targets behind a pending frr_clear.
+int cmd_settle(frr_ctx *c, bool reads_pass)
+{
+    int rc;
+    if (reads_pass && (rc = scan_now(c)) != FRR_OK) return rc;
+    return c->fs.clear.pending ? settle_targets(c) : FRR_OK;
+}
+// *ts: the stream its launches go on, which is the targets' stream.  A reader follows the pass's geometry there, as a tile
+// kernel does.  A writer goes through target_write: it follows the streams of pending frr_frame_wait calls and, issued by
+// the caller rather than by a replay, consumes them.  A command that writes no target has no business with those events
+// (the caller's buffer is fenced like a target); it takes the same stream and, if that is a frame stream, leaves it dirty.
+int cmd_stream(frr_ctx *c, bool reads_pass, bool writes_target, hipStream_t *ts)
+{
+    int rc;
+    if (reads_pass && (rc = tstream_wait_gstream(c)) != FRR_OK) return rc;
+    if (writes_target) return target_write(c, !c->in_replay, ts);
+    *ts = tstream_of(c);
+    frame_stream_dirty(c, *ts);
+    return FRR_OK;
+}
+// The launches are on `ts`.  A reader has read the pass's tables there: the next pass in this lane, which zeroes the fan
+// cursors and may overwrite the workspace, waits for it (frr_ctx::wire_reader), and finish() finds the tables it read in cmd.
+void cmd_done(frr_ctx *c, Cmd &cmd, bool reads_pass, hipStream_t ts)
+{
+    const FrameState &f = c->fs;
+    cmd.lane = f.lane;
+    if (!reads_pass) return;
+    ReaderFence &wr = c->wire_reader[f.lane];
+    wr.pending = true; wr.stream = ts; wr.recorded = false;
+    cmd.par = f.gpar(); cmd.set = f.geom.set;
 }
 
 // ---- the two commands ------------------------------------------------------------------------------------------------
@@ -1049,8 +1084,8 @@ int exec_geometry(frr_ctx *c, Cmd &cmd)
 }
 
 // frr_query_pixels behind exec_raster's binning: k_visible_prep zeroes the caller's buffer and builds the item boundaries,
-// k_query (frr_query.h) counts in the tile kernel's place.  No target is written, so the launches take the frame's stream as
-// exec_visible does: pending frr_frame_wait events are not their business, the caller's buffer is fenced like a target.
+// k_query (frr_query.h) counts in the tile kernel's place.  No target is written, so the launches take the stream cmd_stream
+// gives a command that writes none (exec_raster has ordered it behind the pass's geometry and binning).
 int list_item_first(frr_ctx *c, const uint32_t **item_first);
 template <bool ITEM, bool HIST> void launch_query_nw(hipStream_t ts, uint32_t grid, int nw, const RasterArgs &a, const QueryArgs &qa, int win_safe)
 {
@@ -1062,7 +1097,8 @@ template <bool ITEM, bool HIST> void launch_query_nw(hipStream_t ts, uint32_t gr
 }
 // What the two count commands (frr_visible_pixels, frr_query_pixels) share in front of their counting kernel: the arguments of
 // k_visible_prep -- the window, the unit, the caller's buffer, the pass's id tables and, `bounds`: per item with something to
-// count, the boundary table of the stream the command runs on -- and its launch (the zeros, the boundaries).
+// count, the boundary table of the stream the command runs on -- and its launch (the zeros, the boundaries).  The items form
+// of exec_shade takes the boundaries alone the same way.
 int count_args(frr_ctx *c, const Cmd &cmd, hipStream_t ts, uint32_t ntris, bool bounds, const uint32_t *item_first, VisibleArgs *out)
 {
     const FrameState &f = c->fs;
@@ -1100,8 +1136,8 @@ int launch_query(frr_ctx *c, Cmd &cmd, const RasterArgs &a, uint32_t grid, const
     const bool item = cmd.vis_unit == FRR_PER_ITEM;
     const uint32_t *item_first = nullptr;
     if (item && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
-    hipStream_t ts = tstream_of(c);
-    frame_stream_dirty(c, ts);
+    hipStream_t ts;
+    if ((rc = cmd_stream(c, false, false, &ts)) != FRR_OK) return rc;
     VisibleArgs v;
     if ((rc = count_args(c, cmd, ts, (uint32_t)f.geom.read.ntris, item, item_first, &v)) != FRR_OK) return rc;
     {
@@ -1323,15 +1359,13 @@ int exec_raster(frr_ctx *c, Cmd &cmd)
 }
 
 // FrameBuffer::draw_line (renderer.rs:540-588) for every segment of a list, in list order, or for the edges of the latest
-// geometry pass's triangles: colour only, on the targets' stream, ordered like a tile kernel.  It cannot fail on the
-// device and has nothing in the device tables to reset, so a replay simply runs it again in its place.
+// geometry pass's triangles: colour only.  It writes a target; the wireframe also reads the pass.
 int exec_lines(frr_ctx *c, Cmd &cmd)
 {
     FrameState &f = c->fs;
     const bool wire = cmd.lines < 0;
     int rc;
-    if (wire && (rc = scan_now(c)) != FRR_OK) return rc;   // a fan space that was too small is flagged before the edges are read (they are then cancelled, and replayed)
-    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if ((rc = cmd_settle(c, wire)) != FRR_OK) return rc;
     LinesArgs a;
     memset(&a, 0, sizeof a);
     uint32_t batches;
@@ -1340,14 +1374,13 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
         a.recs = S.recs; a.tinfo = S.tinfo; a.fan_cap = f.geom.fan_cap; a.wire_rgba = cmd.wire_rgba;
         a.gpar = f.gpar(); a.lane = f.lane;
         batches = (uint32_t)((3ull * (f.geom.read.ntris + f.geom.fan_cap) + 63) / 64);
-        if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
     } else {
         const Lines &L = c->lines[cmd.lines];
         a.xyxy = L.xyxy; a.rgba = L.rgba; a.nlines = (uint32_t)L.n;
         batches = (uint32_t)((L.n + 63) / 64);
     }
     hipStream_t ts;
-    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
+    if ((rc = cmd_stream(c, wire, true, &ts)) != FRR_OK) return rc;
     // (a device-bound list needs no join of `ts` with the caller's stream: frr_lines_bind_device has waited on the host for
     // that stream, behind whatever wrote the list)
     DevBuf<uint32_t> &owner = c->line_owner[stream_slot(c, ts)];
@@ -1374,29 +1407,24 @@ int exec_lines(frr_ctx *c, Cmd &cmd)
         else hipLaunchKernelGGL(k_lines_paint<false>, grid, block, 0, ts, a);
     }
     HIP_TRY(c, hipGetLastError());
-    if (wire) tables_read(c, cmd, ts); else cmd.lane = f.lane;
+    cmd_done(c, cmd, wire, ts);
     return FRR_OK;
 }
 
 // frr_resolve_varyings: the interpolated varyings (renderer.rs:368-378) of every pixel of the window that a triangle of the
-// latest geometry pass owns, into the caller's buffer (frr_varyings.h).  On the targets' stream, ordered like a tile kernel
-// behind the pass's geometry; it reads the pass's tables on the device (no host wait), cannot fail there and owns no
-// device table, so a replay runs it again in its place -- behind a failed command it writes nothing (seq_cancelled).
+// latest geometry pass owns, into the caller's buffer (frr_varyings.h).  It reads the pass and writes no target.
 int exec_vary(frr_ctx *c, Cmd &cmd)
 {
     FrameState &f = c->fs;
     int rc;
-    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass (a fan space that was too small is flagged here)
-    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if ((rc = cmd_settle(c, true)) != FRR_OK) return rc;
     GeomSet &S = c->gset[f.geom.set];
     const int par = f.gpar();
     bool fresh_table;
     if ((rc = ensure(c, S.vslot[par], S.recs.cap(), &fresh_table)) != FRR_OK) return rc;
     if (fresh_table) S.vslot_seq[par] = 0;   // new memory: no table
-    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
-    hipStream_t ts = tstream_of(c);
-    // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
-    frame_stream_dirty(c, ts);
+    hipStream_t ts;
+    if ((rc = cmd_stream(c, true, false, &ts)) != FRR_OK) return rc;
     if (S.vslot_stream[par] && S.vslot_stream[par] != ts) {   // the table's previous resolve ran on another stream: after it
         HIP_TRY(c, hipEventRecord(c->ev_join, S.vslot_stream[par]));
         HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_join, 0));
@@ -1429,7 +1457,7 @@ int exec_vary(frr_ctx *c, Cmd &cmd)
     else if (vec) hipLaunchKernelGGL((k_vary_resolve<0, true>), grid, block, 0, ts, a);   // user shaders: K at run time
     else hipLaunchKernelGGL((k_vary_resolve<0, false>), grid, block, 0, ts, a);
     HIP_TRY(c, hipGetLastError());
-    tables_read(c, cmd, ts);   // like a wireframe: the pass's fan cursors and its workspace
+    cmd_done(c, cmd, true, ts);
     return FRR_OK;
 }
 
@@ -1445,23 +1473,18 @@ int list_item_first(frr_ctx *c, const uint32_t **item_first)
 }
 
 // frr_visible_pixels: the triangle-id target of a window as counts per item of the latest geometry pass, or per triangle of
-// the frame (frr_visible.h).  Ordered like frr_resolve_varyings: on the targets' stream behind the pass's geometry, it reads
-// the pass's tables on the device (no host wait), cannot fail there and owns no device table, so a replay runs it again in
-// its place -- behind a failed command it writes nothing, not even the zeros (seq_cancelled).
+// the frame (frr_visible.h).  It reads the pass and writes no target; behind a failed command not even the zeros are written.
 int exec_visible(frr_ctx *c, Cmd &cmd)
 {
     FrameState &f = c->fs;
     int rc;
-    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass
-    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
+    if ((rc = cmd_settle(c, true)) != FRR_OK) return rc;
     const bool item = cmd.vis_unit == FRR_PER_ITEM;
     const bool cleared = f.draws == 0;   // frr_clear since the pass: the id target holds nothing of it, and its tables are gone
     const uint32_t *item_first = nullptr;
     if (item && !cleared && !cmd.query && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
-    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
-    hipStream_t ts = tstream_of(c);
-    // (no target is written, so pending frr_frame_wait events are not its business; the caller's buffer is fenced like a target)
-    frame_stream_dirty(c, ts);
+    hipStream_t ts;
+    if ((rc = cmd_stream(c, true, false, &ts)) != FRR_OK) return rc;
     // the units the histogram can meet: decides the path, and whether there is anything to count at all (a frr_query_pixels
     // with nothing to rasterize is this command with nothing to count: the zeros alone)
     const uint64_t bound = cleared || cmd.query ? 0 : item ? std::min<uint64_t>(f.geom.nitems, cmd.vis_entries) : cmd.vis_entries;
@@ -1489,119 +1512,81 @@ int exec_visible(frr_ctx *c, Cmd &cmd)
         }
     }
     HIP_TRY(c, hipGetLastError());
-    tables_read(c, cmd, ts);   // like a resolve
+    cmd_done(c, cmd, true, ts);
     return FRR_OK;
 }
 
-// frr_shade_varyings: a pixel shader over a buffer of varyings into the colour target (frr_shade.h).  It writes a target, so it
-// is ordered like a line list: on the targets' stream, behind a pending frr_clear and the streams of pending frr_frame_wait
-// calls (the caller's writes of the buffer).  It reads nothing of a geometry pass, cannot fail on the device and owns no
-// device table, so a replay runs it again in its place -- behind a failed command it writes nothing (seq_cancelled).
-template <int K, int PS> void launch_shade(hipStream_t ts, dim3 grid, const ShadeArgs &a, const DevUniforms &du, bool vec)
+// frr_shade_varyings, frr_shade_items: a pixel shader over a buffer of varyings into the colour target (frr_shade.h), under
+// the uniforms of the call (k_shade_vary, over a range of triangle ids) or under the material of each pixel's item
+// (k_shade_items).  Both write a target; the items form also reads the pass -- it finds a pixel's item in the boundaries a
+// per-item count builds, built here the same way, into the same per-stream table -- and a replay reads the material table
+// as it is then.
+ShadeArgs shade_args(const frr_ctx *c, const Cmd &cmd)
 {
-    if constexpr (K > 0 && K % 4 == 0) { if (vec) { hipLaunchKernelGGL((k_shade_vary<K, PS, true>), grid, dim3(SHADE_WG), 0, ts, a, du); return; } }
-    hipLaunchKernelGGL((k_shade_vary<K, PS, false>), grid, dim3(SHADE_WG), 0, ts, a, du);
-}
-int exec_shade(frr_ctx *c, Cmd &cmd)
-{
-    FrameState &f = c->fs;
-    int rc;
-    const UserModule *um = nullptr;
-    if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
-    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
-    hipStream_t ts;
-    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
-    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    const FrameState &f = c->fs;
+    const int64_t wh = (int64_t)cmd.y1 - cmd.y0;
     ShadeArgs a;
     memset(&a, 0, sizeof a);
     a.x0 = cmd.x0; a.x1 = cmd.x1; a.y0 = cmd.y0; a.y1 = cmd.y1;
     a.cstride = (int32_t)c->W;
     a.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
-    a.id_first = cmd.id_first; a.id_count = cmd.id_count;
+    a.id_first = cmd.id_first; a.id_count = cmd.id_count;   // (a SHADE_ITEMS command has none: zeros)
     a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
     a.tri_id = f.bound.tri_id; a.in = cmd.shade_in; a.in_entries = cmd.shade_entries;
     a.color = (uint32_t *)f.bound.color;
+    return a;
+}
+// items: k_shade_items over `a`, else k_shade_vary over a.s
+template <int K, int PS> void launch_shade(hipStream_t ts, dim3 grid, bool items, const ShadeItemsArgs &a, const DevUniforms &du, bool vec)
+{
+    auto go = [&](auto vec_tag) {
+        constexpr bool VEC = decltype(vec_tag)::value;
+        if (items) hipLaunchKernelGGL((k_shade_items<K, PS, VEC>), grid, dim3(SHADE_WG), 0, ts, a, du);
+        else hipLaunchKernelGGL((k_shade_vary<K, PS, VEC>), grid, dim3(SHADE_WG), 0, ts, a.s, du);
+    };
+    if constexpr (K > 0 && K % 4 == 0) { if (vec) { go(std::true_type{}); return; } }
+    go(std::false_type{});
+}
+int exec_shade(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    const bool items = cmd.kind == Cmd::SHADE_ITEMS;
+    int rc;
+    const UserModule *um = nullptr;
+    if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
+    if ((rc = cmd_settle(c, items)) != FRR_OK) return rc;
+    const uint32_t *item_first = nullptr;
+    if (items && (rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
+    hipStream_t ts;
+    if ((rc = cmd_stream(c, items, true, &ts)) != FRR_OK) return rc;
+    ShadeItemsArgs a;
+    memset(&a, 0, sizeof a);
+    a.s = shade_args(c, cmd);
+    if (items) {
+        VisibleArgs v;   // the boundaries, as a per-item count builds them: no counts, so nothing to zero
+        if ((rc = count_args(c, cmd, ts, (uint32_t)f.geom.read.ntris, true, item_first, &v)) != FRR_OK) return rc;
+        v.unit = FRR_PER_ITEM; v.out = nullptr; v.out_entries = 0;
+        a.bounds = v.bounds; a.nitems = v.nitems; a.mats = cmd.mats; a.zero_tex = c->zero_texel;
+        launch_count_prep(ts, v);
+    }
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
     const dim3 grid((unsigned)((ww + SHADE_WG - 1) / SHADE_WG), (unsigned)wh);
     // 16-byte loads where every entry's address allows them: K a multiple of 4 and an aligned buffer
     const bool vec = cmd.shade_K > 0 && (cmd.shade_K & 3) == 0 && ((uintptr_t)cmd.shade_in & 15u) == 0u;
     if (um) {
-        ShadeArgs sa = a; DevUniforms d = cmd.duni;
-        void *args[] = {&sa, &d};
-        (void)hipModuleLaunchKernel(um->shade[vec ? 1 : 0], grid.x, grid.y, 1, SHADE_WG, 1, 1, 0, ts, args, nullptr);
+        DevUniforms d = cmd.duni;
+        void *args[] = {items ? (void *)&a : (void *)&a.s, &d};
+        (void)hipModuleLaunchKernel((items ? um->shade_items : um->shade)[vec ? 1 : 0], grid.x, grid.y, 1, SHADE_WG, 1, 1, 0, ts, args, nullptr);
     } else {
         switch (cmd.ps) {
-        case FRR_PS_FLAT: launch_shade<0, FRR_PS_FLAT>(ts, grid, a, cmd.duni, false); break;   // (reads no varying, whatever K the buffer has)
-        case FRR_PS_COLOR: launch_shade<3, FRR_PS_COLOR>(ts, grid, a, cmd.duni, false); break;
-        case FRR_PS_PHONG: launch_shade<8, FRR_PS_PHONG>(ts, grid, a, cmd.duni, vec); break;
-        case FRR_PS_BLINN: launch_shade<8, FRR_PS_BLINN>(ts, grid, a, cmd.duni, vec); break;
+        case FRR_PS_FLAT: launch_shade<0, FRR_PS_FLAT>(ts, grid, items, a, cmd.duni, false); break;   // (reads no varying, whatever K the buffer has)
+        case FRR_PS_COLOR: launch_shade<3, FRR_PS_COLOR>(ts, grid, items, a, cmd.duni, false); break;
+        case FRR_PS_PHONG: launch_shade<8, FRR_PS_PHONG>(ts, grid, items, a, cmd.duni, vec); break;
+        case FRR_PS_BLINN: launch_shade<8, FRR_PS_BLINN>(ts, grid, items, a, cmd.duni, vec); break;
         }
     }
     HIP_TRY(c, hipGetLastError());
-    cmd.lane = f.lane;
-    return FRR_OK;
-}
-
-// frr_shade_items: frr_shade_varyings with the pixel uniforms of each pixel's item (frr_shade.h: k_shade_items).  It writes a
-// target, so it is ordered like exec_shade; it reads the tables of the latest geometry pass on the device, so it also takes
-// the steps of exec_visible against that pass -- scan_now, tstream_wait_gstream, tables_read -- and the item boundaries are
-// built by that command's own k_visible_prep (with no counts to zero it writes the boundaries alone), into the same
-// per-stream table.  It cannot fail on the device and owns no device table, so a replay runs it again in its place, under
-// the uniforms of the call and over the material table as it is then.
-template <int K, int PS> void launch_shade_items(hipStream_t ts, dim3 grid, const ShadeItemsArgs &a, const DevUniforms &du, bool vec)
-{
-    if constexpr (K > 0 && K % 4 == 0) { if (vec) { hipLaunchKernelGGL((k_shade_items<K, PS, true>), grid, dim3(SHADE_WG), 0, ts, a, du); return; } }
-    hipLaunchKernelGGL((k_shade_items<K, PS, false>), grid, dim3(SHADE_WG), 0, ts, a, du);
-}
-int exec_shade_items(frr_ctx *c, Cmd &cmd)
-{
-    FrameState &f = c->fs;
-    int rc;
-    const UserModule *um = nullptr;
-    if (cmd.ps >= FRR_SHADER_USER_BASE && (rc = user_module(c, cmd.ps, &um)) != FRR_OK) return rc;
-    if ((rc = scan_now(c)) != FRR_OK) return rc;   // n_emit and the block prefix of the pass
-    if (f.clear.pending && (rc = settle_targets(c)) != FRR_OK) return rc;
-    const uint32_t *item_first = nullptr;
-    if ((rc = list_item_first(c, &item_first)) != FRR_OK) return rc;
-    if ((rc = tstream_wait_gstream(c)) != FRR_OK) return rc;   // after the geometry pass, as a tile kernel is
-    hipStream_t ts;
-    if ((rc = target_write(c, !c->in_replay, &ts)) != FRR_OK) return rc;
-    DevBuf<uint32_t> &tab = c->vis_bounds[stream_slot(c, ts)];
-    if ((rc = ensure(c, tab, (size_t)f.geom.nitems + 1)) != FRR_OK) return rc;
-    const GeomSet &S = c->gset[f.geom.set];
-    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
-    VisibleArgs v;   // the boundaries, as a per-item count builds them
-    memset(&v, 0, sizeof v);
-    v.unit = FRR_PER_ITEM;
-    v.nitems = (uint32_t)f.geom.nitems; v.item_first = item_first; v.stride = (uint32_t)f.geom.stride; v.ntris = (uint32_t)f.geom.read.ntris;
-    v.tinfo = S.tinfo; v.block_prefix = S.block_prefix; v.bounds = tab;
-    v.gpar = f.gpar(); v.lane = f.lane;
-    v.seq = cmd.seq; v.epoch = c->epoch; v.cnt = c->cnt;
-    ShadeItemsArgs a;
-    memset(&a, 0, sizeof a);
-    a.s.x0 = cmd.x0; a.s.x1 = cmd.x1; a.s.y0 = cmd.y0; a.s.y1 = cmd.y1;
-    a.s.cstride = (int32_t)c->W;
-    a.s.own = row_owner(f, (int)((wh + TILE - 1) / TILE));
-    a.s.seq = cmd.seq; a.s.epoch = c->epoch; a.s.cnt = c->cnt;
-    a.s.tri_id = f.bound.tri_id; a.s.in = cmd.shade_in; a.s.in_entries = cmd.shade_entries;
-    a.s.color = (uint32_t *)f.bound.color;
-    a.bounds = tab; a.nitems = v.nitems; a.mats = cmd.mats; a.zero_tex = c->zero_texel;
-    hipLaunchKernelGGL(k_visible_prep, dim3((uint32_t)std::min<uint64_t>(((uint64_t)v.nitems + 1 + VIS_WG - 1) / VIS_WG, 2048)), dim3(VIS_WG), 0, ts, v);
-    const dim3 grid((unsigned)((ww + SHADE_WG - 1) / SHADE_WG), (unsigned)wh);
-    const bool vec = cmd.shade_K > 0 && (cmd.shade_K & 3) == 0 && ((uintptr_t)cmd.shade_in & 15u) == 0u;
-    if (um) {
-        ShadeItemsArgs sa = a; DevUniforms d = cmd.duni;
-        void *args[] = {&sa, &d};
-        (void)hipModuleLaunchKernel(um->shade_items[vec ? 1 : 0], grid.x, grid.y, 1, SHADE_WG, 1, 1, 0, ts, args, nullptr);
-    } else {
-        switch (cmd.ps) {
-        case FRR_PS_FLAT: launch_shade_items<0, FRR_PS_FLAT>(ts, grid, a, cmd.duni, false); break;   // (reads no varying, whatever K the buffer has)
-        case FRR_PS_COLOR: launch_shade_items<3, FRR_PS_COLOR>(ts, grid, a, cmd.duni, false); break;
-        case FRR_PS_PHONG: launch_shade_items<8, FRR_PS_PHONG>(ts, grid, a, cmd.duni, vec); break;
-        case FRR_PS_BLINN: launch_shade_items<8, FRR_PS_BLINN>(ts, grid, a, cmd.duni, vec); break;
-        }
-    }
-    HIP_TRY(c, hipGetLastError());
-    tables_read(c, cmd, ts);   // like a count
+    cmd_done(c, cmd, items, ts);
     return FRR_OK;
 }
 
@@ -1618,7 +1603,15 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     cmd.pre = c->fs;
     cmd.seq = c->next_seq++;
     c->verify_pending = false;
-    const int rc = cmd.kind == Cmd::GEOM ? exec_geometry(c, cmd) : cmd.kind == Cmd::RASTER ? exec_raster(c, cmd) : cmd.kind == Cmd::LINES ? exec_lines(c, cmd) : cmd.kind == Cmd::VARY ? exec_vary(c, cmd) : cmd.kind == Cmd::VISIBLE ? exec_visible(c, cmd) : cmd.kind == Cmd::SHADE_ITEMS ? exec_shade_items(c, cmd) : exec_shade(c, cmd);
+    int rc = FRR_OK;
+    switch (cmd.kind) {
+    case Cmd::GEOM: rc = exec_geometry(c, cmd); break;
+    case Cmd::RASTER: rc = exec_raster(c, cmd); break;
+    case Cmd::LINES: rc = exec_lines(c, cmd); break;
+    case Cmd::VARY: rc = exec_vary(c, cmd); break;
+    case Cmd::VISIBLE: rc = exec_visible(c, cmd); break;
+    case Cmd::SHADE: case Cmd::SHADE_ITEMS: rc = exec_shade(c, cmd); break;
+    }
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
     if (c->verify_pending) {
@@ -1685,10 +1678,10 @@ int finish(frr_ctx *c)
         // the device tables as they were before the failed command: it has used its own parity's cursors (and, when its
         // block sums were scanned inside the next raster pass's binning launch, that pass has reserved bin space)
         h.first_bad = SEQ_NONE; h.overflow = 0u;
-        // (line, varyings, count and shade commands in between own no table: the "next" command is the next geometry or raster pass)
+        // (the commands in between that own no table do not count: the "next" command is the next geometry or raster pass)
         for (size_t k = i, seen = 0; k < c->log.size() && seen < 2; ++k) {
             const Cmd &m = c->log[k];
-            if (m.kind == Cmd::LINES || m.kind == Cmd::VARY || m.kind == Cmd::SHADE || m.kind == Cmd::VISIBLE || m.kind == Cmd::SHADE_ITEMS) continue;
+            if (!m.owns_table()) continue;
             ++seen;
             if (m.kind == Cmd::GEOM && k == i) {
                 GeomTab &gt = h.lane[m.lane].gtab[m.par];
@@ -1776,6 +1769,31 @@ template <typename T> int host_round_trip(frr_ctx *c, Cmd cmd, T *Cmd::*out, Dev
     if (rc != FRR_OK) return rc;
     if (e != hipSuccess) return fail(c, FRR_ERR_HIP, std::string("hipMemcpy ") + what + ": " + hipGetErrorString(e));
     return FRR_OK;
+}
+// The host form of a shade command (`cmd` with its shader, window and shade_K set): the part of the caller's array the window
+// can index becomes a device buffer the ctx owns for as long as the command is logged (frr_ctx::shade_tmp), and the command
+// reads that.  shade_K == 0: no copy, a null pointer.
+int shade_from_host(frr_ctx *c, Cmd cmd, const float *host_in)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int K = cmd.shade_K;
+    const uint64_t entries = (uint64_t)((int64_t)cmd.y1 - cmd.y0) * (uint64_t)cmd.x1;
+    DevBuf<float> tmp;
+    if (K > 0) {
+        if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
+        // (returns when the copy is done: in front of the command on any stream)
+        HIP_TRY(c, hipMemcpy(tmp, host_in, (size_t)entries * (size_t)K * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const float *dev = tmp;
+    if (K > 0) c->shade_tmp.push_back(std::move(tmp));
+    cmd.shade_in = dev; cmd.shade_entries = entries;
+    const int rc = exec_cmd(c, cmd);
+    // a command that failed on the host is not logged, and nothing will replay it: its copy goes now.  (A synchronisation
+    // point inside exec_cmd has dropped log and copies alike.)
+    bool logged = false;
+    for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == cmd.kind && c->log[k].shade_in == dev;
+    if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
+    return rc;
 }
 
 } // namespace
@@ -2778,96 +2796,55 @@ int frr_readback_varyings(frr_ctx *c, int32_t x0, int32_t x1, int32_t y0, int32_
     return host_round_trip(c, new_cmd(c, Cmd::VARY, x0, x1, y0, y1), &Cmd::vary_out, tmp, host_inout, bytes, "varyings");
 }
 
-// argument checks of the count commands, `who`: frr_visible_pixels / frr_visible_pixels_host, frr_query_pixels / frr_query_pixels_host
-static int count_check(frr_ctx *c, const char *who, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
+// The count commands, frr_visible_pixels* and (`query`) frr_query_pixels*: the argument checks, the command, and with
+// `host` its round trip through a temporary device buffer, after which *nunits is the number of units the pass has.
+static int count_pixels(frr_ctx *c, bool query, bool host, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *out, uint64_t out_entries, uint64_t *nunits)
 {
     if (!c) return FRR_ERR_INVALID;
+    const char *who = query ? "frr_query_pixels" : "frr_visible_pixels";
+    const FrameState &f = c->fs;
     if (unit != FRR_PER_ITEM && unit != FRR_PER_TRIANGLE) return fail(c, FRR_ERR_INVALID, "unknown frr_visible_unit");
-    if (c->fs.geom.none()) return fail(c, FRR_ERR_INVALID, std::string(who) + " before any geometry pass");
+    if (f.geom.none()) return fail(c, FRR_ERR_INVALID, std::string(who) + " before any geometry pass");
     int rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
     if (rc == FRR_OK) rc = need_unfiltered_list(c, who);
-    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, buf, out_entries, 0, x1, y0, y1));
-    return rc;
-}
-static int visible_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
-{
-    return count_check(c, "frr_visible_pixels", unit, x0, x1, y0, y1, buf, out_entries);
-}
-static Cmd visible_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
-{
-    Cmd cmd = new_cmd(c, Cmd::VISIBLE, x0, x1, y0, y1);
-    cmd.vis_unit = unit; cmd.vis_out = dev_out; cmd.vis_entries = out_entries;
-    return cmd;
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, out, out_entries, 0, x1, y0, y1));
+    const uint32_t *item_first;   // (a query over a list freed since the pass: refused here, before anything is launched)
+    if (rc == FRR_OK && query && unit == FRR_PER_ITEM && f.draws != 0) rc = list_item_first(c, &item_first);
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a query is a raster command that counts, or -- a frr_clear since the pass, a pass without triangles or without items:
+    // nothing to rasterize -- the count command, which then zeroes the buffer and counts nothing
+    const bool raster = query && f.draws != 0 && f.geom.read.ntris != 0 && !(unit == FRR_PER_ITEM && f.geom.nitems == 0);
+    Cmd cmd = new_cmd(c, raster ? Cmd::RASTER : Cmd::VISIBLE, x0, x1, y0, y1);
+    if (query) { cmd.query = true; cmd.ps = FRR_PS_DEPTH; cmd.count_frags = false; }
+    cmd.vis_unit = unit; cmd.vis_out = host ? nullptr : (uint32_t *)out; cmd.vis_entries = out_entries;
+    if (!host) return exec_cmd(c, cmd);
+    DevBuf<uint32_t> tmp;
+    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
+    rc = host_round_trip(c, cmd, &Cmd::vis_out, tmp, (uint32_t *)out, (size_t)out_entries * sizeof(uint32_t), "counts");
+    if (rc != FRR_OK) return rc;
+    if (nunits) {
+        const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
+        *nunits = unit == FRR_PER_ITEM ? f.geom.nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom.read.ntris ? gt.n_emit : 0u);
+    }
+    return FRR_OK;
 }
 
 int frr_visible_pixels(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_u32, uint64_t out_entries)
 {
-    const int rc = visible_check(c, unit, x0, x1, y0, y1, dev_out_u32, out_entries);
-    if (rc != FRR_OK || out_entries == 0) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return exec_cmd(c, visible_cmd(c, unit, x0, x1, y0, y1, (uint32_t *)dev_out_u32, out_entries));
+    return count_pixels(c, false, false, unit, x0, x1, y0, y1, dev_out_u32, out_entries, nullptr);
 }
-
 int frr_visible_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *host_out, uint64_t out_entries, uint64_t *nunits)
 {
-    int rc = visible_check(c, unit, x0, x1, y0, y1, host_out, out_entries);
-    if (rc != FRR_OK || out_entries == 0) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<uint32_t> tmp;
-    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
-    rc = host_round_trip(c, visible_cmd(c, unit, x0, x1, y0, y1, nullptr, out_entries), &Cmd::vis_out, tmp, host_out, (size_t)out_entries * sizeof(uint32_t), "counts");
-    if (rc != FRR_OK) return rc;
-    if (nunits) {
-        const FrameState &f = c->fs;
-        const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
-        *nunits = unit == FRR_PER_ITEM ? f.geom.nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom.read.ntris ? gt.n_emit : 0u);
-    }
-    return FRR_OK;
+    return count_pixels(c, false, true, unit, x0, x1, y0, y1, host_out, out_entries, nunits);
 }
-
-// frr_query_pixels / frr_query_pixels_host: the argument checks are frr_visible_pixels'
-static int query_check(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const void *buf, uint64_t out_entries)
-{
-    int rc = count_check(c, "frr_query_pixels", unit, x0, x1, y0, y1, buf, out_entries);
-    const uint32_t *item_first;   // (a list freed since the pass: refused here, before anything is launched)
-    if (rc == FRR_OK && unit == FRR_PER_ITEM && c->fs.draws != 0) rc = list_item_first(c, &item_first);
-    return rc;
-}
-// the command: a raster command that counts, or -- a frr_clear since the pass, a pass without triangles or without items:
-// nothing to rasterize -- the count command that zeroes the buffer and counts nothing
-static Cmd query_cmd(const frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *dev_out, uint64_t out_entries)
-{
-    const FrameState &f = c->fs;
-    const bool nothing = f.draws == 0 || f.geom.read.ntris == 0 || (unit == FRR_PER_ITEM && f.geom.nitems == 0);
-    Cmd cmd = new_cmd(c, nothing ? Cmd::VISIBLE : Cmd::RASTER, x0, x1, y0, y1);
-    cmd.query = true; cmd.ps = FRR_PS_DEPTH; cmd.count_frags = false;
-    cmd.vis_unit = unit; cmd.vis_out = dev_out; cmd.vis_entries = out_entries;
-    return cmd;
-}
-
 int frr_query_pixels(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_u32, uint64_t out_entries)
 {
-    const int rc = query_check(c, unit, x0, x1, y0, y1, dev_out_u32, out_entries);
-    if (rc != FRR_OK || out_entries == 0) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return exec_cmd(c, query_cmd(c, unit, x0, x1, y0, y1, (uint32_t *)dev_out_u32, out_entries));
+    return count_pixels(c, true, false, unit, x0, x1, y0, y1, dev_out_u32, out_entries, nullptr);
 }
-
 int frr_query_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *host_out, uint64_t out_entries, uint64_t *nunits)
 {
-    int rc = query_check(c, unit, x0, x1, y0, y1, host_out, out_entries);
-    if (rc != FRR_OK || out_entries == 0) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<uint32_t> tmp;
-    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
-    rc = host_round_trip(c, query_cmd(c, unit, x0, x1, y0, y1, nullptr, out_entries), &Cmd::vis_out, tmp, host_out, (size_t)out_entries * sizeof(uint32_t), "counts");
-    if (rc != FRR_OK) return rc;
-    if (nunits) {
-        const FrameState &f = c->fs;
-        const GeomTab &gt = c->hc.lane[f.lane].gtab[f.gpar()];
-        *nunits = unit == FRR_PER_ITEM ? f.geom.nitems : f.draws == 0 ? 0 : (uint64_t)gt.tri_base + (f.geom.read.ntris ? gt.n_emit : 0u);
-    }
-    return FRR_OK;
+    return count_pixels(c, true, true, unit, x0, x1, y0, y1, host_out, out_entries, nunits);
 }
 
 int frr_host_fragment_passes(float rhw, float depth) { return fragment_passes(rhw, depth) ? 1 : 0; }
@@ -2912,26 +2889,9 @@ int frr_shade_varyings_host(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32
                             uint32_t id_first, uint32_t id_count)
 {
     bool nothing = false;
-    int rc = shade_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, id_count, &nothing);
+    const int rc = shade_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, id_count, &nothing);
     if (rc != FRR_OK || nothing) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the part of the caller's array the window can index, as a device buffer the ctx owns for as long as the command is logged
-    const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
-    DevBuf<float> tmp;
-    if (K > 0) {
-        if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
-        // (returns when the copy is done: in front of the command on any stream)
-        HIP_TRY(c, hipMemcpy(tmp, host_in, (size_t)entries * (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-    }
-    const float *dev = tmp;
-    if (K > 0) c->shade_tmp.push_back(std::move(tmp));
-    rc = exec_cmd(c, shade_cmd(c, ps_id, x0, x1, y0, y1, dev, entries, K, id_first, id_count));
-    // a command that failed on the host is not logged, and nothing will replay it: its copy goes now.  (A synchronisation
-    // point inside exec_cmd has dropped log and copies alike.)
-    bool logged = false;
-    for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == Cmd::SHADE && c->log[k].shade_in == dev;
-    if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
-    return rc;
+    return shade_from_host(c, shade_cmd(c, ps_id, x0, x1, y0, y1, nullptr, 0, K, id_first, id_count), host_in);
 }
 
 // ---- per-item materials (frr_shade_items): tables of frr_material, one entry per item of a pass ----------------------
@@ -3035,23 +2995,9 @@ int frr_shade_items(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, i
 int frr_shade_items_host(frr_ctx *c, int ps_id, int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *host_in, uint64_t in_entries, int K, int materials)
 {
     bool nothing = false;
-    int rc = shade_items_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, materials, &nothing);
+    const int rc = shade_items_check(c, ps_id, x0, x1, y0, y1, host_in, in_entries, K, materials, &nothing);
     if (rc != FRR_OK || nothing) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // (the device copy and its lifetime: as in frr_shade_varyings_host)
-    const uint64_t entries = (uint64_t)((int64_t)y1 - y0) * (uint64_t)x1;
-    DevBuf<float> tmp;
-    if (K > 0) {
-        if (tmp.reset((size_t)entries * (size_t)K) != hipSuccess) return nomem(c, "varyings buffer");
-        HIP_TRY(c, hipMemcpy(tmp, host_in, (size_t)entries * (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-    }
-    const float *dev = tmp;
-    if (K > 0) c->shade_tmp.push_back(std::move(tmp));
-    rc = exec_cmd(c, shade_items_cmd(c, ps_id, x0, x1, y0, y1, dev, entries, K, materials));
-    bool logged = false;
-    for (size_t k = c->log.size(); k-- > 0 && !logged;) logged = c->log[k].kind == Cmd::SHADE_ITEMS && c->log[k].shade_in == dev;
-    if (K > 0 && !logged && !c->shade_tmp.empty() && c->shade_tmp.back().get() == dev) c->shade_tmp.pop_back();
-    return rc;
+    return shade_from_host(c, shade_items_cmd(c, ps_id, x0, x1, y0, y1, nullptr, 0, K, materials), host_in);
 }
 
 int64_t frr_host_entry_items(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,

@@ -522,12 +522,7 @@ public:
     // the same on the host (a synchronisation point): the counts of all n units
     std::vector<uint32_t> visible_pixels(int unit, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
     {
-        uint64_t n = 0;
-        uint32_t probe = 0;   // (one entry is enough to ask for n)
-        check(frr_visible_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, &probe, 1, &n));
-        std::vector<uint32_t> out((size_t)n, probe);
-        if (n > 1) check(frr_visible_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, out.data(), n, &n));
-        return out;
+        return counts_on_host(frr_visible_pixels_host, unit, width_range, height_range);
     }
     std::vector<uint32_t> visible_pixels(int unit) { return visible_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
     // The occlusion query (include/frr.h: frr_query_pixels): how many fragments of each unit of the latest geometry pass would
@@ -542,12 +537,7 @@ public:
     // the same on the host (a synchronisation point): the counts of all n units
     std::vector<uint32_t> query_pixels(int unit, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
     {
-        uint64_t n = 0;
-        uint32_t probe = 0;   // (one entry is enough to ask for n)
-        check(frr_query_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, &probe, 1, &n));
-        std::vector<uint32_t> out((size_t)n, probe);
-        if (n > 1) check(frr_query_pixels_host(ctx_, unit, width_range.first, width_range.second, height_range.first, height_range.second, out.data(), n, &n));
-        return out;
+        return counts_on_host(frr_query_pixels_host, unit, width_range, height_range);
     }
     std::vector<uint32_t> query_pixels(int unit) { return query_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
     void sync() { check(frr_sync(ctx_)); }
@@ -655,6 +645,17 @@ public:
 private:
     // negative status: throw; a positive one (warning; none defined at present): results were delivered, remembered in last_warning
     void check(int rc) { if (rc < FRR_OK) throw Error(rc, frr_last_error(ctx_)); last_warning = rc; }
+    // the host form of a count command (frr_visible_pixels_host, frr_query_pixels_host): n first, then the counts
+    std::vector<uint32_t> counts_on_host(int (*host)(frr_ctx *, int, int32_t, int32_t, int32_t, int32_t, uint32_t *, uint64_t, uint64_t *), int unit,
+                                         std::pair<int32_t, int32_t> wr, std::pair<int32_t, int32_t> hr)
+    {
+        uint64_t n = 0;
+        uint32_t probe = 0;   // (one entry is enough to ask for n)
+        check(host(ctx_, unit, wr.first, wr.second, hr.first, hr.second, &probe, 1, &n));
+        std::vector<uint32_t> out((size_t)n, probe);
+        if (n > 1) check(host(ctx_, unit, wr.first, wr.second, hr.first, hr.second, out.data(), n, &n));
+        return out;
+    }
 public:
     int last_warning = FRR_OK;
 private:

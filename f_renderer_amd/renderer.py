@@ -717,26 +717,9 @@ class Renderer:
         `entries` are counted nowhere; order the reads with frame_fence(a created stream) or sync(), and keep the buffer
         until then.  Without `out_ptr` it is the host form (a synchronisation point) and returns a uint32 array of the n
         counts, or of `entries` of them."""
-        u = {"item": N.PER_ITEM, "triangle": N.PER_TRIANGLE}.get(unit, unit)
         wr = width_range or (0, self.width)
         hr = height_range or (0, self.height)
-        win = (int(wr[0]), int(wr[1]), int(hr[0]), int(hr[1]))
-        if out_ptr is not None:
-            if entries is None:
-                raise FrrError(N.FRR_ERR_INVALID, "visible_pixels: the device form needs the buffer's entries")
-            self._check(self._lib.frr_visible_pixels(self._ctx, int(u), *win, C.c_void_p(out_ptr), int(entries)))
-            return None
-        n = C.c_uint64()
-        if entries is None:   # n first (one entry is enough to ask), then the counts
-            probe = np.zeros(1, np.uint32)
-            self._check(self._lib.frr_visible_pixels_host(self._ctx, int(u), *win, probe.ctypes.data, 1, C.byref(n)))
-            entries = int(n.value)
-            if entries <= 1:
-                return probe[:entries]
-        out = np.zeros(int(entries), np.uint32)
-        if out.size:
-            self._check(self._lib.frr_visible_pixels_host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
-        return out
+        return self._count_pixels("visible_pixels", unit, (wr[0], wr[1], hr[0], hr[1]), out_ptr, entries)
 
     def query_pixels(self, unit="item", window=None, out_ptr=None, entries=None):
         """The occlusion query (frr_query_pixels): how many fragments of each unit of the latest geometry pass -- unit="item"
@@ -745,23 +728,28 @@ class Renderer:
         uint32) it is a command on the frame's stream with no host wait and returns nothing: the buffer can be the keep
         buffer of a later draw_list_if as it is.  Without `out_ptr` it is the host form (a synchronisation point) and
         returns a uint32 array of the n counts, or of `entries` of them."""
+        return self._count_pixels("query_pixels", unit, window or (0, self.width, 0, self.height), out_ptr, entries)
+
+    def _count_pixels(self, who, unit, window, out_ptr, entries):
+        """visible_pixels / query_pixels (`who`): frr_<who> over the caller's device buffer, or frr_<who>_host"""
         u = {"item": N.PER_ITEM, "triangle": N.PER_TRIANGLE}.get(unit, unit)
-        win = tuple(int(v) for v in (window or (0, self.width, 0, self.height)))
+        win = tuple(int(v) for v in window)
         if out_ptr is not None:
             if entries is None:
-                raise FrrError(N.FRR_ERR_INVALID, "query_pixels: the device form needs the buffer's entries")
-            self._check(self._lib.frr_query_pixels(self._ctx, int(u), *win, C.c_void_p(out_ptr), int(entries)))
+                raise FrrError(N.FRR_ERR_INVALID, who + ": the device form needs the buffer's entries")
+            self._check(getattr(self._lib, "frr_" + who)(self._ctx, int(u), *win, C.c_void_p(out_ptr), int(entries)))
             return None
+        host = getattr(self._lib, "frr_" + who + "_host")
         n = C.c_uint64()
         if entries is None:   # n first (one entry is enough to ask), then the counts
             probe = np.zeros(1, np.uint32)
-            self._check(self._lib.frr_query_pixels_host(self._ctx, int(u), *win, probe.ctypes.data, 1, C.byref(n)))
+            self._check(host(self._ctx, int(u), *win, probe.ctypes.data, 1, C.byref(n)))
             entries = int(n.value)
             if entries <= 1:
                 return probe[:entries]
         out = np.zeros(int(entries), np.uint32)
         if out.size:
-            self._check(self._lib.frr_query_pixels_host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
+            self._check(host(self._ctx, int(u), *win, out.ctypes.data, out.size, C.byref(n)))
         return out
 
     def frame_fence(self, stream=None):

@@ -728,3 +728,39 @@ def test_errors_leave_the_ctx_drawing(oracle):
     r.shade_items(fr.PS_PHONG, p, tab)
     _assert_B(_snap(r), fb)
     r.close()
+
+
+# ---- 15. a host-form shade refused on the host after its array was staged -------------------------------------------------------
+def test_host_form_refused_after_staging_leaves_the_next_shade_alone(oracle):
+    """The pass's draw list is freed behind the pre-pass, so the argument rules still pass, the host form stages the caller's
+    array on the device, and the executor then refuses the command: nothing is logged, nothing is written, and the staged copy
+    goes with the call.  Behind a sync the same shade from host memory, over a pass of a list that exists, is the oracle's
+    frame (B) -- with a logged host-form shade_varyings, whose copy stays, on either side of the refused call."""
+    import f_renderer_amd as fr
+    sc = D.scene("clipped")
+    mats = IT.materials(sc.nitems)
+    fb, _ = IT.expected_B("clipped")
+    r = _renderer()
+    tab = r.upload_materials(mats)
+    dl, _ = _list(r, sc)
+    buf = _sentinel()
+    _prepass(r, dl, buf)
+    host = buf.cpu().numpy()
+    dl.free()                                                     # (finishes first: the pass and its resolve are done)
+    r.shade_varyings(fr.PS_PHONG, host)                           # logged; reads its own staged copy
+    with pytest.raises(fr.FrrError) as err:
+        r.shade_items(fr.PS_PHONG, host, tab)
+    assert err.value.code == fr.FRR_ERR_INVALID and "freed" in str(err.value), err.value
+    r.shade_varyings(fr.PS_PHONG, host)
+    r.sync()
+    before = _snap(r)
+    assert (before["c"] != np.array(D.CLEAR[0], np.uint8)).any()
+    with pytest.raises(fr.FrrError):
+        r.shade_items(fr.PS_PHONG, host, tab)
+    _unchanged(before, _snap(r))
+    np.testing.assert_array_equal(before["c"], _snap(r)["c"])
+    dl2, _ = _list(r, sc)
+    _prepass(r, dl2, buf)
+    r.shade_items(fr.PS_PHONG, buf.cpu().numpy(), tab)
+    _assert_B(_snap(r), fb)
+    r.close()

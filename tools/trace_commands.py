@@ -1,5 +1,6 @@
 """Dev tool: two 64 x 48 frames that use every command kind once (geometry, raster, line list, wireframe, resolve, shade,
-visible count), for a kernel trace that shows what the host layer dispatches, in order:
+visible count; then, behind a list pass of two items and its raster pass, the per-item shade over a table of two materials
+and the occlusion query per item), for a kernel trace that shows what the host layer dispatches, in order:
   rocprofv3 --kernel-trace --output-format csv -d DIR -o kt -- python3 tools/trace_commands.py
   python3 tools/trace_commands.py --names DIR/.../kt_kernel_trace.csv > names.txt     (kernel names by dispatch id)"""
 import csv
@@ -26,6 +27,8 @@ def frames():
     r = fr.Renderer(W, H)
     mesh = r.upload_mesh(scenes.single_triangle_rgb(), fr.VS_CLIP_COLOR)
     lines = r.upload_lines(np.array([[1, 1, 40, 30]], np.uint32), np.array([[255, 255, 0, 255]], np.uint8))
+    items = r.upload_draw_list([mesh, mesh], np.stack([np.eye(4, dtype=np.float32)] * 2))
+    mats = r.upload_materials([{"flat_color": (1, 0, 0, 1)}, {"flat_color": (0, 1, 0, 1)}])
     vary = torch.zeros(W * H * 3, dtype=torch.float32, device="cuda")
     counts = torch.zeros(4, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -38,6 +41,10 @@ def frames():
         r.resolve_varyings(vary.data_ptr(), W * H)
         r.shade_varyings(fr.PS_COLOR, vary.data_ptr())
         r.visible_pixels("item", out_ptr=counts.data_ptr(), entries=4)
+        r.geometry_list(items)
+        r.rasterization((0, W), (0, H), fr.PS_DEPTH)
+        r.shade_items(fr.PS_COLOR, vary.data_ptr(), mats)
+        r.query_pixels("item", out_ptr=counts.data_ptr(), entries=4)
         r.sync()
     c, _, t = r.readback()
     print("drawn pixels", int((t != 0xFFFFFFFF).sum()), "colour sum", int(c.sum()))
