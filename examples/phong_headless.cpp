@@ -28,6 +28,10 @@
 //   --materials with --list --deferred gives every object a material of its own -- texture slots 0, 1, 2 in turn (the diffuse
 //       texture, and it with its first / its second channel inverted) and a flat colour in turn -- and shades the whole list
 //       with ONE pass over the frame (shade_items_host): phong.rs:361-370, a ps_uniform per object, for a list
+//   --boxes with --list runs the loop of --occlusion with the box query in the proxy pass's place: the objects' bounds computed on
+//       the device (list_bounds), their boxes tested against a pyramid of the occluder's depth (query_boxes: no geometry pass, no
+//       binning), the objects it keeps drawn (draw_list_if).  It prints per item the status and the value, and whether colour and
+//       depth equal the frame that draws every object
 //   --occlusion with --list draws the mesh once more, unscaled, as an occluder in front of the right part of the grid, and then
 //       runs the occlusion loop of INTEGRATION.md 1f with no host wait in between: the objects' bounding boxes as a proxy list,
 //       queried against the occluder's depth (query_pixels: nothing is drawn), the objects whose box passed somewhere drawn
@@ -61,12 +65,12 @@ static std::vector<char> slurp(const char *path)
 
 int main(int argc, char **argv)
 {
-    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false, materials = false, occlusion = false;
+    bool wireframe = false, deferred = false, list = false, visible = false, reuse = false, materials = false, occlusion = false, boxes = false;
     for (int i = 1; i < argc; ++i)
         if (std::string(argv[i]) == "--wireframe" || std::string(argv[i]) == "--deferred" || std::string(argv[i]) == "--list" || std::string(argv[i]) == "--visible" || std::string(argv[i]) == "--reuse" ||
-            std::string(argv[i]) == "--materials" || std::string(argv[i]) == "--occlusion") {
+            std::string(argv[i]) == "--materials" || std::string(argv[i]) == "--occlusion" || std::string(argv[i]) == "--boxes") {
             (std::string(argv[i]) == "--wireframe" ? wireframe : std::string(argv[i]) == "--list" ? list : std::string(argv[i]) == "--visible" ? visible : std::string(argv[i]) == "--reuse" ? reuse :
-             std::string(argv[i]) == "--materials" ? materials : std::string(argv[i]) == "--occlusion" ? occlusion : deferred) = true;
+             std::string(argv[i]) == "--materials" ? materials : std::string(argv[i]) == "--occlusion" ? occlusion : std::string(argv[i]) == "--boxes" ? boxes : deferred) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc; --i;
         }
@@ -89,6 +93,7 @@ int main(int argc, char **argv)
     if (visible && !list && instances < 0) { std::cerr << "--visible goes with --list or --instances N\n"; return 2; }
     if (reuse && (!list || !visible || wireframe || deferred)) { std::cerr << "--reuse goes with --list --visible (and without --wireframe / --deferred)\n"; return 2; }
     if (materials && (!list || !deferred)) { std::cerr << "--materials goes with --list --deferred\n"; return 2; }
+    if (boxes && (!list || occlusion || visible || reuse || wireframe || deferred)) { std::cerr << "--boxes goes with --list (and without --occlusion / --visible / --reuse / --wireframe / --deferred)\n"; return 2; }
     if (occlusion && (!list || visible || reuse || wireframe || deferred)) { std::cerr << "--occlusion goes with --list (and without --visible / --reuse / --wireframe / --deferred)\n"; return 2; }
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "--dump-assets") {
@@ -114,7 +119,9 @@ int main(int argc, char **argv)
                      "        --reuse (with --list --visible): a second frame by draw_list_if on the first one's counts;\n"
                      "        --materials (with --list --deferred): a texture slot and a flat colour per object, one shade_items;\n"
                      "        --occlusion (with --list): an occluder in front of part of the list, box proxies queried against its depth\n"
-                     "        (query_pixels), and only the objects whose proxy passed drawn (draw_list_if))\n";
+                     "        (query_pixels), and only the objects whose proxy passed drawn (draw_list_if);\n"
+                     "        --boxes (with --list): the same occluder, the objects' bounds computed on the device (list_bounds), their boxes\n"
+                     "        tested against the depth pyramid (query_boxes: no proxy pass), and only the objects it keeps drawn)\n";
         return 2;
     }
     const int a0 = assets ? 4 : 5;                                             // index of W
@@ -172,6 +179,59 @@ int main(int argc, char **argv)
                 m[14] = -0.25f * (float)(i % 3);
             }
         } else if (list) models.assign(1, model);
+        if (boxes) {
+            // The loop of --occlusion without the proxy pass: the occluder, then -- no host wait in between -- query_boxes over the
+            // objects' own list (bounds from list_bounds: nothing of the mesh is read on the host) and draw_list_if on its answer.
+            const uint64_t n = models.size();
+            const frr::DrawList objects = renderer.upload_draw_list(std::vector<frr::Mesh>((size_t)n, mesh), models);
+            std::vector<float> lo_hi; std::vector<uint32_t> flags;
+            renderer.list_bounds(objects, lo_hi, flags);                                        // on the device, once per distinct mesh
+            frr::Mat4 occluder = frr::set_identity();
+            occluder[12] = 0.9f; occluder[13] = -0.1f; occluder[14] = 1.0f;
+            auto draw_occluder = [&] {
+                std::memcpy(renderer.uniforms.model, occluder.data(), 64); renderer.set_uniforms();
+                renderer.draw(mesh, FRR_PS_PHONG);
+                std::memcpy(renderer.uniforms.model, model.data(), 64); renderer.set_uniforms();
+            };
+            frr::FrameBuffer all = frr::FrameBuffer::create(W, H);
+            std::vector<float> all_depth, depth, occ_depth;
+            draw_occluder();
+            renderer.read_depth(occ_depth);                                                     // (for the host build of the rule, below)
+            renderer.draw_list(objects, FRR_PS_PHONG);                                          // the frame that draws everything
+            renderer.read_frame_buffer(all);
+            renderer.read_depth(all_depth);
+            uint32_t *dev = nullptr;
+            if (hipMalloc((void **)&dev, (size_t)(n ? n : 1) * 2 * sizeof(uint32_t)) != 0) { std::cerr << "hipMalloc failed\n"; return 1; }
+            renderer.clear({30, 30, 30, 255}, 0.0f);
+            draw_occluder();
+            renderer.query_boxes(objects, dev, n);                                              // can the object change a pixel of what is there?
+            renderer.draw_list_if(objects, dev, n, FRR_PS_PHONG);                               // keep[i] >= 1
+            renderer.visible_pixels(FRR_PER_ITEM, dev + n, n);
+            renderer.read_frame_buffer(frame_buffer);                                           // (the first host wait of the loop)
+            renderer.read_depth(depth);
+            std::vector<uint32_t> host((size_t)n * 2, 0u), rule((size_t)n, 0u);
+            if (n && hipMemcpy(host.data(), dev, host.size() * sizeof(uint32_t), 2 /* device to host */) != 0) { std::cerr << "hipMemcpy failed\n"; return 1; }
+            // the status of every item, by the host build of the rule over the occluder's depth: the values have to be the device's
+            std::vector<float> mvps((size_t)n * 16);
+            std::vector<int32_t> srl((size_t)n * 6, 0);
+            for (size_t k = 0; k < (size_t)n; ++k) frr_host_instance_mvp(renderer.uniforms.proj, renderer.uniforms.view, models[k].data(), &mvps[16 * k]);
+            if (frr_host_query_boxes(mvps.data(), lo_hi.data(), flags.data(), n, W, H, 0, (int32_t)W, 0, (int32_t)H, occ_depth.data(), occ_depth.size(), nullptr,
+                                     rule.data(), n, srl.data()) != (int64_t)n) { std::cerr << "frr_host_query_boxes failed\n"; return 1; }
+            static const char *const names[5] = {"none", "outside", "hidden", "kept", "unbounded"};
+            size_t skipped = 0;
+            for (size_t k = 0; k < (size_t)n; ++k) {
+                std::printf("item %zu: %s, value %u, visible pixels %u\n", k, names[srl[6 * k]], host[k], host[(size_t)n + k]);
+                skipped += host[k] == 0u;
+                if (host[k] != rule[k]) { std::cerr << "item " << k << ": the device's value differs from the host build's\n"; return 3; }
+                if (host[(size_t)n + k] > host[k]) { std::cerr << "item " << k << ": owns more pixels than the query promised\n"; return 3; }
+            }
+            const bool same_colour = frame_buffer.get_data() == all.get_data();
+            const bool same_depth = depth.size() == all_depth.size() && std::memcmp(depth.data(), all_depth.data(), depth.size() * sizeof(float)) == 0;
+            std::printf("boxes: skipped %zu of %zu items, colour equal: %s, depth equal: %s\n", skipped, (size_t)n, same_colour ? "yes" : "no", same_depth ? "yes" : "no");
+            (void)hipFree(dev);
+            std::ofstream(out_rgba, std::ios::binary).write(reinterpret_cast<const char *>(frame_buffer.get_data().data()), frame_buffer.get_size());
+            return 0;
+        }
         if (occlusion) {
             // An occluder in front of part of the list; then, with no host wait in between: the box proxies of all objects queried
             // against its depth, the objects whose proxy passed drawn, what ended up on screen counted (with

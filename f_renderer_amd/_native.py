@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("FRR_LIB") or os.path.join(_HERE, "libfrr_hip.so")  # FRR_LIB: developer override
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_rules.h", "frr_proof.h", "frr_lines.h", "frr_varyings.h", "frr_shade.h", "frr_visible.h", "frr_query.h", "frr_own.h")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("frr_api.hip", "frr_kernels.h", "frr_raster.h", "frr_device.h", "frr_exact.h", "frr_tile_order.h", "frr_rules.h", "frr_proof.h", "frr_lines.h", "frr_varyings.h", "frr_shade.h", "frr_visible.h", "frr_query.h", "frr_boxes.h", "frr_own.h")]
 _HDR = os.path.join(_ROOT, "include", "frr.h")
 
 HIPCC_FLAGS = [
@@ -165,6 +165,11 @@ SIGNATURES = {
     "frr_query_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
     "frr_query_pixels_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "frr_host_fragment_passes": (C.c_int, [C.c_float, C.c_float]),
+    "frr_drawlist_bounds": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "frr_query_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
+    "frr_query_boxes_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "frr_host_query_boxes": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "frr_materials_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_materials_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_int)]),
     "frr_materials_free": (C.c_int, [C.c_void_p, C.c_int]),

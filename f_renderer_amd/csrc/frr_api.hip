@@ -9,6 +9,7 @@
 #include "frr_shade.h"
 #include "frr_visible.h"
 #include "frr_query.h"
+#include "frr_boxes.h"
 #include "frr_own.h"
 
 #include <math.h>
@@ -47,10 +48,10 @@ static_assert(PASS_FAN_BITS == FAN_BITS && MAX_PASS_INPUTS << FAN_BITS == 1ull <
 namespace {
 
 enum KernelId { KID_CLEAR, KID_GEOM, KID_GEOM_SCAN, KID_BIN_COUNT,
-                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_LINES_MARK, KID_LINES_PAINT, KID_VISIBLE, KID_COUNT };
+                KID_TILE_SCAN, KID_BIN_FILL, KID_RASTER, KID_BIN_SEG, KID_LINES_MARK, KID_LINES_PAINT, KID_VISIBLE, KID_BOXES, KID_COUNT };
 const char *const kKernelNames[KID_COUNT] = {"k_clear", "k_geom", "k_geom_scan",
                                              "k_bin_count", "k_tile_scan", "k_bin_fill",
-                                             "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint", "k_visible"};
+                                             "k_raster", "k_bin_seg", "k_lines_mark", "k_lines_paint", "k_visible", "k_boxes"};
 
 struct Mesh {
     DevBuf<float> own_dev; DevBuf<uint32_t> own_idx;   // a host upload: the library's copies (dev / idx point at them); else empty, and dev AND idx are the caller's
@@ -95,6 +96,9 @@ struct DrawList {
     DevBuf<ListRow> rows;          // [n] GeomArgs::items
     DevBuf<uint32_t> first;        // [2 n] first[n] | ntris[n]: GeomArgs::item_first / item_ntris
     DevBuf<float> models;          // [n][16] the k_instance_mvp input
+    std::vector<ListRow> hrows;    // [n] the host's copy of `rows` (frr_drawlist_bounds: the distinct meshes of the snapshot)
+    // frr_drawlist_bounds: per item the object-space box of its mesh and the flags (frr_boxes.h); frr_query_boxes reads them
+    DevBuf<float> box_lo_hi; DevBuf<uint32_t> box_flags; bool has_bounds = false;
     std::vector<int> mesh; std::vector<uint64_t> mesh_gen;   // [n] who the rows were taken from (frr_mesh_free)
     uint64_t n = 0, total = 0;     // items, and the sum of their triangle counts (< 2^27)
     int vs = FRR_VS_CLIP;          // the one vertex shader of all items (no items: any pixel shader goes with nothing)
@@ -258,11 +262,11 @@ struct FrameState {
 };
 
 struct Cmd {
-    enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE, SHADE_ITEMS } kind;
-    // GEOM and RASTER own device tables (GeomTab / BinTab), which finish() resets before it replays them.  The other five run
-    // behind a geometry pass, own none, and are replayed by running them again; what tells them apart is two traits -- does the
-    // command read the latest pass's tables (VARY, VISIBLE, SHADE_ITEMS, a wireframe LINES), and does it write a target
-    // (LINES, SHADE, SHADE_ITEMS): cmd_settle / cmd_stream / cmd_done
+    enum Kind { GEOM, RASTER, LINES, VARY, SHADE, VISIBLE, SHADE_ITEMS, BOXES } kind;
+    // GEOM and RASTER own device tables (GeomTab / BinTab), which finish() resets before it replays them.  The other six own
+    // none and are replayed by running them again; what tells them apart is two traits -- does the command read the latest
+    // pass's tables (VARY, VISIBLE, SHADE_ITEMS, a wireframe LINES), and does it write a target (LINES, SHADE, SHADE_ITEMS);
+    // BOXES does neither: cmd_settle / cmd_stream / cmd_done
     bool owns_table() const { return kind == GEOM || kind == RASTER; }
     FrameState pre;            // host state before the command
     uint32_t seq = 0;          // sequence number of its latest execution
@@ -291,6 +295,7 @@ struct Cmd {
     // frr_query_pixels: a RASTER command that counts instead of drawing (exec_raster), with VISIBLE's unit and buffer -- or, where
     // there is nothing to rasterize, a VISIBLE command that only zeroes the buffer
     bool query = false;
+    // BOXES (frr_query_boxes): the window in x0 .. y1, the list in list / list_gen, proj * view of the call in pv, VISIBLE's buffer
     int par = 0;               // the parity it ran with (finish(): which table a failed command left behind; LINES: of the geometry pass a wireframe read)
     int set = 0;               // RASTER: the BinSet it ran with
     int lane = 0;              // the lane of device tables it ran in
@@ -417,6 +422,10 @@ struct frr_ctx {
     // (as line_owner); commands of one stream follow each other, and every one builds the table again
     DevBuf<uint32_t> vis_bounds[3];
     uint32_t visible_lds_bins = 0;  // option visible_lds_bins (0: VIS_LDS_BINS)
+    // frr_query_boxes: the depth pyramid of a command in flight, one per stream that can carry one (as vis_bounds); every
+    // command builds it again.  Sized by the window before the command is logged, so a replay never grows it.
+    DevBuf<uint32_t> box_pyr[3];
+    uint32_t box_bounds_chunks = 0; // option box_bounds_chunks: cap on the workgroups per mesh of k_box_bounds (0: 1,024; the tests' hook for its stride loop)
     // per lane of device tables: the latest wireframe reads its geometry pass's fan cursors, which the next pass IN THAT LANE
     // zeroes (geom_bookkeeping), whatever workspace set it writes; the other lane's frame shares nothing with it
     ReaderFence wire_reader[2];
@@ -1590,6 +1599,74 @@ int exec_shade(frr_ctx *c, Cmd &cmd)
     return FRR_OK;
 }
 
+// frr_query_boxes: the pyramid of the window's depth (k_box_base, k_box_top), then the test of every item of the list against
+// it (k_box_test; frr_boxes.h).  It reads no pass and writes no target.  The levels: the first from BOX_LEVEL_MIN at which
+// four cells span the window in both directions is the last.  Every extent grows with the window, so the layout of the
+// whole viewport bounds the cells of any window: the buffer is allocated at that size on first use and never grown.
+BoxPyramid box_pyramid_layout(int64_t ww, int64_t wh, size_t *cells)
+{
+    BoxPyramid p;
+    memset(&p, 0, sizeof p);
+    const uint32_t tx = (uint32_t)((ww + TILE - 1) / TILE), ty = (uint32_t)((wh + TILE - 1) / TILE);
+    int top = BOX_LEVEL_MIN;
+    while (((ww - 1) >> top) > 3 || ((wh - 1) >> top) > 3) ++top;
+    p.top = top;
+    size_t at = 0;
+    for (int s = BOX_LEVEL_MIN; s <= std::max(top, (int)BOX_LEVEL_TILE); ++s) {   // (the base pass always writes its four levels)
+        if (s <= BOX_LEVEL_TILE) { p.lw[s] = tx << (BOX_LEVEL_TILE - s); p.lh[s] = ty << (BOX_LEVEL_TILE - s); }
+        else {
+            const int k = s - BOX_LEVEL_TILE;
+            p.lw[s] = (tx + (1u << k) - 1u) >> k; p.lh[s] = (ty + (1u << k) - 1u) >> k;
+            p.top_cells += p.lw[s] * p.lh[s];
+        }
+        p.off[s] = (uint32_t)at;
+        at += (size_t)p.lw[s] * p.lh[s];
+    }
+    *cells = at;
+    return p;
+}
+int exec_boxes(frr_ctx *c, Cmd &cmd)
+{
+    FrameState &f = c->fs;
+    int rc;
+    if ((rc = cmd_settle(c, false)) != FRR_OK) return rc;
+    const DrawList &dl = c->lists[cmd.list];   // (checked by the call; a list cannot go, nor its table change, while the command is logged)
+    hipStream_t ts;
+    if ((rc = cmd_stream(c, false, false, &ts)) != FRR_OK) return rc;
+    const int64_t ww = (int64_t)cmd.x1 - cmd.x0, wh = (int64_t)cmd.y1 - cmd.y0;
+    BoxArgs a;
+    memset(&a, 0, sizeof a);
+    size_t cells, most;
+    a.pyr = box_pyramid_layout(ww, wh, &cells);
+    (void)box_pyramid_layout((int64_t)c->W, (int64_t)c->H, &most);
+    DevBuf<uint32_t> &pyr = c->box_pyr[stream_slot(c, ts)];
+    if ((rc = ensure(c, pyr, std::max(cells, most))) != FRR_OK) return rc;   // (new memory on the slot's first use only: no drain, no host wait)
+    a.pyr.cells = pyr;
+    a.w = BoxWindow{c->W, c->H, cmd.x0, cmd.x1, cmd.y0, cmd.y1};
+    a.tiles_x = (int32_t)((ww + TILE - 1) / TILE); a.tiles_y = (int32_t)((wh + TILE - 1) / TILE);
+    a.own = row_owner(f, a.tiles_y);
+    for (int t = 0; t < a.tiles_y; ++t) {
+        if (owns_tile_row(t, a.own)) a.window_owned_rows += (uint32_t)std::min<int64_t>(TILE, wh - (int64_t)t * TILE);
+    }
+    a.depth = f.bound.depth; a.depth_vec = ((uintptr_t)f.bound.depth & 15u) == 0u ? 1 : 0;
+    memcpy(a.pv.m, cmd.pv, sizeof a.pv.m);
+    a.models = dl.models; a.lo_hi = dl.box_lo_hi; a.flags = dl.box_flags; a.nitems = (uint32_t)dl.n;
+    a.out = cmd.vis_out; a.out_entries = cmd.vis_entries;
+    a.seq = cmd.seq; a.epoch = c->epoch; a.cnt = c->cnt;
+    {
+        ProfScope p(c, KID_BOXES, ts);
+        if (dl.n) {
+            hipLaunchKernelGGL(k_box_base, dim3((uint32_t)(a.tiles_x * a.tiles_y)), dim3(256), 0, ts, a);
+            if (a.pyr.top_cells) hipLaunchKernelGGL(k_box_top, dim3((a.pyr.top_cells + 3u) / 4u), dim3(256), 0, ts, a);
+        }
+        const uint64_t units = std::max<uint64_t>(dl.n, cmd.vis_entries);
+        hipLaunchKernelGGL(k_box_test, dim3((uint32_t)std::min<uint64_t>((units + 15) / 16, 4096)), dim3(256), 0, ts, a);
+    }
+    HIP_TRY(c, hipGetLastError());
+    cmd_done(c, cmd, false, ts);
+    return FRR_OK;
+}
+
 int finish(frr_ctx *c);
 
 // run a command and remember it (finish() replays the commands from a failed one onwards)
@@ -1611,6 +1688,7 @@ int exec_cmd(frr_ctx *c, Cmd cmd)
     case Cmd::VARY: rc = exec_vary(c, cmd); break;
     case Cmd::VISIBLE: rc = exec_visible(c, cmd); break;
     case Cmd::SHADE: case Cmd::SHADE_ITEMS: rc = exec_shade(c, cmd); break;
+    case Cmd::BOXES: rc = exec_boxes(c, cmd); break;
     }
     if (rc != FRR_OK) { c->fs = cmd.pre; c->verify_pending = false; return rc; }
     c->log.push_back(cmd);
@@ -1913,6 +1991,7 @@ int frr_set_option(frr_ctx *c, const char *name, int64_t v)
     else if (n == "overlap") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "overlap: 0, 1 or 2"); c->overlap = (int)v; }
     else if (n == "bound_targets_in_flight") c->bound_in_flight = v != 0;
     else if (n == "tile_order") { if (v < 0 || v > 2) return fail(c, FRR_ERR_INVALID, "tile_order: 0, 1 or 2"); c->tile_order = (int)v; }
+    else if (n == "box_bounds_chunks") { if (v < 0 || v > 1024) return fail(c, FRR_ERR_INVALID, "box_bounds_chunks: 0 .. 1024"); c->box_bounds_chunks = (uint32_t)v; }
     else if (n == "visible_lds_bins") { if (v < 0 || v > (int64_t)VIS_LDS_BINS) return fail(c, FRR_ERR_INVALID, "visible_lds_bins: 0 .. VIS_LDS_BINS"); c->visible_lds_bins = (uint32_t)v; }
     else if (n == "lines_chunk") { if (v < 0 || v > (int64_t)LINES_CHUNK) return fail(c, FRR_ERR_INVALID, "lines_chunk: 0 .. 2^24"); c->lines_chunk = (uint32_t)v; }
     else if (n == "frames_in_flight") { if (v != 1 && v != 2) return fail(c, FRR_ERR_INVALID, "frames_in_flight: 1 or 2"); c->frames_in_flight = (int)v; }
@@ -2492,6 +2571,7 @@ int frr_drawlist_upload(frr_ctx *c, const frr_draw_item *items, uint64_t nitems,
         if (rc == FRR_OK) rc = upload(c, l.models, models.data(), models.size() * sizeof(float), "draw list");
         if (rc != FRR_OK) return rc;
     }
+    l.hrows = std::move(rows);
     l.n = nitems; l.total = total; l.used = true; l.gen = ++c->list_gen;
     *list_out = slot_put(c->lists, std::move(l));
     return FRR_OK;
@@ -2848,6 +2928,102 @@ int frr_query_pixels_host(frr_ctx *c, int unit, int32_t x0, int32_t x1, int32_t 
 }
 
 int frr_host_fragment_passes(float rhw, float depth) { return fragment_passes(rhw, depth) ? 1 : 0; }
+
+// ---- box queries (frr_boxes.h) -----------------------------------------------------------------------------------------
+int frr_drawlist_bounds(frr_ctx *c, int list, float *host_lo_hi, uint32_t *host_flags, uint64_t cap, uint64_t *nitems)
+{
+    if (!c || !slot_ok(c->lists, list)) return fail(c, FRR_ERR_INVALID, "bad draw list id");
+    if (c->lists[list].dead) return fail(c, FRR_ERR_INVALID, "a mesh the draw list names was freed: the list is dead (frr_drawlist_free still takes it)");
+    const uint64_t n = c->lists[list].n;
+    int rc = n ? rule_rc(c, bounds_rule(c->lists[list].vs)) : FRR_OK;
+    if (rc != FRR_OK) return rc;
+    // a table of this list may be read by a command in flight or in the log: nothing reads it any more after this
+    if ((rc = finish(c)) != FRR_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DrawList &dl = c->lists[list];
+    dl.has_bounds = false;
+    if (nitems) *nitems = n;
+    if (n == 0) { dl.has_bounds = true; return FRR_OK; }
+    // the distinct meshes of the snapshot: one reduction each
+    const uint32_t nf = (uint32_t)frr_vs_input_floats(dl.vs);
+    std::vector<BoundsJob> jobs;
+    std::vector<uint32_t> item_job(n), keys;
+    std::map<std::pair<const void *, std::pair<const void *, uint64_t>>, uint32_t> seen;
+    uint32_t most = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const ListRow &r = dl.hrows[i];
+        const auto key = std::make_pair((const void *)r.verts, std::make_pair((const void *)r.idx, ((uint64_t)r.nverts << 32) | r.ntris));
+        auto it = seen.find(key);
+        if (it == seen.end()) {
+            it = seen.emplace(key, (uint32_t)jobs.size()).first;
+            jobs.push_back(BoundsJob{r.verts, r.idx, r.nverts, r.ntris, nf, 0u});
+            most = std::max(most, r.ntris);
+        }
+        item_job[i] = it->second;
+    }
+    keys.resize(jobs.size() * 8);
+    for (size_t j = 0; j < jobs.size(); ++j) for (int k = 0; k < 8; ++k) keys[8 * j + k] = k < 3 ? 0xFFFFFFFFu : 0u;
+    DevBuf<BoundsJob> djobs; DevBuf<uint32_t> ditem, dkeys; DevBuf<float> lo_hi; DevBuf<uint32_t> flags;
+    if (lo_hi.reset((size_t)n * 6) != hipSuccess || flags.reset((size_t)n) != hipSuccess) return nomem(c, "bounds table");
+    if ((rc = upload(c, djobs, jobs.data(), jobs.size() * sizeof(BoundsJob), "bounds jobs", false)) != FRR_OK) return rc;
+    if ((rc = upload(c, ditem, item_job.data(), item_job.size() * sizeof(uint32_t), "bounds jobs", false)) != FRR_OK) return rc;
+    if ((rc = upload(c, dkeys, keys.data(), keys.size() * sizeof(uint32_t), "bounds jobs", false)) != FRR_OK) return rc;
+    // on the ctx's stream, behind what the caller has put there (a device-bound mesh's vertices), as k_index_check runs
+    {
+        ProfScope p(c, KID_BOXES, c->stream);
+        const uint32_t chunks = std::min<uint32_t>((most + BOX_WG_TRIS - 1) / BOX_WG_TRIS, c->box_bounds_chunks ? c->box_bounds_chunks : 1024u);
+        if (chunks) hipLaunchKernelGGL(k_box_bounds, dim3(chunks, (uint32_t)jobs.size()), dim3(BOX_WG), 0, c->stream, djobs.get(), dkeys.get());
+        hipLaunchKernelGGL(k_box_bounds_finish, dim3((uint32_t)((n + BOX_WG - 1) / BOX_WG)), dim3(BOX_WG), 0, c->stream, dkeys.get(), ditem.get(), djobs.get(), (uint32_t)n, lo_hi.get(), flags.get());
+    }
+    hipError_t e = hipGetLastError();
+    const uint64_t take = std::min<uint64_t>(cap, n);
+    if (e == hipSuccess && host_lo_hi && take) e = hipMemcpyAsync(host_lo_hi, lo_hi.get(), (size_t)take * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && host_flags && take) e = hipMemcpyAsync(host_flags, flags.get(), (size_t)take * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_rc(c, e);
+    dl.box_lo_hi = std::move(lo_hi); dl.box_flags = std::move(flags); dl.has_bounds = true;
+    return FRR_OK;
+}
+
+// frr_query_boxes*: the argument checks, the command, and with `host` its round trip through a temporary device buffer
+static int query_boxes(frr_ctx *c, bool host, int list, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *out, uint64_t out_entries, uint64_t *nunits)
+{
+    if (!c || !slot_ok(c->lists, list)) return fail(c, FRR_ERR_INVALID, "bad draw list id");
+    const DrawList &dl = c->lists[list];
+    if (dl.dead) return fail(c, FRR_ERR_INVALID, "a mesh the draw list names was freed: the list is dead (frr_drawlist_free still takes it)");
+    int rc = rule_rc(c, boxes_rule(dl.has_bounds));
+    if (rc == FRR_OK) rc = rule_rc(c, window_rule(WINDOW_ENTRIES, c->W, c->H, x0, x1, y0, y1));
+    if (rc == FRR_OK) rc = rule_rc(c, buffer_rule(BUFFER_COUNTS_OUT, out, out_entries, 0, x1, y0, y1));
+    if (rc != FRR_OK || out_entries == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Cmd cmd = new_cmd(c, Cmd::BOXES, x0, x1, y0, y1);
+    cmd.list = list; cmd.list_gen = dl.gen;
+    h_mat4_mul(c->uni.proj, c->uni.view, cmd.pv);   // as list_cmd takes it: the list pass's mvp = pv * model
+    cmd.vis_out = host ? nullptr : (uint32_t *)out; cmd.vis_entries = out_entries;
+    if (!host) return exec_cmd(c, cmd);
+    DevBuf<uint32_t> tmp;
+    if (tmp.reset((size_t)out_entries) != hipSuccess) return nomem(c, "count buffer");
+    rc = host_round_trip(c, cmd, &Cmd::vis_out, tmp, (uint32_t *)out, (size_t)out_entries * sizeof(uint32_t), "box counts");
+    if (rc == FRR_OK && nunits) *nunits = c->lists[list].n;
+    return rc;
+}
+int frr_query_boxes(frr_ctx *c, int list, int32_t x0, int32_t x1, int32_t y0, int32_t y1, void *dev_out_u32, uint64_t out_entries)
+{
+    return query_boxes(c, false, list, x0, x1, y0, y1, dev_out_u32, out_entries, nullptr);
+}
+int frr_query_boxes_host(frr_ctx *c, int list, int32_t x0, int32_t x1, int32_t y0, int32_t y1, uint32_t *host_out, uint64_t out_entries, uint64_t *nunits)
+{
+    return query_boxes(c, true, list, x0, x1, y0, y1, host_out, out_entries, nunits);
+}
+int64_t frr_host_query_boxes(const float *mvps, const float *lo_hi, const uint32_t *flags, uint64_t nitems, uint32_t W, uint32_t H,
+                             int32_t x0, int32_t x1, int32_t y0, int32_t y1, const float *depth, uint64_t depth_entries, const uint8_t *row_owned,
+                             uint32_t *out, uint64_t out_entries, int32_t *status_rect_level)
+{
+    if ((nitems && (!mvps || !lo_hi || !flags)) || !depth || (out_entries && !out)) return -1;
+    if (window_rule(WINDOW_ENTRIES, W, H, x0, x1, y0, y1).code != FRR_OK) return -1;
+    if ((uint64_t)((int64_t)y1 - y0 - 1) * (uint64_t)x1 + (uint64_t)((int64_t)x1 - x0) > depth_entries) return -1;   // the last entry the window reads
+    return box_host_query(mvps, lo_hi, flags, nitems, BoxWindow{W, H, x0, x1, y0, y1}, depth, row_owned, out, out_entries, status_rect_level);
+}
 
 int64_t frr_host_visible_counts(const uint32_t *ids, uint64_t id_entries, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                                 const uint32_t *bounds, uint64_t nunits, uint32_t *out, uint64_t out_entries)

@@ -278,8 +278,8 @@ struct RasterArgs {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// does this rank rasterize tile row ty (window-local)?
-__device__ __forceinline__ bool owns_tile_row(int ty, const RowOwner &o)
+// does this rank rasterize tile row ty (window-local)?  (also the host's rule where it counts a rank's rows: exec_boxes)
+FRR_HD bool owns_tile_row(int ty, const RowOwner &o)
 {
     return o.world <= 1 || (o.blocked ? (ty >= o.brow0 && ty < o.brow1) : ty % o.world == o.rank);
 }

@@ -144,6 +144,24 @@ inline Rule keep_rule(const void *keep, uint64_t keep_entries, uint64_t nitems)
     return RULE_OK;
 }
 
+// ---- the box rules -----------------------------------------------------------------------------------------------------
+// bounds_rule  frr_drawlist_bounds: the object-space box of an item's mesh bounds what the item draws only where the vertex
+//              shader is position -> mvp * position: FRR_VS_PHONG and FRR_VS_GOURAUD.  The inputs of FRR_VS_CLIP* are clip
+//              coordinates (there is no object space), and a user vertex shader may move a vertex anywhere.
+// boxes_rule   frr_query_boxes*: the list has a bounds table (frr_drawlist_bounds succeeded on it since its upload).  Its
+//              window is a WINDOW_ENTRIES window, its buffer a BUFFER_COUNTS_OUT buffer.
+inline Rule bounds_rule(int vs_id)
+{
+    if (vs_id == FRR_VS_PHONG || vs_id == FRR_VS_GOURAUD) return RULE_OK;
+    if (vs_id >= FRR_SHADER_USER_BASE) return {FRR_ERR_UNSUPPORTED, "frr_drawlist_bounds: a user vertex shader may move a vertex anywhere, a box of its inputs bounds nothing"};
+    return {FRR_ERR_UNSUPPORTED, "frr_drawlist_bounds: the inputs of FRR_VS_CLIP* are clip coordinates, there is no object space"};
+}
+inline Rule boxes_rule(bool has_bounds)
+{
+    if (!has_bounds) return {FRR_ERR_INVALID, "the draw list has no bounds table: call frr_drawlist_bounds first"};
+    return RULE_OK;
+}
+
 // ---- the materials rule ------------------------------------------------------------------------------------------------
 // A table of frr_material (frr_materials_upload / frr_materials_bind_device) and its use by frr_shade_items*.
 // material_ok    one entry: texture_slot in 0 .. FRR_MAX_TEXTURES-1 and reserved == 0 -- the one test the host (upload) and

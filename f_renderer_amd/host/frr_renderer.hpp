@@ -540,6 +540,33 @@ public:
         return counts_on_host(frr_query_pixels_host, unit, width_range, height_range);
     }
     std::vector<uint32_t> query_pixels(int unit) { return query_pixels(unit, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // Box queries (include/frr.h: frr_drawlist_bounds, frr_query_boxes).  list_bounds: per item of the list the object-space box
+    // of its mesh -- lo_hi: 6 floats per item, lo xyz then hi xyz -- and flags (bit 0: a non-finite position, bit 1: no
+    // triangles), computed on the device; a synchronisation point.  The table stays with the list: query_boxes needs it.
+    void list_bounds(const DrawList &list, std::vector<float> &lo_hi, std::vector<uint32_t> &flags)
+    {
+        uint64_t n = 0;
+        lo_hi.assign((size_t)list.nitems * 6, 0.0f); flags.assign((size_t)list.nitems, 0u);
+        check(frr_drawlist_bounds(ctx_, list.id, lo_hi.data(), flags.data(), list.nitems, &n));
+    }
+    void list_bounds(const DrawList &list) { check(frr_drawlist_bounds(ctx_, list.id, nullptr, nullptr, 0, nullptr)); }
+    // query_boxes: per item 0 where its box lies behind the depth target as it stands or outside the window -- drawing the
+    // item now would change nothing -- else an upper bound of the pixels it can own.  Conservative, not exact; no geometry
+    // pass, no host wait.  The buffer is a keep buffer for draw_list_if as it is.
+    void query_boxes(const DrawList &list, void *dev_out_u32, uint64_t entries, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        check(frr_query_boxes(ctx_, list.id, width_range.first, width_range.second, height_range.first, height_range.second, dev_out_u32, entries));
+    }
+    void query_boxes(const DrawList &list, void *dev_out_u32, uint64_t entries) { query_boxes(list, dev_out_u32, entries, {0, (int32_t)width_}, {0, (int32_t)height_}); }
+    // the same on the host (a synchronisation point): one value per item of the list
+    std::vector<uint32_t> query_boxes(const DrawList &list, std::pair<int32_t, int32_t> width_range, std::pair<int32_t, int32_t> height_range)
+    {
+        std::vector<uint32_t> out((size_t)list.nitems, 0u);
+        uint64_t n = 0;
+        if (!out.empty()) check(frr_query_boxes_host(ctx_, list.id, width_range.first, width_range.second, height_range.first, height_range.second, out.data(), out.size(), &n));
+        return out;
+    }
+    std::vector<uint32_t> query_boxes(const DrawList &list) { return query_boxes(list, {0, (int32_t)width_}, {0, (int32_t)height_}); }
     void sync() { check(frr_sync(ctx_)); }
     // stream-side ordering against a caller's hipStream_t (nullptr: the renderer's own), no host wait: frame_fence -- the stream
     // waits for every frame issued so far; frame_wait -- the next write of the frame targets waits for what the stream holds now

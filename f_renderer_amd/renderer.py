@@ -254,6 +254,35 @@ def host_entry_items(ids, width_range, height_range, bounds):
     return out, int(rounds)
 
 
+BOX_NONE, BOX_OUTSIDE, BOX_HIDDEN, BOX_KEPT, BOX_UNBOUNDED = 0, 1, 2, 3, 4   # status of frr_host_query_boxes (frr_boxes.h: BoxStatus)
+
+
+def host_query_boxes(mvps, lo_hi, flags, size, window, depth, row_owned=None, entries=None):
+    """The whole rule of frr_query_boxes over host arrays, by the host build of the header the kernels compile
+    (frr_host_query_boxes): mvps float32 [n, 16], lo_hi float32 [n, 6], flags uint32 [n]; size = (W, H), the viewport;
+    window = (x0, x1, y0, y1); depth float32, entry (cy - y0) * x1 + (cx - x0); row_owned: None, or one byte per
+    window-local tile row.  Returns (out uint32 [entries, default n], status_rect_level int32 [n, 6])."""
+    m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+    b = np.ascontiguousarray(lo_hi, np.float32).reshape(-1, 6)
+    f = np.ascontiguousarray(flags, np.uint32).reshape(-1)
+    d = np.ascontiguousarray(depth, np.float32).reshape(-1)
+    n = f.size
+    if m.shape[0] != n or b.shape[0] != n:
+        raise FrrError(N.FRR_ERR_INVALID, "host_query_boxes: one matrix, one box and one flag word per item")
+    ro = None if row_owned is None else np.ascontiguousarray(row_owned, np.uint8).reshape(-1)
+    x0, x1, y0, y1 = (int(v) for v in window)
+    if ro is not None and ro.size < (max(y1 - y0, 0) + 31) // 32:
+        raise FrrError(N.FRR_ERR_INVALID, "host_query_boxes: one row_owned byte per tile row of the window")
+    out = np.full(n if entries is None else int(entries), 0xDEADBEEF, np.uint32)
+    srl = np.zeros((n, 6), np.int32)
+    rc = N.lib().frr_host_query_boxes(m.ctypes.data if n else None, b.ctypes.data if n else None, f.ctypes.data if n else None, n, int(size[0]), int(size[1]),
+                                      x0, x1, y0, y1, d.ctypes.data, d.size, None if ro is None else ro.ctypes.data,
+                                      out.ctypes.data if out.size else None, out.size, srl.ctypes.data if n else None)
+    if rc < 0:
+        raise FrrError(N.FRR_ERR_INVALID, "host_query_boxes: bad window or arrays")
+    return out, srl
+
+
 def host_instance_mvp(proj, view, model):
     """(proj * view) * model as the device computes it per instance (frr_host_instance_mvp): float32 [16], column-major."""
     p, v, m = (np.ascontiguousarray(x, np.float32).reshape(16) for x in (proj, view, model))
@@ -609,6 +638,37 @@ class Renderer:
         hr = height_range or (0, self.height)
         self._check(self._lib.frr_draw_list_if(self._ctx, draw_list.id, keep_ptr, entries, min_value, pixel_shader, wr[0], wr[1], hr[0], hr[1]))
 
+    def list_bounds(self, draw_list):
+        """(lo_hi float32 [nitems, 6], flags uint32 [nitems]): per item of the list the object-space box of the positions
+        its mesh's triangles name -- lo xyz, hi xyz -- and flags, bit 0: a position is NaN or infinite, bit 1: the mesh has no
+        triangles (frr_drawlist_bounds; computed on the device, a synchronisation point).  The table stays with the list:
+        query_boxes needs it."""
+        n = C.c_uint64()
+        lo_hi, flags = np.zeros((draw_list.nitems, 6), np.float32), np.zeros(draw_list.nitems, np.uint32)
+        self._check(self._lib.frr_drawlist_bounds(self._ctx, -1 if draw_list.id is None else draw_list.id, lo_hi.ctypes.data if lo_hi.size else None,
+                                                  flags.ctypes.data if flags.size else None, draw_list.nitems, C.byref(n)))
+        return lo_hi, flags
+
+    def query_boxes(self, draw_list, out_ptr=None, entries=None, window=None):
+        """The box query (frr_query_boxes): per item of the list 0 where the item's box, under the item's matrix and the
+        current view and projection, lies behind the depth target as it stands or outside window = (x0, x1, y0, y1)
+        (default: the frame) -- drawing the item now would change nothing -- else an upper bound of the pixels it can own.
+        Conservative, not exact; needs list_bounds(draw_list) first.  With `out_ptr` (device memory of `entries` uint32) it
+        is a command on the frame's stream with no host wait and returns nothing: the buffer is a keep buffer for
+        draw_list_if as it is.  Without `out_ptr` it is the host form (a synchronisation point) and returns a uint32 array
+        of the list's items, or of `entries` of them."""
+        win = tuple(int(v) for v in (window or (0, self.width, 0, self.height)))
+        lid = -1 if draw_list.id is None else draw_list.id
+        if out_ptr is not None:
+            if entries is None:
+                raise FrrError(N.FRR_ERR_INVALID, "query_boxes: the device form needs the buffer's entries")
+            self._check(self._lib.frr_query_boxes(self._ctx, lid, *win, C.c_void_p(out_ptr), int(entries)))
+            return None
+        out = np.zeros(draw_list.nitems if entries is None else int(entries), np.uint32)
+        n = C.c_uint64()
+        self._check(self._lib.frr_query_boxes_host(self._ctx, lid, *win, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
     def item_ranges(self, cap=None):
         """(first, count), uint32 arrays: per item of the latest geometry pass -- the items of a list pass, the instances of
         an instanced pass, one item for a plain pass -- the triangle id of its first setup triangle and how many it emitted
@@ -808,11 +868,13 @@ class Renderer:
 
     # the order of the profile's mask bits: KERNELS, the kernels of a frame, then what was appended since
     PROFILE_ORDER = KERNELS + ("k_visible",)
+    # ... and the bits behind those (frr_profile_get's list goes on: the bits above keep their meaning)
+    PROFILE_APPENDED = ("k_boxes",)
 
     def profile_enable(self, on=True, kernels=None, period=1):
         """Bracket launches with HIP events: all kernels (on=True), none (False) or the named ones; only every
         `period`-th launch of each (an event pair costs the stream ~4 us)."""
-        mask = (-1 if on else 0) if kernels is None else sum(1 << self.PROFILE_ORDER.index(k) for k in kernels)
+        mask = (-1 if on else 0) if kernels is None else sum(1 << (self.PROFILE_ORDER + self.PROFILE_APPENDED).index(k) for k in kernels)
         self._check(self._lib.frr_profile_set_period(self._ctx, period))
         self._check(self._lib.frr_profile_enable(self._ctx, mask))
 

@@ -750,6 +750,79 @@ int frr_query_pixels_host(frr_ctx *ctx, int unit, int32_t x0, int32_t x1, int32_
 /* host build of the query's depth test (cf. frr_host_list_item): 1 iff a fragment of that rhw passes against that depth */
 int frr_host_fragment_passes(float rhw, float depth);
 
+/* ---- box queries ------------------------------------------------------------------------------- */
+/* The cheap occlusion test: per item of a draw list the object-space box of its mesh, projected under the item's own matrix,
+ * against the farthest depth stored under its screen rectangle.  No geometry pass, no binning, no work list, no host wait.
+ * The test is conservative: out[i] == 0 implies that drawing item i now changes no entry of colour, depth or ids, and out[i]
+ * is an upper bound of what frr_visible_pixels(FRR_PER_ITEM) can report for the item after it is drawn now -- so the buffer is
+ * a keep buffer for frr_draw_list_if (min_value 1), and with a larger min_value contribution culling before anything is drawn.
+ * It is not exact: an item it keeps may still own no pixel (frr_query_pixels of the item's own mesh answers that).
+ *
+ * frr_drawlist_bounds: per item the object-space AABB lo, hi of the positions (floats 0..2 of a vertex record) of the corners
+ * its triangles name -- for an indexed mesh the corners gathered through the indices, clamped as the geometry kernels clamp,
+ * so an unreferenced vertex does not widen the box -- and flags: bit 0, some referenced component is NaN or +-inf (lo / hi are
+ * then unspecified); bit 1, the mesh has no triangles (lo / hi are zeros).  -0.0 is reported as +0.0.  Computed on the device,
+ * once per distinct mesh of the list's snapshot, in integer atomics only (two runs give the same bytes); on the ctx's stream
+ * behind what it holds, and the call waits for it on the host (a set-up call and a synchronisation point, like
+ * frr_mesh_bind_device_indexed's check).  The table stays with the list until frr_drawlist_free; a second call computes it
+ * again (after an in-place rewrite of a device-bound mesh: fence, rewrite, bind again, upload the list again, then this).
+ * host_lo_hi ([cap][6]: lo xyz, hi xyz) and host_flags ([cap]) receive min(cap, n) items where not NULL; *nitems receives n.
+ * Errors: FRR_ERR_INVALID for an unknown, freed or dead list; FRR_ERR_UNSUPPORTED, and no table is stored, where the list's
+ * vertex shader is not FRR_VS_PHONG or FRR_VS_GOURAUD -- the inputs of FRR_VS_CLIP* are clip coordinates, there is no object
+ * space, and a user vertex shader may move a vertex anywhere, so a box of its inputs bounds nothing.  A list without items is
+ * valid whatever its shader.
+ *
+ * frr_query_boxes: for item i with lo, hi, flags and mvp_i = (proj * view) * items[i].model (the arithmetic of
+ * frr_host_instance_mvp: the bits the list pass transforms the item with; proj, view the uniforms of the call; the viewport is
+ * the ctx's W, H), in f32 with the written association (f_renderer_amd/csrc/frr_boxes.h is the definition):
+ *   NONE       flag bit 1: out = 0.
+ *   corners    corner j = 0..7 (bit k of j picks hi[k]): clip_j = mvp_i * (c, 1), rhw, ndc, spf, spi by renderer.rs:223-234.
+ *   E          = |mvp_i| * (a, 1) * 2^-21, a = max(|lo|, |hi|) per axis: twice the rounding error of any vertex's clip position.
+ *   UNBOUNDED  flag bit 0; a clip component, an ndc or E not finite; a corner with z_j - E_z < 0 (the reference's near-plane
+ *              intersection, renderer.rs:70, leaves the triangle) or w_j - E_w <= 0; wmin - 2 E_w <= 0; a guard of 2^15 or
+ *              more.  out = the window's pixels.
+ *   rectangle  [min spi.x - Gx, max spi.x + Gx) x [min spi.y - Gy, max spi.y + Gy) clamped to the window; G = 1 + (int)d,
+ *              d = eps * D + (n + 1) * D * 2^-21, eps = (E_axis + n * E_w) / (wmin - 2 E_w) + n * 2^-21, n the corners' largest
+ *              |ndc| on the axis and D = W or H.  Empty: OUTSIDE, out = 0.
+ *   zub        = (1 / (wmin - E_w)) * (1 + 2^-18): no fragment of the item has a larger rhw.
+ *   region     in window-local coordinates the smallest level s >= 2 at which the rectangle touches at most 4 x 4 cells of
+ *              2^s x 2^s pixels; dmin = the smallest depth key (a NaN depth below everything) over those cells cut to the window,
+ *              depth[(cy - y0) * x1 + (cx - x0)] (renderer.rs:362).
+ *   verdict    HIDDEN iff key(zub) < dmin, strictly (a tie keeps, as the depth test lets ties pass): out = 0; else KEPT: out =
+ *              the pixels of the clamped rectangle.
+ * Units: n = the list's items; unit k < min(n, out_entries) gets its value, entries at and beyond n get 0, a unit >=
+ * out_entries is written nowhere.  A command on the current frame's stream like frr_visible_pixels: behind the draws issued
+ * so far and in front of those issued after it; it settles a pending frr_clear first (never fused), reads the current target
+ * set (own or caller-bound, one or two frames in flight), writes no target, touches no field of frr_stats, leaves the latest
+ * geometry pass as it is and waits for nothing on the host.  It is logged and replayed: behind a failed command it writes
+ * nothing and runs again with it, under the uniforms of the call.  A later frr_draw_list_if of this ctx that names the buffer
+ * is already ordered behind it; the caller orders its own reads with frr_frame_fence or frr_sync.
+ * On a partitioned ctx the region, the rectangle's pixels and the window's pixels are those of the tile rows this rank owns
+ * (an item with none: OUTSIDE): the answer is the rank's own, "would this item change a pixel of mine", which is what the
+ * rank's frr_draw_list_if needs.  The ranks' values do NOT add up to the unpartitioned ones.
+ * frr_query_boxes_host: the same through a temporary device buffer into host memory; a synchronisation point; *nunits
+ * (optional) receives n.
+ * Errors: the list errors of frr_draw_list (FRR_ERR_INVALID: unknown, freed or dead); FRR_ERR_INVALID for a list without a
+ * bounds table (frr_last_error names frr_drawlist_bounds); the window and buffer errors of frr_visible_pixels.  A refused call
+ * leaves the ctx drawing.  out_entries == 0 (after these checks): FRR_OK, nothing happens.
+ * The pyramid is a buffer of the ctx, allocated for the whole viewport on first use and never grown: no command waits for it.
+ * frr_profile_get("k_boxes"): the launches of both calls.  Option "box_bounds_chunks" (0 .. 1024; 0: the default, 1,024) caps
+ * the workgroups frr_drawlist_bounds gives one mesh -- a test hook for its stride loop; the table does not depend on it. */
+int frr_drawlist_bounds(frr_ctx *ctx, int list, float *host_lo_hi, uint32_t *host_flags, uint64_t cap, uint64_t *nitems);
+int frr_query_boxes(frr_ctx *ctx, int list, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                    void *dev_out_u32, uint64_t out_entries);
+int frr_query_boxes_host(frr_ctx *ctx, int list, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                         uint32_t *host_out, uint64_t out_entries, uint64_t *nunits);
+/* host build of the whole rule over arrays (no ctx, no device): mvps [nitems][16], lo_hi [nitems][6], flags [nitems]; depth
+ * addressed as above (depth_entries: how many it holds); row_owned: NULL, or one byte per window-local tile row (32 pixel
+ * rows), non-zero where the rank owns it.  The region's minimum is a plain walk over its pixels.  status_rect_level (or NULL):
+ * [nitems][6] = status (0 NONE, 1 OUTSIDE, 2 HIDDEN, 3 KEPT, 4 UNBOUNDED), the clamped rectangle rx0, ry0, rx1, ry1
+ * (window-local, inclusive) and the level.  Returns nitems, or -1 for arguments frr_query_boxes would refuse. */
+int64_t frr_host_query_boxes(const float *mvps, const float *lo_hi, const uint32_t *flags, uint64_t nitems,
+                             uint32_t W, uint32_t H, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                             const float *depth, uint64_t depth_entries, const uint8_t *row_owned,
+                             uint32_t *out, uint64_t out_entries, int32_t *status_rect_level);
+
 /* Stream-side fence, no host wait: `stream` (a hipStream_t of the caller; NULL = the ctx's stream) waits for every frame
  * issued so far, so that what the caller enqueues on it next sees their targets.  Needed with option bound_targets_in_flight
  * (below) and by callers that read the ctx's own targets (frr_target_ptrs) on a stream other than the ctx's; also the way to

@@ -126,6 +126,12 @@ pub mod ffi {
         pub fn frr_visible_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
         pub fn frr_query_pixels(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
         pub fn frr_query_pixels_host(ctx: *mut frr_ctx, unit: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
+        // box queries: per item of a list its mesh's object-space box (computed on the device), tested against the depth target
+        pub fn frr_drawlist_bounds(ctx: *mut frr_ctx, list: c_int, host_lo_hi: *mut f32, host_flags: *mut u32, cap: u64, nitems: *mut u64) -> c_int;
+        pub fn frr_query_boxes(ctx: *mut frr_ctx, list: c_int, x0: i32, x1: i32, y0: i32, y1: i32, dev_out_u32: *mut c_void, out_entries: u64) -> c_int;
+        pub fn frr_query_boxes_host(ctx: *mut frr_ctx, list: c_int, x0: i32, x1: i32, y0: i32, y1: i32, host_out: *mut u32, out_entries: u64, nunits: *mut u64) -> c_int;
+        pub fn frr_host_query_boxes(mvps: *const f32, lo_hi: *const f32, flags: *const u32, nitems: u64, w: u32, h: u32, x0: i32, x1: i32, y0: i32, y1: i32,
+                                    depth: *const f32, depth_entries: u64, row_owned: *const u8, out: *mut u32, out_entries: u64, status_rect_level: *mut i32) -> i64;
         pub fn frr_host_list_item(first: *const u32, ntris: *const u32, nitems: u64, t: u32) -> i64;
         // per-item materials: one shade of all the items of the latest geometry pass, each under its own frr_material
         pub fn frr_materials_upload(ctx: *mut frr_ctx, mats: *const frr_material, n: u64, materials_out: *mut c_int) -> c_int;
