@@ -46,6 +46,23 @@ a further frr_raster behind it are Undefined (FRR_ERR_INVALID) until the next ge
 partitioned mode refuses, it computes nothing else: the model is the UNPARTITIONED frame, which the ranks' parts must stitch to.
 run_rank() is one rank's part of a frame, for the fixed sequence line_ownership().
 
+The query sequences.  generate(seed, queries=True) for seed in QSEEDS yields the extended sequences plus (the sequences of
+SEEDS and XSEEDS stay as they were: two digests are pinned):
+  query         {unit, buf, entries}: frr_query_pixels over the latest pass in the frame's window -- per setup triangle the
+                entries rasterization(t) ALONE changes on a copy of the frame's depth at this step (query_reference.counts_c; the
+                NumPy oracle's counts asserted equal where the pass is no rung), summed per item or offset by the pass's first
+                id, by frr_visible_pixels' every-entry-is-written rule.  A pass that is not rastered counts like any other; zeros
+                per item after a clear since the pass; Undefined before any pass and, partitioned, behind a fused draw*.  Targets
+                and statistics stay; it bins like frr_raster of the pass, so in front of a rung's raster it is what overflows
+  boxes         {vs, items, buf, entries}: frr_query_boxes of a draw list (any list) under the uniforms of the step:
+                box_reference.query over the frame's depth, bounds from box_reference.bounds_of of the items' meshes
+  query_host, boxes_host, bounds: the host forms and frr_drawlist_bounds, as host queries (QUERIES)
+  feeding       m.prov records what wrote a count buffer (count, query or boxes), for which list; a list_if pass may name any of
+                them, a box answer only for the list that was asked and under min_value 1.  _Gen.loop is the loop the queries are
+                for: the `cover` mesh as occluder, the query, the pass it decides, on one stream
+On a partition a rank's box answer is its own (box_answer(args, row_owned)); the ranks' answers sum to zero exactly where the
+unpartitioned answer is zero, which is what the partitioned runner's all-reduce relies on.
+
 Left out: user shaders, x0 < 0, a second raster of one geometry pass in another window (the model has one window per
 frame), state setters that change the vertex shader's uniforms between a geometry* and its rasterization, resolves behind
 the rasterization of a rung mesh (the NumPy oracle's cost).  The generator issues set_cull between passes only;
@@ -58,11 +75,13 @@ import numpy as np
 from f_renderer_amd import scenes
 from oracle import oracle_np as onp
 
+from . import box_reference as BX
 from . import cull_scenes as CS
 from . import drawlist_scenes as D
 from . import instanced_scenes as S
 from . import lines_reference as R
 from . import predicate_scenes as P
+from . import query_reference as QR
 from . import varyings_scenes as V
 from . import visible_scenes as VIS
 
@@ -89,10 +108,14 @@ PIN_VS = {"CLIP_COLOR": (3, ("DEPTH", "FLAT", "COLOR"))}   # what the generator 
 K_PS = {8: ("FLAT", "PHONG", "BLINN"), 3: ("FLAT", "COLOR")}
 KINDS = ("plain", "indexed", "instanced", "list", "list_if")
 COMMANDS = ("lines", "wireframe", "resolve", "shade", "count_item", "count_triangle")
-QUERIES = ("item_ranges", "setup_triangles", "stats", "sync")
-WRITERS = ("geom", "draw", "lines", "wireframe", "resolve", "shade", "count", "set_cull", "set_uniforms", "set_texture", "shade_items")
+HOST_QUERIES = ("item_ranges", "setup_triangles", "stats", "sync")      # what the first two generators draw from
+QUERIES = HOST_QUERIES + ("query_host", "boxes_host", "bounds")
+WRITERS = ("geom", "draw", "lines", "wireframe", "resolve", "shade", "count", "set_cull", "set_uniforms", "set_texture", "shade_items",
+           "query", "boxes")
 COMMANDS_X = COMMANDS + ("shade_items",)       # the extended generator's
+COMMANDS_Q = COMMANDS_X + ("query_item", "query_triangle")   # the query generator's
 XSEEDS = range(100, 112)                       # the extended seeds: tests/test_gpu_frame_model.py runs them on partitioned contexts
+QSEEDS = range(200, 216)                       # the query seeds: run on single contexts with both list sizes AND on partitioned ones
 
 UP, FOVY, ZN, ZF = (0.0, 1.0, 0.0), scenes.demo_camera(W, H)[3], 0.1, 100.0
 CAMERAS = [((0.0, 1.0, 3.0), (0.0, 0.0, 0.0)), ((0.9, 0.6, 2.6), (0.0, 0.05, 0.0))]
@@ -160,11 +183,27 @@ def _rung2():
     return t
 
 
+def _cover():
+    """the occluder of the query sequences: two large triangles in the plane z = 1 between both cameras and the origin, over
+    the left half of the view and a little more -- under the identity the boxes of the small meshes behind it are hidden, those
+    beside it are kept.  It is clipped into a dozen setup triangles and is no rung."""
+    x0, x1, y0, y1, z = -1.1, 0.3, -0.8, 1.0, 1.0
+    c = [(x0, y0), (x1, y0), (x1, y1), (x0, y1)]
+    t = np.zeros((2, 3, 8), F)
+    for k, corners in enumerate(((0, 1, 2), (0, 2, 3))):
+        for j, i in enumerate(corners):
+            t[k, j, :3] = (c[i][0], c[i][1], z)
+            t[k, j, 3:5] = ((c[i][0] - x0) / (x1 - x0), (c[i][1] - y0) / (y1 - y0))
+            t[k, j, 5:8] = (0.0, 0.0, 1.0)
+    return t
+
+
 _GRID = S.patch_grid(8, 8)                     # the indexed mesh: 81 vertices under 128 triangles
 MESHES = {
     "p40": S.patch(40), "p100": S.patch(100), "p257": S.patch(257), "spiky": D.spiky(30),
     "torus": scenes.torus(10, 6, R=0.3, r=0.12), "grid": np.ascontiguousarray(_GRID[0][_GRID[1].astype(np.int64)]),
     "empty": np.zeros((0, 3, 8), F), "r1": _big(128, 101), "r2": _rung2(),
+    "cover": _cover(),                         # (the query sequences alone draw it)
 }
 INDEXED = {"grid": _GRID}
 RUNGS = {1: "r1", 2: "r2"}
@@ -233,6 +272,7 @@ class _Memo(dict):
 
 
 _RASTER, _SHADE, _PAINT = _Memo(400), _Memo(400), _Memo(200)
+_QUERY, _BOXES = _Memo(400), _Memo(2000)
 
 
 def _digest(*parts):
@@ -333,7 +373,8 @@ class Model:
         self.tris_in = self.draws = self.emitted = 0
         self.last = None
         self.bufs = new_buffers()
-        self.prov = {}                         # count buffer -> what the latest frr_visible_pixels into it was
+        self.prov = {}                         # count buffer -> what the latest count, query or box query into it was
+        self.box_log = []                      # this frame's box queries into buffers: what a rank's own answer is computed from
         self.wrote = {}                        # varyings buffer -> the entries this frame's resolves wrote (bool[ENTRIES])
         self.buf_win = {}                      # varyings buffer -> the (x1, rows) of the windows its resolves ran in, ever
         self.fan_cap, self.bin_cap = TINY["fan_capacity"], TINY["bin_capacity"]
@@ -352,6 +393,7 @@ class Model:
         ctypes.memmove(ctypes.byref(m.frame.counters), ctypes.byref(self.frame.counters), ctypes.sizeof(self.frame.counters))
         m.bufs = {k: v.copy() for k, v in self.bufs.items()}
         m.prov = dict(self.prov)
+        m.box_log = list(self.box_log)
         m.wrote = {k: v.copy() for k, v in self.wrote.items()}
         m.buf_win = {k: set(v) for k, v in self.buf_win.items()}
         return m
@@ -389,6 +431,7 @@ class Model:
         self.tris_in = self.draws = self.emitted = 0
         self.crossed = self.crossed_fan = False
         self.wrote = {}
+        self.box_log = []
         if self.last is not None:
             self.last = self._copy_pass(self.last)
             self.last.cleared = True
@@ -422,6 +465,7 @@ class Model:
         p = _Pass()
         # (a list without items names no vertex shader: its K is 0, and any pixel shader goes with nothing)
         p.items, p.vs, p.K, p.kind, p.cam, p.light = items, vs, _vs_k(vs) if items else 0, s["kind"], self.cam, self.light
+        p.kept, p.cull = kept, self.cull        # (which items the predicate kept; the cull mode of the geometry call)
         p.keep, p.per_item, setups, fans = [], [], [], []
         for i, (mesh, mi) in enumerate(items):
             setup, counts = _item_geometry(self.o, mesh, mi, self.cam, self.light, vs, self.W, self.H)
@@ -626,7 +670,96 @@ class Model:
             out = VIS.want_counts(self.frame.tri_id, (x0, x1), (y0, y1), units=n, entries=e)
         self.changed = (buf[:e] != out).any()
         buf[:e] = out
-        self.prov[s["buf"]] = dict(frame=self.fno, unit=s["unit"], n=n, entries=e, items=p.items, kind=p.kind)
+        self.prov[s["buf"]] = dict(frame=self.fno, unit=s["unit"], n=n, entries=e, items=p.items, kind=p.kind, source="count", vs=p.vs)
+
+    # -- occlusion queries (include/frr.h, "occlusion queries") --
+    def _query_counts(self, p):
+        """per setup triangle of pass p the entries rasterization(t) ALONE changes on a copy of the frame's depth as it is now
+        (query_reference.counts_c); where the pass is no rung the same on the NumPy oracle, asserted equal"""
+        assert (self.W, self.H) == (QR.W, QR.H), "query_reference is written for the 128 x 96 frame"
+        depth = np.array(self.frame.depth, F)
+        key = _digest(b"query", depth, p.setup, self.window)
+        if key not in _QUERY:
+            per_tri = QR.counts_c(self.o, depth, p.setup, self.window)
+            if not any(mesh in RUNGS.values() for mesh, _ in p.items):
+                np.testing.assert_array_equal(QR.counts_np(depth, p.setup, self.window), per_tri, err_msg="the NumPy oracle's query counts differ from the C oracle's")
+            _QUERY.put(key, per_tri)
+        return _QUERY[key]
+
+    def _query_answer(self, s):
+        """(out uint32 [entries], n, the pass) of frr_query_pixels at this place.  The units, n and the every-entry-is-written
+        rule are frr_visible_pixels': after a clear since the pass the per-item answer is zeros (the per-triangle one the model
+        leaves undefined, as it leaves that count); a dropped item and a culled input have no setup triangle and count 0"""
+        e = int(s["entries"])
+        if not 0 < e <= COUNT_CAP:
+            raise Undefined("out_entries")
+        if self.last is None:
+            raise Undefined("before any geometry pass")
+        p = self._latest(cleared_ok=s["unit"] == "item")
+        out = np.zeros(e, np.uint32)
+        if s["unit"] == "item":
+            n = len(p.items)
+            vals = np.zeros(n, np.uint32) if p.cleared else QR.per_item_sums(self._query_counts(p), p.per_item)
+        else:
+            n = p.base + p.emit
+            vals = np.concatenate([np.zeros(p.base, np.uint32), self._query_counts(p)])
+        out[:min(n, e)] = vals[:min(n, e)]
+        return out, n, p
+
+    def _query(self, s):
+        buf = self.bufs[s["buf"]]
+        out, n, p = self._query_answer(s)
+        e = out.size
+        # (the query bins like frr_raster of the same pass: in front of the raster of a bin rung it is the command that overflows)
+        if not p.cleared:
+            self.crossed |= p.fan_rung or p.bin_rung
+        self.changed = bool((buf[:e] != out).any())
+        buf[:e] = out
+        self.prov[s["buf"]] = dict(frame=self.fno, unit=s["unit"], n=n, entries=e, items=p.items, kind=p.kind, source="query", vs=p.vs)
+
+    def _query_host(self, s):
+        return dict(out=self._query_answer(s)[0])
+
+    # -- box queries (include/frr.h, "box queries") --
+    def _bounds_of(self, items):
+        per = [BX.bounds_of(MESHES[mesh]) for mesh, _ in items]      # (the expanded `grid`: the corners its triangles name)
+        lo_hi = np.stack([b for b, _ in per]).astype(F) if per else np.zeros((0, 6), F)
+        return lo_hi, np.array([f for _, f in per], np.uint32)
+
+    def _box_args(self, s):
+        """what frr_query_boxes of the step's list reads at this place: the matrices under the uniforms of the moment, the
+        bounds table, the viewport, the frame's window and the depth as it is now (a pending clear is settled: the model's
+        clear is never pending)"""
+        if s["vs"] not in VS_PS:
+            raise Undefined("a list whose vertex shader has no object space")
+        e = int(s["entries"])
+        if not 0 < e <= COUNT_CAP:
+            raise Undefined("out_entries")
+        items = [tuple(i) for i in s["items"]]
+        kw, _ = self._uniforms()
+        proj, view = (np.asarray(kw[k], F).reshape(16) for k in ("proj", "view"))
+        lo_hi, flags = self._bounds_of(items)
+        return dict(mvps=BX.mvps_of(proj, view, MODELS[[mi for _, mi in items]].reshape(-1, 16)), lo_hi=lo_hi, flags=flags, size=(self.W, self.H),
+                    window=self.window, depth=np.array(self.frame.depth, F), entries=e)
+
+    def _boxes(self, s):
+        buf, args = self.bufs[s["buf"]], self._box_args(s)
+        out, srl = box_answer(args)
+        e = out.size
+        self.changed = bool((buf[:e] != out).any())
+        buf[:e] = out
+        items = [tuple(i) for i in s["items"]]
+        self.box_log = self.box_log + [dict(buf=s["buf"], args=args, out=out, srl=srl)]
+        self.prov[s["buf"]] = dict(frame=self.fno, unit="item", n=len(items), entries=e, items=items, kind="list", source="boxes", vs=s["vs"])
+
+    def _boxes_host(self, s):
+        args = self._box_args(s)
+        out, srl = box_answer(args)
+        return dict(out=out, args=args, srl=srl)
+
+    def _bounds(self, s):
+        lo_hi, flags = self._bounds_of([tuple(i) for i in s["items"]])
+        return dict(lo_hi=lo_hi, flags=flags)
 
     def _item_ranges(self, s):
         p = self._latest()
@@ -655,8 +788,25 @@ class Model:
         """what a frame end is compared with"""
         f = self.frame
         return dict(color=f.color.copy(), depth=f.depth.copy(), tri_id=f.tri_id.copy(), stats=self.stats(),
-                    bufs={k: v.copy() for k, v in self.bufs.items()}, crossed=self.crossed, crossed_fan=self.crossed_fan,
+                    bufs={k: v.copy() for k, v in self.bufs.items()}, crossed=self.crossed, crossed_fan=self.crossed_fan, boxes=list(self.box_log),
                     wrote={k: v.copy() for k, v in self.wrote.items()})
+
+
+def box_answer(args, row_owned=None):
+    """(out, status_rect_level) of a box query whose inputs Model._box_args recorded -- with row_owned (bool per window-local
+    tile row) the answer of the rank of a partition that owns those rows"""
+    key = _digest(b"boxes", args["mvps"], args["lo_hi"], args["flags"], (args["size"], args["window"], args["entries"]), args["depth"],
+                  None if row_owned is None else np.asarray(row_owned, bool))
+    if key not in _BOXES:
+        _BOXES.put(key, BX.query(args["mvps"], args["lo_hi"], args["flags"], args["size"], args["window"], args["depth"], row_owned=row_owned,
+                                 entries=args["entries"]))
+    return _BOXES[key]
+
+
+def rank_tile_rows(window, rank, world, blocked):
+    """bool per window-local tile row: the rows rank `rank` owns in the window (what a draw, a count and a query go by)"""
+    from f_renderer_amd.multigpu import tile_row_owner
+    return np.asarray(tile_row_owner((window[3] - window[2] + 31) // 32, world, blocked)) == rank
 
 
 def run_frames(model, frames, skip=None):
@@ -737,7 +887,7 @@ def same_outputs(a, b):
     for (na, xa), (nb, xb) in zip(a["answers"], b["answers"]):
         if na != nb or (xa is None) != (xb is None):
             return False
-        if isinstance(xa, dict) and any(np.asarray(xa[k]).tobytes() != np.asarray(xb[k]).tobytes() for k in xa):
+        if isinstance(xa, dict) and any(np.asarray(xa[k]).tobytes() != np.asarray(xb[k]).tobytes() for k in xa if not isinstance(xa[k], dict)):
             return False
     return True
 
@@ -792,9 +942,14 @@ class _Gen:
     place is drawn again, a step that writes is kept only if it changes a target or a buffer (or is a no-op on purpose, while
     the seed's share of those allows one more), a state setter only in front of a command that comes out differently under it."""
 
-    def __init__(self, oracle, seed, extended=False):
+    def __init__(self, oracle, seed, extended=False, queries=False):
+        extended = extended or queries
         self.o, self.seed, self.rng, self.m = oracle, seed, np.random.RandomState(seed), Model(oracle, partitioned=extended)
         self.ext = extended                    # shade_items, second rasters and abandoned passes; legal on a partitioned context
+        self.q = queries                       # ... and occlusion queries, box queries, their host forms and the passes they decide
+        self.commands = COMMANDS_Q if queries else COMMANDS_X if extended else COMMANDS
+        self.box_lists = []                    # (vs, items) of the lists a box query has been asked of
+        self.list_cam = {}                     # (vs, items) -> the camera of the list's last use (a pass over it or a box query)
         self.last_resolve = None               # the varyings buffer the latest resolve wrote into
         self.frames, self.steps, self.reserve = [], None, 0
         self.noops = self.total = 0
@@ -833,7 +988,7 @@ class _Gen:
             trial.apply(s)
         except (Undefined, RuntimeError):
             return False
-        if s["op"] in ("lines", "wireframe", "resolve", "shade", "shade_items", "count", "draw", "raster") and not trial.changed:
+        if s["op"] in ("lines", "wireframe", "resolve", "shade", "shade_items", "count", "draw", "raster", "query", "boxes") and not trial.changed:
             if not force and not (noop_ok and self.noop_allowed()):
                 return False
             (self.geom_step if s["op"] == "raster" else s)["noop"] = True
@@ -841,6 +996,8 @@ class _Gen:
         self.m = trial
         self.steps.append(s)
         self.total += 1
+        if self.q and s["op"] in ("geom", "draw", "boxes", "boxes_host") and (s["op"] in ("boxes", "boxes_host") or s["kind"] in ("list", "list_if")):
+            self.list_cam[s["vs"], tuple(tuple(i) for i in s["items"])] = trial.cam
         if s["op"] == "geom":
             self.geom_step = s
             if self.ext:                       # (an abandoned pass meets no raster that would record them)
@@ -882,7 +1039,8 @@ class _Gen:
             if self.ext and rng.rand() < 0.5:  # (every kind of pass in front of a shade_items in several seeds)
                 kind = ("list", "instanced", "plain")[(self.seed + self.m.fno + len(self.steps)) % 3]
             fed = [(b, pr) for b, pr in sorted(m.prov.items()) if pr["unit"] == "item" and pr["frame"] >= m.fno - 1 and pr["kind"] in ("list", "list_if")
-                   and pr["entries"] >= pr["n"] >= 3 and all(mesh not in RUNGS.values() for mesh, _ in pr["items"])]
+                   and pr["entries"] >= pr["n"] >= 3 and all(mesh not in RUNGS.values() for mesh, _ in pr["items"])
+                   and (self.q or pr["source"] == "count")]
             if fed and rng.rand() < 0.4:
                 kind = "list_if"               # the counts of an earlier pass are there to be fed back
             if kind == "plain":
@@ -900,6 +1058,10 @@ class _Gen:
                     b, pr = fed[int(rng.randint(len(fed)))]
                     items = list(pr["items"])
                     s.update(keep=b, keep_entries=pr["entries"], min=int(self.pick(MIN_VALUES)), fed=True)
+                    if self.q:
+                        s["source"] = pr["source"]
+                        if pr["source"] == "boxes":      # the list that was queried; on a partition only `min 1` reads the ranks' sum as one answer
+                            s.update(vs=pr["vs"], min=1)
                 else:
                     n = int(rng.randint(3, 8)) if rng.rand() < 0.93 else 0
                     ms = [int(x) for x in rng.choice(list(M_GRID) + list(M_CLIPPED), n, replace=False)]
@@ -942,6 +1104,8 @@ class _Gen:
             ps = self.pick(("PHONG", "BLINN")) if p.K == 8 and rng.rand() < 0.6 else self.pick(K_PS[p.K])
             return dict(op="shade_items", ps=ps, buf=buf, table=self.pick(sorted(MATERIALS)))
         unit = kind.split("_")[1]
+        if kind.startswith("query") and (m.last is None or (m.part and m.last.filtered)):
+            return None
         if unit == "item":
             if m.last is None:
                 return None
@@ -951,7 +1115,7 @@ class _Gen:
                 return None
             n = p.base + p.emit
         e = n + int(self.pick((0, -1, 3)))
-        return dict(op="count", unit=unit, buf=f"{pool}.c{int(rng.randint(3))}", entries=e) if e > 0 else None
+        return dict(op=kind.split("_")[0], unit=unit, buf=f"{pool}.c{int(rng.randint(3))}", entries=e) if e > 0 else None
 
     def place(self, kind, inside):
         """one command of the kind; a shade half the time behind a state setter it comes out differently under"""
@@ -967,7 +1131,7 @@ class _Gen:
     def kind_of_command(self):
         """shades and resolves come up more often where they can do something"""
         p = self.m.last
-        commands = COMMANDS_X if self.ext else COMMANDS
+        commands = self.commands
         w = {k: 1.0 for k in commands}
         w["shade"] = 2.5 if self.resolved else 0.0
         w["resolve"] = 2.0 if p is not None and p.rastered and not p.cleared else 0.5
@@ -976,7 +1140,7 @@ class _Gen:
         return self.pick(commands, p=ws / ws.sum())
 
     def add_command(self, c):
-        ok = bool(c) and self.add(c, noop_ok=c["op"] in ("resolve", "count") or (c["op"] == "shade" and c["ids"][1] == 0) or
+        ok = bool(c) and self.add(c, noop_ok=c["op"] in ("resolve", "count", "query") or (c["op"] == "shade" and c["ids"][1] == 0) or
                                   (c["op"] == "shade_items" and not self.m.last.rastered))
         if ok and c["op"] == "resolve" and not c.get("noop"):
             self.last_resolve = c["buf"]
@@ -1025,7 +1189,7 @@ class _Gen:
                     break
                 r = rng.rand()
                 if r < 0.15:
-                    n += self.add(dict(op=self.pick(QUERIES)))
+                    n += self.add(self.host_query())
                 else:
                     n += self.place(kinds.pop(), True)
             added = self.add(dict(op="raster", ps=ps), force=True)
@@ -1065,16 +1229,22 @@ class _Gen:
             abandon = rng.rand() < (1.0 if rung == 1 and self.seed % 4 == 1 else 0.12)
             pair = not abandon and self.room() >= 4 and rng.rand() < 0.5
             want = int(rng.randint(1, 3)) if rung else int(rng.randint(0, 2))
-            kinds = [str(k) for k in rng.permutation(COMMANDS_X)]
+            kinds = [str(k) for k in rng.permutation(self.commands)]
             if rng.rand() < (0.35 if self.seed % 2 else 0.0):     # (the seeds that run with the tiny lists)
                 kinds.remove("shade_items")
                 kinds.append("shade_items")
+            if self.q and (rng.rand() < 0.6 or (rung and self.seed % 2)):
+                # a query is the first command tried inside the pass: in front of a rung's raster it is what overflows the lists
+                first = "query_item" if rng.rand() < 0.6 else "query_triangle"
+                kinds.remove(first)
+                kinds.append(first)
+                want = max(want, 1)
             n = 0
             for _ in range(12):
                 if n >= want or self.room() <= (3 if pair else 2) or not kinds:
                     break
                 if rng.rand() < 0.15:
-                    n += self.add(dict(op=self.pick(QUERIES)))
+                    n += self.add(self.host_query())
                 else:
                     n += self.place(kinds.pop(), True)
             if abandon:
@@ -1096,11 +1266,118 @@ class _Gen:
     def items_behind(self):
         """behind a pass: a resolve of it, and one shade of all its items under a table"""
         p = self.m.last
-        if p.rastered and not (self.m.part and p.filtered) and p.K and p.emit and self.room() >= 2 and self.rng.rand() < 0.95 and \
+        if p.rastered and not (self.m.part and p.filtered) and p.K and p.emit and self.room() >= 2 and self.rng.rand() < (0.4 if self.q else 0.95) and \
                 not any(mesh in RUNGS.values() for mesh, _ in p.items):
             self.add_command(self.command("resolve", False))
             if self.last_resolve and buffer_k(self.last_resolve) == p.K:
                 self.place("shade_items", False)
+
+    # -- the query generator's own patterns --
+    def host_query(self):
+        """a host query at this place; the query generator draws the host forms of the two queries and frr_drawlist_bounds too"""
+        if not self.q:
+            return dict(op=self.pick(HOST_QUERIES))
+        op = self.pick(QUERIES, p=(0.1, 0.1, 0.15, 0.1, 0.25, 0.2, 0.1))
+        if op == "query_host":
+            c = self.command(self.pick(("query_item", "query_triangle")), False)
+            return dict(op="query_host", unit=c["unit"], entries=c["entries"]) if c else dict(op="stats")
+        if op in ("boxes_host", "bounds"):
+            vs, items = self.a_list()
+            s = dict(op=op, vs=vs, items=list(items))
+            if op == "boxes_host":
+                s["entries"] = len(items) + int(self.pick((0, -1, 3)))
+                self.note_list(vs, items)
+            return s
+        return dict(op=op)
+
+    def note_list(self, vs, items):
+        if (vs, items) not in self.box_lists:
+            self.box_lists.append((vs, items))
+
+    def a_list(self, known=0.4):
+        """(vs, items) of a list for a box query: one that was asked before, or 4 to 7 small meshes, the empty one among them,
+        under any of the matrices -- behind the cover, beside it, through the near plane, off the screen"""
+        rng = self.rng
+        if self.box_lists and rng.rand() < known:
+            return self.box_lists[int(rng.randint(len(self.box_lists)))]
+        n = int(rng.randint(4, 8))
+        ms = [int(x) for x in rng.choice(len(MODELS), n, replace=False)]
+        items = tuple((self.pick(("p40", "p40", "torus", "grid", "p100", "spiky", "empty")), mi) for mi in ms)
+        return self.pick(("PHONG", "GOURAUD")), items
+
+    def cover_draw(self):
+        vs = self.pick(("PHONG", "GOURAUD"))
+        return dict(op="draw", kind="plain", vs=vs, items=[("cover", M_IDENT)], ps="DEPTH" if self.rng.rand() < 0.5 else self.pick(VS_PS[vs]), rung=0, fused=True)
+
+    def fed_draw(self, vs, items, buf, entries, source):
+        """frr_draw_list_if of the list under the keep buffer a query or a box query wrote (min_value 1)"""
+        return dict(op="draw", kind="list_if", vs=vs, items=[tuple(i) for i in items], keep=buf, keep_entries=entries, min=1, fed=True, source=source,
+                    ps=self.pick(VS_PS[vs]), rung=0, fused=True)
+
+    def fits(self, vs, items):
+        """the list as a pass is no rung by accident"""
+        digest, _ = self.probe([dict(op="geom", kind="list", vs=vs, items=list(items), rung=0, fused=False)])
+        return digest is not None and self.probed.last.fan_need <= ORDINARY_FAN_NEED
+
+    def start_q(self, fno):
+        """behind the clear: a pass decided by what the previous frame's query or box query left in its buffer; a box query as the
+        first command behind the clear; a per-item query of the previous frame's pass (zeros)"""
+        rng, m, pool = self.rng, self.m, "AB"[fno % 2]
+        self.reserve = 4
+        prev = [(b, pr) for b, pr in sorted(m.prov.items()) if pr["source"] in ("query", "boxes") and pr["frame"] == m.fno - 1 and pr["unit"] == "item"
+                and pr["kind"] in ("list", "list_if") and pr["entries"] >= pr["n"] >= 3 and all(mesh not in RUNGS.values() for mesh, _ in pr["items"])]
+        h = (self.seed + fno) % 4
+        if h in (0, 2):
+            vs, items = self.a_list()
+            if self.add(dict(op="boxes", vs=vs, items=list(items), buf=f"{pool}.c{int(rng.randint(3))}", entries=len(items) + int(self.pick((0, 3)))),
+                        noop_ok=True):
+                self.note_list(vs, items)
+        elif h == 1 and fno > 0:
+            self.add_command(self.command("query_item", False))
+        if prev and rng.rand() < 0.8:
+            b, pr = prev[int(rng.randint(len(prev)))]
+            vs = pr["vs"] if pr["source"] == "boxes" else self.pick(("PHONG", "GOURAUD"))
+            if self.fits(vs, pr["items"]):
+                self.add(self.fed_draw(vs, pr["items"], b, pr["entries"], pr["source"]), noop_ok=True)
+        self.reserve = 0
+
+    def loop(self, fno):
+        """the loop the two queries are there for, all on one stream: occluders, the query, the pass it decides.
+        boxes:      draw cover; [set_uniforms: the other camera]; boxes(list) -> buf; draw list_if(list, keep = buf)
+        two boxes:  boxes(list) -> buf'; draw cover; boxes(list) -> buf; draw list_if(list, keep = buf)
+        query:      draw cover; geom list; query item -> buf; [raster]; draw list_if(list, keep = buf): the list's own geometry is
+                    the proxy, and the pass that asked is abandoned or rastered depth-only"""
+        rng, m, pool = self.rng, self.m, "AB"[fno % 2]
+        kind = ("boxes", "query", "two_boxes")[(self.seed + fno) % 3]
+        if self.room() < 4:
+            return
+        for _ in range(6):
+            vs, items = self.a_list(0.6 if kind == "boxes" and self.seed % 2 else 0.3)
+            if self.fits(vs, items):
+                break
+        else:
+            return
+        n, bufs = len(items), [f"{pool}.c{int(k)}" for k in rng.permutation(3)]
+        e = n + int(self.pick((0, 3)))
+        if kind == "two_boxes" and self.room() >= 5:
+            if self.add(dict(op="boxes", vs=vs, items=list(items), buf=bufs[1], entries=n), noop_ok=True):
+                self.note_list(vs, items)
+        self.add(self.cover_draw(), noop_ok=True)
+        if kind == "query":
+            if not self.add(dict(op="geom", kind="list", vs=vs, items=list(items), rung=0, fused=False)):
+                return
+            g = self.geom_step
+            self.add(dict(op="query", unit="item", buf=bufs[0], entries=e), noop_ok=True)
+            if not (self.room() >= 3 and rng.rand() < 0.5 and self.add(dict(op="raster", ps="DEPTH"), force=True)):
+                g["abandoned"] = True
+            self.add(self.fed_draw(vs, items, bufs[0], e, "query"), noop_ok=True)
+            return
+        cam = self.list_cam.get((vs, items))
+        if kind == "boxes" and cam is not None and cam == m.cam and self.room() >= 3:
+            self.add(dict(op="set_uniforms", cam=1 - m.cam, light=m.light, flat=m.flat, slot=m.slot))
+        if self.add(dict(op="boxes", vs=vs, items=list(items), buf=bufs[0], entries=e), noop_ok=True):
+            self.note_list(vs, items)
+            self.add(self.fed_draw(vs, items, bufs[0], e, "boxes"), noop_ok=True)
 
     # -- one frame --
     def frame(self, fno, window, rung, end):
@@ -1109,11 +1386,16 @@ class _Gen:
         self.m.apply(self.steps[0])
         npass = int(rng.randint(2, 5))
         at = int(rng.randint(npass)) if rung else -1
+        if self.q:
+            self.start_q(fno)
         if fno > 0 and rng.rand() < 0.3:       # a per-item count of the previous frame's pass right after the clear: zeros
             self.reserve = 3
             self.add_command(self.command("count_item", False))
         for k in range(npass):
             r = rung if k == at else 0
+            self.reserve = 3 if rung and k <= at else 0
+            if self.q and k == (self.seed + fno) % npass:
+                self.loop(fno)
             self.reserve = 3 if rung and k < at else 0        # (room for the rung's pass behind this one)
             if not r and self.room() < 2:
                 continue
@@ -1133,7 +1415,7 @@ class _Gen:
                 if self.room() < 1:
                     break
                 if rng.rand() < 0.2:
-                    self.add(dict(op=self.pick(QUERIES)))
+                    self.add(self.host_query())
                 else:
                     self.place(self.kind_of_command(), False)
         self.reserve = 0
@@ -1150,19 +1432,19 @@ def steps_of(frames):
     return [s for steps in frames for s in steps if s["op"] != "clear"]
 
 
-def generate(seed, oracle=None, extended=False):
+def generate(seed, oracle=None, extended=False, queries=False):
     """The frames of a seed: a list of FRAMES lists of steps (dicts: "op" and its arguments; "noop" on a step that writes
     nothing on purpose; "rung" on a pass over a rung mesh; "fan_rung", "bin_rung", "fan_need", "bin_need" on every pass, from
     the model).  Every frame starts with its "clear" and ends with "readback" or "fenced"; the steps after the clear are at most
     MAX_STEPS.  A pure function of the seed: np.random.RandomState(seed) is the only source of randomness, and the model the
     generator consults is deterministic."""
-    key = (seed, "extended") if extended else seed
+    key = (seed, "queries") if queries else (seed, "extended") if extended else seed
     if key in _GENERATED:
         return _GENERATED[key]
     if oracle is None:
         from oracle import cref as oracle
-    model_kw = dict(partitioned=True) if extended else {}
-    g = _Gen(oracle, seed, extended)
+    model_kw = dict(partitioned=True) if extended or queries else {}
+    g = _Gen(oracle, seed, extended, queries)
     rng = g.rng
     f1 = int(rng.randint(0, 2))
     f2 = int(rng.randint(f1 + 1, FRAMES))
@@ -1196,8 +1478,34 @@ def generate(seed, oracle=None, extended=False):
             break
         else:
             raise AssertionError("the share of no-ops cannot be met")
+    if queries:
+        _settle_feeds(oracle, frames)
     _GENERATED[key] = frames
     return frames
+
+
+def fed_by(oracle, frames):
+    """{id(step): the model's provenance of the keep buffer at that step} for every predicated pass of `frames` that names a
+    caller buffer"""
+    m, out = Model(oracle, partitioned=True), {}
+    for steps in frames:
+        for s in steps:
+            if s["op"] in ("geom", "draw") and s["kind"] == "list_if" and s["keep"] in m.bufs:
+                out[id(s)] = m.prov.get(s["keep"])
+            m.apply(s)
+    return out
+
+
+def _settle_feeds(oracle, frames):
+    """after the pruning: a predicated pass whose feeding command left the sequence reads whatever the buffer holds -- it is
+    marked as not fed -- and every pass that is fed says by what"""
+    prov = fed_by(oracle, frames)
+    for s in steps_of(frames):
+        if id(s) in prov:
+            pr = prov[id(s)]
+            ok = pr is not None and pr["unit"] == "item" and [tuple(i) for i in pr["items"]] == [tuple(i) for i in s["items"]] and \
+                pr["entries"] == s["keep_entries"] and (pr["source"] != "boxes" or pr["vs"] == s["vs"])
+            s["fed"], s["source"] = bool(ok), pr["source"] if ok else None
 
 
 def cull_inside_split():
@@ -1239,6 +1547,8 @@ def refused_behind_fused():
              dict(no, op="resolve", buf="A.v8b"),
              dict(no, op="count", unit="item", buf="A.c0", entries=4),
              dict(no, op="count", unit="triangle", buf="A.c1", entries=64),
+             dict(no, op="query", unit="item", buf="A.c0", entries=4),
+             dict(no, op="query_host", unit="triangle", entries=64),
              dict(no, op="shade_items", ps="PHONG", buf="A.v8a", table="mat0"),
              dict(op="lines", list=0),
              dict(op="shade", buf="A.v8a", ps="BLINN", ids=(0, NONE)),
@@ -1265,6 +1575,60 @@ def abandoned_then_larger():
              dict(op="raster", ps="PHONG"),
              dict(op="item_ranges"),
              dict(op="stats"),
+             dict(op="readback")]]
+
+
+LOOP_LIST = [("p40", 0), ("torus", 6), ("spiky", 2), ("empty", 4), ("p40", 12), ("grid", 10), ("p100", 3)]
+
+
+def query_overflows_a_rung():
+    """A fixed frame: the loop of an occlusion query with the query as the command that meets the tiny lists.  The cover, the
+    geometry of a list over r1 (a rung of the fan slots and of the bin records), a per-item query of it between a line list and
+    a count -- the first command that bins the pass, verified inside the call --, its depth-only raster, then the geometry of
+    the small list, its query, and the pass the query decides while the small list's own pass stays abandoned."""
+    big = [("r1", M_IDENT), ("p40", int(M_GRID[0])), ("torus", int(M_GRID[1]))]
+    return [[dict(op="clear", window=FULL),
+             dict(op="draw", kind="plain", vs="PHONG", items=[("cover", M_IDENT)], ps="FLAT", rung=0, fused=True),
+             dict(op="geom", kind="list", vs="PHONG", items=big, rung=1, fused=False),
+             dict(op="lines", list=0),
+             dict(op="query", unit="item", buf="A.c0", entries=3),
+             dict(op="count", unit="item", buf="A.c1", entries=3),
+             dict(op="raster", ps="DEPTH"),
+             dict(op="geom", kind="list", vs="GOURAUD", items=LOOP_LIST, rung=0, fused=False, abandoned=True),
+             dict(op="query", unit="item", buf="A.c2", entries=len(LOOP_LIST) + 3),
+             dict(op="query_host", unit="triangle", entries=40),
+             dict(op="draw", kind="list_if", vs="GOURAUD", items=LOOP_LIST, keep="A.c2", keep_entries=len(LOOP_LIST) + 3, min=1, fed=True, source="query",
+                  ps="COLOR", rung=0, fused=True),
+             dict(op="stats"),
+             dict(op="fenced")]]
+
+
+def boxes_around_a_draw():
+    """Two fixed frames in the two windows: a box query as the first command behind the clear (it settles the clear, eager or
+    not), the cover, the same query under the other camera, again under the first one -- the answers differ around the draw
+    and around the camera --, the pass the last one decides; in the next frame, in the sub-window, the buffer decides a pass
+    again before a box query of this frame replaces it, inside a split pass."""
+    n = len(LOOP_LIST)
+    boxes = dict(op="boxes", vs="PHONG", items=LOOP_LIST, entries=n)
+    fed = dict(op="draw", kind="list_if", vs="PHONG", items=LOOP_LIST, keep_entries=n, min=1, fed=True, source="boxes", rung=0, fused=True)
+    return [[dict(op="clear", window=FULL),
+             dict(boxes, buf="A.c0"),
+             dict(op="bounds", vs="PHONG", items=LOOP_LIST),
+             dict(op="draw", kind="plain", vs="GOURAUD", items=[("cover", M_IDENT)], ps="DEPTH", rung=0, fused=True),
+             dict(op="set_uniforms", cam=1, light=0, flat=0, slot=0),
+             dict(boxes, buf="A.c1"),
+             dict(op="set_uniforms", cam=0, light=0, flat=1, slot=0),
+             dict(boxes, buf="A.c2", entries=n + 2),
+             dict(op="boxes_host", vs="PHONG", items=LOOP_LIST, entries=n - 2),
+             dict(fed, keep="A.c2", keep_entries=n + 2, ps="BLINN"),
+             dict(op="fenced")],
+            [dict(op="clear", window=SUB),
+             dict(fed, keep="A.c2", keep_entries=n + 2, ps="FLAT"),
+             dict(op="geom", kind="plain", vs="PHONG", items=[("cover", M_IDENT)], rung=0, fused=False),
+             dict(boxes, buf="B.c0"),
+             dict(op="raster", ps="PHONG"),
+             dict(boxes, buf="B.c1"),
+             dict(fed, keep="B.c1", ps="PHONG"),
              dict(op="readback")]]
 
 

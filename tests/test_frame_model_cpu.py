@@ -541,7 +541,7 @@ def test_the_fixed_sequences_of_the_partitioned_runs(oracle):
     frames = M.refused_behind_fused()
     want, = M.run_model(oracle, frames, partitioned=True)
     refused = [s for s in frames[0] if s.get("refused")]
-    assert {s["op"] for s in refused} == {"wireframe", "setup_triangles", "item_ranges", "resolve", "count", "shade_items"}
+    assert {s["op"] for s in refused} == {"wireframe", "setup_triangles", "item_ranges", "resolve", "count", "shade_items", "query", "query_host"}
     assert {s["unit"] for s in refused if s["op"] == "count"} == {"item", "triangle"}
     with pytest.raises(AssertionError, match="marked as refused"):
         M.run_model(oracle, frames)            # (without a partition nothing filters the setup list: every one is taken)
@@ -591,3 +591,368 @@ def test_lines_and_draws_own_different_rows_in_a_short_window_of_the_blocked_lay
                         stitched[rule[rank]] = ranks[rank][rule[rank]]
                     assert (stitched[32:40] != want["color"][32:40]).any(), "rows 32 .. 39 are complete on no rank"
                     assert (stitched[:32] == want["color"][:32]).all()
+
+
+# ---- the query sequences: occlusion queries, box queries, their host forms, and the passes they decide ------------------------
+
+# sha256 over repr(frame_model.steps_of(frame_model.generate(seed, extended=True))) of the seeds 100 .. 111 in order, computed
+# at the commit before the generator learnt the query steps
+DIGEST_OF_XSEEDS = "41783c2fe72959ea4139486565e198a2b2acb51e18ad56376e6602d18f6aa8f2"
+
+
+def test_the_sequences_of_the_extended_seed_set_are_unchanged(extended):
+    import hashlib
+    h = hashlib.sha256()
+    for seed in M.XSEEDS:
+        h.update(repr(M.steps_of(extended[seed])).encode())
+    assert h.hexdigest() == DIGEST_OF_XSEEDS
+    assert not any(s["op"] in ("query", "boxes", "query_host", "boxes_host", "bounds") or "cover" in repr(s.get("items")) for f in extended.values()
+                   for s in M.steps_of(f))
+
+
+@pytest.fixture(scope="module")
+def queried(oracle):
+    return {seed: M.generate(seed, oracle, queries=True) for seed in M.QSEEDS}
+
+
+def _key(s):
+    return s["vs"], tuple(tuple(i) for i in s["items"])
+
+
+def _walk(oracle, frames):
+    """the model over a sequence, step by step: yields (frame number, index in the frame, step, the model BEFORE the step, the
+    step's answer), applying the step when the consumer comes back"""
+    m = M.Model(oracle, partitioned=True)
+    for fi, steps in enumerate(frames):
+        for k, s in enumerate(steps):
+            before = m.copy()
+            a = m.apply(s)
+            yield fi, k, s, before, m, a
+
+
+def test_query_sequences_are_deterministic_and_legal(oracle, queried):
+    assert len(M.QSEEDS) == 16
+    seed = M.QSEEDS[5]
+    M._GENERATED.pop((seed, "queries"))
+    assert _strip(M.generate(seed, oracle, queries=True)) == _strip(queried[seed])
+    assert len({repr(_strip(f)) for f in queried.values()}) == len(queried)
+    for seed, frames in queried.items():
+        assert len(frames) == M.FRAMES
+        out = M.run_model(oracle, frames, partitioned=True)          # (raises where a step is refused on a partitioned context)
+        plain = M.run_model(oracle, frames)
+        assert all(M.same_outputs(a, b) for a, b in zip(out, plain)), "the partitioned mode only refuses: it computes nothing else"
+        windows = [tuple(steps[0]["window"]) for steps in frames]
+        assert sorted(windows) == sorted([M.FULL, M.FULL, M.SUB]), (seed, windows)
+        for fi, steps in enumerate(frames):
+            assert steps[0]["op"] == "clear" and steps[-1]["op"] in ("readback", "fenced") and len(steps) - 1 <= M.MAX_STEPS, (seed, fi)
+            latest = None                      # the latest pass: (its step, rastered how often)
+            for s in steps[1:-1]:
+                if s["op"] in ("geom", "draw"):
+                    latest = [s, int(s["op"] == "draw")]
+                    if s["kind"] in ("list", "list_if") and not s["rung"] and s["items"]:
+                        assert 3 <= len(s["items"]) <= 7
+                elif s["op"] == "raster":
+                    assert latest is not None and latest[0]["op"] == "geom" and not latest[0].get("abandoned")
+                    assert bool(s.get("again")) == (latest[1] > 0), "`again` marks the rasters behind a pass's first"
+                    latest[1] += 1
+                elif s["op"] in ("wireframe", "resolve", "count", "item_ranges", "setup_triangles", "shade_items", "query", "query_host") and latest is not None:
+                    assert latest[0]["op"] == "geom", f"seed {seed} frame {fi}: {s['op']} behind a fused pass"
+                if s["op"] in ("count", "query", "boxes", "resolve"):
+                    assert s["buf"][0] == "AB"[fi % 2], "caller buffers come from two pools that alternate by frame"
+                if s["op"] in ("boxes", "boxes_host", "bounds"):
+                    assert s["vs"] in M.VS_PS and 3 <= len(s["items"]) <= 7 and all(m in M.MESHES and m not in M.RUNGS.values() for m, _ in s["items"])
+        # every fed pass names a buffer whose provenance matches its list; a buffer of box answers is read under min_value 1 only
+        for fi, k, s, m, _, _ in _walk(oracle, frames):
+            if s["op"] in ("geom", "draw") and s["kind"] == "list_if" and s["keep"] in m.bufs:
+                pr = m.prov.get(s["keep"])
+                if s["fed"]:
+                    assert pr is not None and pr["unit"] == "item" and [tuple(i) for i in pr["items"]] == [tuple(i) for i in s["items"]], (seed, fi, k)
+                    assert pr["entries"] == s["keep_entries"] >= len(s["items"]) and pr["frame"] >= m.fno - 1 and pr["source"] == s["source"]
+                    assert pr["source"] != "boxes" or pr["vs"] == s["vs"], "a box answer feeds the list that was queried"
+                assert pr is None or pr["source"] != "boxes" or s["min"] == 1, (seed, fi, k)
+
+
+def test_every_kept_step_of_the_query_sequences_is_felt(oracle, queried):
+    for seed, frames in queried.items():
+        bad = M.insensitive_steps(oracle, frames, partitioned=True)
+        assert not bad, f"seed {seed}: removing {[(fi, M.describe(s)) for fi, s in bad]} changes no compared output"
+        flat = M.steps_of(frames)
+        assert len([s for s in flat if s.get("noop")]) <= M.NOOP_SHARE * len(flat), seed
+
+
+def _query_coverage(oracle, queried):
+    from . import box_reference as BX
+    n, status = collections.Counter(), collections.Counter()
+    for seed, frames in queried.items():
+        tiny = seed % 2 == 1                   # the seeds that run with the tiny lists on a partition too
+        cam_of = {}                            # list -> the camera of its last use
+        for fi, k, s, m, after, a in _walk(oracle, frames):
+            op = s["op"]
+            if op == "clear":
+                latest, rastered, abandoned, draws, asked = None, 0, False, 0, {}
+                sub = tuple(s["window"]) == M.SUB
+                steps = frames[fi]
+            elif op in ("geom", "draw"):
+                latest, rastered = s, int(op == "draw")
+                abandoned |= bool(s.get("abandoned"))
+                draws += op == "draw"
+                if s["kind"] in ("list", "list_if"):
+                    cam_of[_key(s)] = m.cam
+                if s["kind"] == "list_if" and s.get("fed") and s.get("source") in ("query", "boxes"):
+                    src, pr = s["source"], m.prov[s["keep"]]
+                    kept = P.kept_of(m.bufs[s["keep"]][:len(s["items"])], s["min"])
+                    n["fed by " + src] += 1
+                    n["fed by " + src + ", some dropped and some kept"] += bool(kept.any() and not kept.all())
+                    n["fed by " + src + " within one frame"] += pr["frame"] == m.fno
+                    n["fed by " + src + " across a frame boundary"] += pr["frame"] == m.fno - 1
+            elif op == "raster":
+                rastered += 1
+                draws += 1
+            elif op in ("query", "query_host"):
+                n["host form"] += op == "query_host"
+                if op == "query_host":
+                    continue
+                p = m.last
+                inside = latest is not None and latest["op"] == "geom" and not rastered and not p.cleared
+                units = len(p.items) if s["unit"] == "item" else p.base + p.emit
+                n["query"] += 1
+                n["query per triangle"] += s["unit"] == "triangle"
+                n["query with entries below n"] += s["entries"] < units
+                n["query with entries above n"] += s["entries"] > units
+                n["query inside a split pass, tiny lists"] += inside and tiny
+                n["query inside a bin rung's split pass, tiny lists"] += bool(inside and tiny and latest["bin_rung"])
+                n["query in a sub-window frame"] += sub
+                n["query behind an abandoned pass"] += abandoned
+                n["query after a clear since the pass"] += bool(p.cleared)
+                n["query of a list_if pass with a dropped item"] += bool(not p.cleared and p.kind == "list_if" and not p.kept.all())
+                n["query under a cull mode"] += bool(not p.cleared and p.cull != 0)
+            elif op in ("boxes", "boxes_host", "bounds"):
+                n["host form"] += op != "boxes"
+                if op == "bounds":
+                    continue
+                if op == "boxes":
+                    log = after.box_log[-1]
+                    nitems = len(s["items"])
+                    n["boxes"] += 1
+                    n["boxes first behind the clear"] += k == 1
+                    n["boxes behind a changed camera"] += _key(s) in cam_of and cam_of[_key(s)] != m.cam and \
+                        any(x["op"] == "set_uniforms" for f in frames[:fi + 1] for x in f)
+                    status.update(int(v) for v in log["srl"][:, 0])
+                    if _key(s) in asked and draws > asked[_key(s)][1] and (asked[_key(s)][0] != log["srl"][:, 0]).any():
+                        n["two boxes of one list around a draw that differ"] += 1
+                    asked[_key(s)] = (log["srl"][:, 0].copy(), draws)
+                cam_of[_key(s)] = m.cam
+    names = {BX.NONE: "NONE", BX.OUTSIDE: "OUTSIDE", BX.HIDDEN: "HIDDEN", BX.KEPT: "KEPT", BX.UNBOUNDED: "UNBOUNDED"}
+    return n, {names[k]: v for k, v in status.items()}
+
+
+def test_coverage_of_the_query_seed_set(oracle, queried):
+    n, status = _query_coverage(oracle, queried)
+    print(dict(n), status)
+    for what in ("query", "boxes", "host form"):
+        assert n[what] >= 6, (what, dict(n))
+    for what in ("query per triangle", "query with entries below n", "query with entries above n", "query inside a split pass, tiny lists",
+                 "query in a sub-window frame", "boxes first behind the clear", "boxes behind a changed camera",
+                 "two boxes of one list around a draw that differ", "fed by query", "fed by boxes"):
+        assert n[what] >= 3, (what, dict(n))
+    for what in ("query inside a bin rung's split pass, tiny lists", "query behind an abandoned pass", "query after a clear since the pass",
+                 "query of a list_if pass with a dropped item", "query under a cull mode"):
+        assert n[what] >= 1, (what, dict(n))
+    for what in ("HIDDEN", "KEPT", "UNBOUNDED"):
+        assert status.get(what, 0) >= 3, (what, status)
+    for what in ("OUTSIDE", "NONE"):
+        assert status.get(what, 0) >= 1, (what, status)
+    for src in ("query", "boxes"):
+        assert n["fed by " + src + ", some dropped and some kept"] >= 2, (src, dict(n))
+        assert n["fed by " + src + " within one frame"] >= 2, (src, dict(n))
+    assert n["fed by query across a frame boundary"] + n["fed by boxes across a frame boundary"] >= 1, dict(n)
+
+
+def _pin_scene(prefix, sc):
+    """a drawlist_scenes list as items of the model: its meshes under names of their own, its matrices behind MODELS"""
+    base = len(M.MODELS)
+    M.MESHES.update({f"{prefix}_{k}": m.tris for k, m in enumerate(sc.meshes)})
+    M.MODELS = np.concatenate([M.MODELS, np.asarray(sc.models, np.float32).reshape(-1, 16)])
+    return [(f"{prefix}_{w}", base + i) for i, w in enumerate(sc.which)]
+
+
+def test_pinned_to_the_query_pairs(oracle):
+    """tests/query_reference.py: the per-item answers of the pair (`clipped` as the occluders, `sizes` as the probe) and of
+    `sizes` against the cleared depth, as the device form writes them and as the host form returns them"""
+    from . import drawlist_scenes as D
+    from . import query_reference as QR
+    models, names = M.MODELS, set(M.MESHES)
+    try:
+        occ, probe = _pin_scene("qpin_occ", D.scene("clipped")), _pin_scene("qpin_probe", D.scene("sizes"))
+        n = len(probe)
+        steps = [dict(op="clear", window=M.FULL),
+                 dict(op="geom", kind="list", vs="PHONG", items=probe, rung=0), dict(op="query", unit="item", buf="A.c0", entries=n),
+                 dict(op="draw", kind="list", vs="PHONG", items=occ, ps="DEPTH", rung=0),
+                 dict(op="geom", kind="list", vs="PHONG", items=probe, rung=0), dict(op="query", unit="item", buf="A.c1", entries=n + 2),
+                 dict(op="query_host", unit="item", entries=n - 1), dict(op="query_host", unit="triangle", entries=M.COUNT_CAP), dict(op="stats"),
+                 dict(op="readback")]
+        got, = M.run_model(oracle, [steps])
+    finally:
+        M.MODELS = models
+        for k in set(M.MESHES) - names:
+            M.MESHES.pop(k)
+    pair = QR.PAIRS["clipped", "sizes"]
+    assert list(got["bufs"]["A.c0"][:n]) == QR.CLEARED["sizes"] and list(got["bufs"]["A.c1"][:n]) == pair
+    assert list(got["bufs"]["A.c1"][n:n + 2]) == [0, 0] and got["bufs"]["A.c1"][n + 2] == M.SENTINEL_BITS and got["bufs"]["A.c0"][n] == M.SENTINEL_BITS
+    (_, a), (_, t), (_, st) = got["answers"]
+    assert list(a["out"]) == pair[:n - 1]
+    d0, setup, per, per_tri, per_item = QR.pair(oracle, "clipped", "sizes")
+    first = st["tris_setup"] - len(setup)          # the second probe pass's first id: behind the first probe pass and the occluders
+    assert first > len(setup) and not t["out"][:first].any() and list(t["out"][first:first + len(setup)]) == list(per_tri) and not t["out"][first + len(setup):].any()
+    frame = D.oracle_frame(oracle, "clipped", "DEPTH")[0]
+    np.testing.assert_array_equal(got["depth"].view(np.uint32), frame.depth.view(np.uint32), err_msg="a query draws nothing")
+    assert st["draws"] == 3 and st["frag_covered"] == int(frame.counters.frag_covered), "a query counts no fragment"
+
+
+def _box_steps(oracle, frames):
+    """(frame, index, step, the recorded inputs, out, status) of every box query of a sequence, the host forms included"""
+    for fi, k, s, _, after, a in _walk(oracle, frames):
+        if s["op"] == "boxes":
+            log = after.box_log[-1]
+            yield fi, k, s, log["args"], log["out"], log["srl"]
+        elif s["op"] == "boxes_host":
+            yield fi, k, s, a["args"], a["out"], a["srl"]
+
+
+def test_box_answers_are_the_host_builds(oracle, queried):
+    """every box query of the query seeds: the model's answer (tests/box_reference.py over the model's depth) equals
+    frr_host_query_boxes, the host build of the header the kernels compile, value for value -- and so do a rank's own"""
+    import f_renderer_amd as fr
+    seen = 0
+    for seed, frames in queried.items():
+        for fi, k, s, args, out, srl in _box_steps(oracle, frames):
+            for rows in (None, M.rank_tile_rows(args["window"], 1, 2, False), M.rank_tile_rows(args["window"], 0, 3, True)):
+                want, want_srl = M.box_answer(args, rows)
+                host, host_srl = fr.host_query_boxes(args["mvps"], args["lo_hi"], args["flags"], args["size"], args["window"], args["depth"],
+                                                     row_owned=None if rows is None else rows.astype(np.uint8), entries=args["entries"])
+                np.testing.assert_array_equal(host, want, err_msg=f"seed {seed} frame {fi} step {k}")
+                np.testing.assert_array_equal(host_srl, want_srl, err_msg=f"seed {seed} frame {fi} step {k}")
+            np.testing.assert_array_equal(M.box_answer(args)[0], out)
+            seen += 1
+    assert seen >= 6
+
+
+def test_the_ranks_box_answers_are_zero_together_where_the_whole_answer_is(oracle, queried):
+    """The partition rule for box answers: a rank's answer is its own and the ranks' answers do not add up to the unpartitioned
+    one, but their sum is zero exactly where the unpartitioned answer is zero -- which is all frr_draw_list_if reads under
+    min_value 1.  For every box query of the query seeds, on every world and layout of the partitioned GPU runs."""
+    differ = checked = 0
+    for seed, frames in queried.items():
+        for fi, k, s, args, out, srl in _box_steps(oracle, frames):
+            for world in (2, 3, 4):
+                for blocked in (False, True):
+                    total = sum(M.box_answer(args, M.rank_tile_rows(args["window"], rank, world, blocked))[0].astype(np.int64) for rank in range(world))
+                    np.testing.assert_array_equal(total == 0, out == 0, err_msg=f"seed {seed} frame {fi} step {k}, world {world}, blocked {blocked}")
+                    differ += int((total != out).sum())
+                    checked += out.size
+    assert checked > 1000 and differ > 0, (checked, differ)
+
+
+def test_a_pass_decided_by_a_box_query_is_the_whole_pass(oracle, queried):
+    """include/frr.h: `out[i] == 0 implies that drawing item i now changes no entry`.  Every predicated pass of the query seeds
+    that a box query of the same list decides under min_value 1, with nothing written to a target and no uniform changed
+    between the two, against the same sequence with the unpredicated list pass in its place: colour and depth after the pass
+    are equal, and every item the query dropped owns no pixel of the whole pass (the ids differ: the survivors' are dense)."""
+    checked = dropped = 0
+    for seed, frames in queried.items():
+        for fi, k, s, m, _, _ in _walk(oracle, frames):
+            if not (s["op"] == "draw" and s["kind"] == "list_if" and s.get("fed") and s.get("source") == "boxes" and s["min"] == 1):
+                continue
+            steps = frames[fi]
+            at = max((j for j in range(k) if steps[j]["op"] == "boxes" and steps[j]["buf"] == s["keep"]), default=None)
+            if at is None or _key(steps[at]) != _key(s) or \
+                    any(x["op"] in ("draw", "raster", "lines", "wireframe", "shade", "shade_items", "set_uniforms", "set_cull", "clear") for x in steps[at + 1:k]):
+                continue
+            a, b = m.copy(), m.copy()
+            a.apply(s)
+            b.apply(dict(s, kind="list"))
+            what = f"seed {seed} frame {fi} step {k}"
+            np.testing.assert_array_equal(a.frame.color, b.frame.color, err_msg=what)
+            np.testing.assert_array_equal(a.frame.depth.view(np.uint32), b.frame.depth.view(np.uint32), err_msg=what)
+            first = M.VIS.bounds_of(b.last.per_item, b.last.base).astype(np.int64)
+            ids = b.frame.tri_id.astype(np.int64)
+            for i, kept in enumerate(a.last.kept):
+                if not kept:
+                    assert not ((ids >= first[i]) & (ids < first[i + 1]) & (b.frame.tri_id != M.NONE)).any(), f"{what}: dropped item {i} owns a pixel"
+                    dropped += 1
+            checked += 1
+    assert checked >= 3 and dropped >= 3, (checked, dropped)
+
+
+def test_the_fixed_query_sequences(oracle):
+    """frame_model.query_overflows_a_rung and boxes_around_a_draw, which tests/test_gpu_frame_model.py runs: legal on a
+    partition, every step felt, and they hold what they are there for"""
+    from . import box_reference as BX
+    frames = M.query_overflows_a_rung()
+    want, = M.run_model(oracle, frames, partitioned=True)
+    m = M.Model(oracle, partitioned=True)
+    for s in frames[0][:3]:
+        m.apply(s)
+    assert m.last.fan_rung and m.last.bin_rung and want["crossed"] and want["crossed_fan"]
+    n = len(M.LOOP_LIST)
+    c0, c2 = want["bufs"]["A.c0"][:3], want["bufs"]["A.c2"][:n + 3]
+    assert c0[0] > 0 and (c2[:n] == 0).any() and (c2[:n] > 0).any() and not c2[n:].any(), (c0, c2)
+    assert (want["bufs"]["A.c1"][:3] == 0).all(), "a count in front of the pass's raster finds none of its ids"
+    assert not M.insensitive_steps(oracle, frames, partitioned=True)
+    frames = M.boxes_around_a_draw()
+    want = M.run_model(oracle, frames, partitioned=True)
+    n = len(M.LOOP_LIST)
+    b0, b1, b2 = (want[0]["bufs"][f"A.c{k}"][:n] for k in range(3))
+    assert (b0 != b1).any() and (b1 != b2).any() and (b0 != b2).any() and (b2 == 0).any() and (b2 > 0).any()
+    st = {int(v) for log in want[0]["boxes"] + want[1]["boxes"] for v in log["srl"][:, 0]}
+    assert st >= {BX.NONE, BX.HIDDEN, BX.KEPT, BX.UNBOUNDED}, st
+    (_, bounds), (_, host) = want[0]["answers"]
+    assert bounds["flags"][3] == 2 and list(host["out"]) == list(b2[:n - 2])
+    assert (want[1]["bufs"]["B.c0"][:n] != want[1]["bufs"]["B.c1"][:n]).any(), "the split pass's raster lies between the two"
+    assert not M.insensitive_steps(oracle, frames, partitioned=True)
+
+
+def test_queries_where_they_are_undefined_and_where_they_answer_zeros(oracle):
+    lst = [("p100", int(M.M_CLIPPED[0])), ("torus", int(M.M_GRID[1])), ("spiky", int(M.M_CLIPPED[3])), ("empty", int(M.M_GRID[2]))]
+    clear, geom = dict(op="clear", window=M.SUB), dict(op="geom", kind="list", vs="PHONG", items=lst, rung=0)
+    query = dict(op="query", unit="item", buf="A.c0", entries=6)
+    m = M.Model(oracle, partitioned=True)
+    m.apply(clear)
+    with pytest.raises(M.Undefined):           # before any geometry pass
+        m.apply(query)
+    m.apply(dict(op="boxes", vs="PHONG", items=lst, buf="A.c1", entries=4))            # a box query needs no pass
+    with pytest.raises(M.Undefined):
+        m.copy().apply(dict(op="boxes", vs="CLIP_COLOR", items=lst, buf="A.c1", entries=4))
+    m.apply(geom)
+    before = (m.frame.color.copy(), m.frame.depth.copy(), m.frame.tri_id.copy(), m.stats(), m.last)
+    m.apply(query)
+    got = m.bufs["A.c0"][:7]
+    assert got[0] > 0 and got[3] == 0 and got[4] == got[5] == 0 and got[6] == M.SENTINEL_BITS, got
+    assert m.stats() == before[3] and m.last is before[4] and all((a == b).all() for a, b in zip(before[:3], (m.frame.color, m.frame.depth, m.frame.tri_id)))
+    # a pass that is not rastered yet counts like any other: the raster changes exactly the entries the triangles' queries
+    # count together, at most their sum
+    m.apply(dict(op="raster", ps="DEPTH"))
+    assert 0 < (m.frame.tri_id != M.NONE).sum() <= int(got[:4].sum())
+    again = m.copy()
+    again.apply(dict(query, buf="A.c2"))
+    assert (again.bufs["A.c2"][:4] <= got[:4]).all() and again.bufs["A.c2"][0] > 0, "rhw == depth passes: the pass's own fragments still count"
+    # per triangle: indices below the pass's first id get 0; a dropped item of a predicated pass counts 0
+    m.apply(dict(geom, kind="list_if", keep="mask0", keep_entries=8, min=1))
+    n = m.last.base + m.last.emit
+    m.apply(dict(op="query", unit="triangle", buf="A.c1", entries=n + 3))
+    m.apply(dict(query, buf="A.c2"))
+    assert not m.bufs["A.c1"][:m.last.base].any() and m.bufs["A.c1"][m.last.base:n].any() and not m.bufs["A.c1"][n:n + 3].any()
+    assert m.last.base > 0 and m.bufs["A.c2"][1] == 0 and not m.last.kept[1] and m.bufs["A.c2"][0] > 0
+    # after a clear since the pass: zeros per item, and the model leaves the per-triangle form undefined there
+    m.apply(clear)
+    m.apply(query)
+    assert not m.bufs["A.c0"][:6].any()
+    with pytest.raises(M.Undefined):
+        m.copy().apply(dict(op="query", unit="triangle", buf="A.c1", entries=9))
+    # on a partitioned context behind a fused pass: refused, where the count is refused; the box query is not
+    m.apply(dict(geom, op="draw", ps="DEPTH"))
+    for s in (query, dict(op="query_host", unit="item", entries=4), dict(op="count", unit="item", buf="A.c0", entries=4)):
+        with pytest.raises(M.Undefined):
+            m.copy().apply(s)
+    m.apply(dict(op="boxes", vs="PHONG", items=lst, buf="A.c1", entries=4))
+    assert m.box_log[-1]["srl"][3, 0] == 0 and m.prov["A.c1"]["source"] == "boxes"

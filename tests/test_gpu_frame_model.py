@@ -30,11 +30,12 @@ TARGET_SENTINEL = 0x5A5A5A5A                    # what the caller-bound targets 
 _EXPECTED = {}
 
 
-def _expected(oracle, seed, fixed=None):
-    """the seed's frames, or those of the fixed sequence frame_model.<fixed>(), with what the model says they leave"""
-    key = fixed or seed
+def _expected(oracle, seed, fixed=None, queries=False):
+    """the seed's frames (queries: those of the query generator), or those of the fixed sequence frame_model.<fixed>(), with
+    what the model says they leave"""
+    key = fixed or (("queries", seed) if queries else seed)
     if key not in _EXPECTED:
-        frames = getattr(M, fixed)() if fixed else M.generate(seed, oracle)
+        frames = getattr(M, fixed)() if fixed else M.generate(seed, oracle, queries=queries)
         _EXPECTED[key] = (frames, M.run_model(oracle, frames))
     return _EXPECTED[key]
 
@@ -114,6 +115,23 @@ class _Run:
         x0, x1, y0, y1 = self.window
         return dict(width_range=(x0, x1), height_range=(y0, y1))
 
+    def draw_list(self, vs, items):
+        key = (vs, tuple(tuple(i) for i in items))
+        if key not in self.lists:
+            self.lists[key] = self.r.upload_draw_list([self.mesh(name, vs) for name, _ in items], M.MODELS[[mi for _, mi in items]].reshape(-1, 16))
+        return self.lists[key]
+
+    def prepare(self, frames):
+        """set-up before the frames start, like the mesh uploads: every list that becomes the subject of a box query gets its
+        bounds table once (frr_drawlist_bounds is a synchronisation point)"""
+        done = set()
+        for s in M.steps_of(frames):
+            if s["op"] in ("boxes", "boxes_host", "bounds"):
+                dl = self.draw_list(s["vs"], s["items"])
+                if id(dl) not in done:
+                    self.r.list_bounds(dl)
+                    done.add(id(dl))
+
     def geometry(self, s, ps=None):
         """the geometry* call of a split pass (ps None) or the draw* call of a fused one"""
         r, fr, kind, vs, items = self.r, self.fr, s["kind"], s["vs"], s["items"]
@@ -128,10 +146,7 @@ class _Run:
                 self.insts[key] = r.upload_instances(M.MODELS[list(key)])
             mesh, inst = self.mesh(items[0][0], vs), self.insts[key]
             return r.draw_instanced(mesh, inst, ps, **win) if ps is not None else r.geometry_processing_instanced(mesh, inst)
-        key = (vs, tuple(items))
-        if key not in self.lists:
-            self.lists[key] = r.upload_draw_list([self.mesh(name, vs) for name, _ in items], M.MODELS[[mi for _, mi in items]].reshape(-1, 16))
-        dl = self.lists[key]
+        dl = self.draw_list(vs, items)
         if kind == "list":
             return r.draw_list(dl, ps, **win) if ps is not None else r.geometry_list(dl)
         keep = (self.bufs[s["keep"]] if s["keep"] in self.bufs else self.masks[s["keep"]]).data_ptr()
@@ -173,6 +188,17 @@ class _Run:
                           K=M.buffer_k(s["buf"]), **self.ranges())
         elif op == "count":
             r.visible_pixels(s["unit"], out_ptr=self.bufs[s["buf"]].data_ptr(), entries=s["entries"], **self.ranges())
+        elif op == "query":
+            r.query_pixels(s["unit"], self.window, out_ptr=self.bufs[s["buf"]].data_ptr(), entries=s["entries"])
+        elif op == "query_host":
+            return dict(out=r.query_pixels(s["unit"], self.window, entries=s["entries"]))
+        elif op == "boxes":
+            r.query_boxes(self.draw_list(s["vs"], s["items"]), out_ptr=self.bufs[s["buf"]].data_ptr(), entries=s["entries"], window=self.window)
+        elif op == "boxes_host":
+            return dict(out=r.query_boxes(self.draw_list(s["vs"], s["items"]), entries=s["entries"], window=self.window))
+        elif op == "bounds":
+            lo_hi, flags = r.list_bounds(self.draw_list(s["vs"], s["items"]))
+            return dict(lo_hi=lo_hi, flags=flags)
         elif op == "item_ranges":
             first, count = r.item_ranges()
             return dict(first=first, count=count)
@@ -225,6 +251,11 @@ def _same_answer(op, got, want, what):
         np.testing.assert_array_equal(got["spi"], want["spi"], err_msg=f"{what}: setup spi")
         V.assert_bits_equal(got["spf"], want["spf"], err_msg=f"{what}: setup spf")
         V.assert_bits_equal(got["rhw"], want["rhw"], err_msg=f"{what}: setup rhw")
+    elif op in ("query_host", "boxes_host"):
+        np.testing.assert_array_equal(got["out"], want["out"], err_msg=f"{what}: {op}")
+    elif op == "bounds":
+        np.testing.assert_array_equal(got["lo_hi"].view(np.uint32), want["lo_hi"].view(np.uint32), err_msg=f"{what}: bounds lo, hi (bits)")
+        np.testing.assert_array_equal(got["flags"], want["flags"], err_msg=f"{what}: bounds flags")
 
 
 def _same_frame(got, want, what):
@@ -241,19 +272,22 @@ def _same_frame(got, want, what):
             np.testing.assert_array_equal(b, want["bufs"][name], err_msg=f"{what}: count buffer {name}")
 
 
-def _run(oracle, seed, tiny, fixed=None):
+def _run(oracle, seed, tiny, fixed=None, queries=False):
     """one run of the seed's sequence (or of a fixed one under the seed's mode and options); returns (what every frame left, as
     host arrays; the replay counter at the frame ends that synchronise: {frame: count})"""
-    frames, want = _expected(oracle, seed, fixed)
+    frames, want = _expected(oracle, seed, fixed, queries)
     x = _Run(seed, tiny)
     log = [f"{fixed or 'seed'} {seed} mode={x.mode} lists={'tiny' if tiny else 'default'}"]
     got, replays, pending, fenced_stats = [None] * len(frames), {}, [], {}
+    open_geom = False                           # the latest geometry pass is open or abandoned (see _Ranks.step)
     try:
+        x.prepare(frames)
         for fi, steps in enumerate(frames):
             answers = iter(want[fi]["answers"])
             for s in steps[:-1]:
                 log.append(f"  frame {fi}: " + M.describe(s))
                 a = x.step(s)
+                open_geom = _open_after(s, open_geom)
                 if s["op"] in M.QUERIES:
                     op, w = next(answers)
                     assert op == s["op"]
@@ -264,6 +298,8 @@ def _run(oracle, seed, tiny, fixed=None):
                 replays[fi] = got[fi]["stats"]["replays"]
                 _same_frame(got[fi], want[fi], f"frame {fi} (read back)")
             else:
+                if open_geom:                   # (include/frr.h, frr_frame_fence: "A caller that fences such a frame calls frr_sync first.")
+                    x.r.sync()
                 pending.append((fi, x.end_fenced()))
                 if tiny:
                     # the counters restart at the next frr_clear: a half-frame that was cancelled and replayed must not
@@ -298,15 +334,58 @@ def test_frame_model(oracle, seed):
     _both_runs(oracle, seed)
 
 
-def _both_runs(oracle, seed, fixed=None):
-    tiny, replays = _run(oracle, seed, True, fixed)
-    default, _ = _run(oracle, seed, False, fixed)
+def _open_after(s, open_geom):
+    """is the latest geometry pass open or abandoned behind step s?  include/frr.h, frr_frame_fence: "What is not whole at a
+    fence: commands issued behind a frr_geometry* that no frr_raster has followed yet (an open or abandoned pass)" -- so a
+    geometry* opens, and a raster, a fused draw* and the next frame's clear close; frr_query_pixels: "It closes an open pass in
+    the sense of the frr_frame_fence comment" (it bins, and is verified inside the call); its host form and every other host
+    query are synchronisation points, at which the commands behind the open pass were replayed, but the pass stays open for
+    the commands that follow"""
+    if s["op"] == "geom":
+        return True
+    if s["op"] in ("raster", "draw", "clear", "query"):
+        return False
+    return open_geom
+
+
+def _both_runs(oracle, seed, fixed=None, queries=False):
+    tiny, replays = _run(oracle, seed, True, fixed, queries)
+    default, _ = _run(oracle, seed, False, fixed, queries)
     print(f"{fixed or 'seed'} {seed}: replays with the tiny lists, per frame: {[replays[k] for k in sorted(replays)]}")
     for fi, (a, b) in enumerate(zip(tiny, default)):
         for k in ("color", "depth", "tri_id"):
             assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), f"seed {seed} frame {fi}: {k} differs between the two runs"
         for name in a["bufs"]:
             assert a["bufs"][name].tobytes() == b["bufs"][name].tobytes(), f"seed {seed} frame {fi}: buffer {name} differs between the two runs"
+
+
+@pytest.mark.parametrize("seed", [pytest.param(s, marks=pytest.mark.xfail(strict=True, reason=XFAIL[s])) if s in XFAIL else s for s in M.QSEEDS])
+def test_frame_model_queries(oracle, seed):
+    """The query sequences (generate(seed, queries=True)): frr_query_pixels and frr_query_boxes among every other command --
+    between a geometry* and its raster, behind abandoned passes, as the command that first overflows the tiny lists, first
+    behind the clear, behind camera changes, in both windows with frames in flight -- their host forms, frr_drawlist_bounds,
+    and the frr_draw_list_if passes their buffers decide, within a frame and across a frame boundary, with no host wait.  Held
+    to the model like the first seed set: targets, statistics (a query adds nothing but `replays`), every buffer, every
+    answer; the tiny-list and the default-list run byte for byte; no replay with the default lists, at least one in a frame
+    where the model says a rung is crossed."""
+    _both_runs(oracle, seed, queries=True)
+
+
+@pytest.mark.parametrize("seed", (0, 1, 2, 3, 7, 11))
+def test_a_query_inside_a_rungs_split_pass_is_what_overflows(oracle, seed):
+    """frame_model.query_overflows_a_rung in the three target modes, with option overlap 2 and 0 and clear_eager off and on: the
+    per-item query between a rung's geometry and its raster is the first command that bins the pass; the line list in front
+    of it is replayed with it, the count behind it needs no synchronisation point any more; a second query, of an abandoned
+    pass, decides a frr_draw_list_if, and the frame is fenced with no host wait"""
+    _both_runs(oracle, seed, "query_overflows_a_rung")
+
+
+@pytest.mark.parametrize("seed", (0, 1, 2, 6, 7, 8))
+def test_box_queries_behind_a_clear_a_camera_and_a_draw(oracle, seed):
+    """frame_model.boxes_around_a_draw in the three target modes with clear_eager off and on: frr_query_boxes as the first command
+    behind frr_clear, under two cameras, in front of and behind the occluder, inside a split pass in the sub-window while the
+    previous frame is in flight, and the passes its buffers decide in the same and in the next frame"""
+    _both_runs(oracle, seed, "boxes_around_a_draw")
 
 
 @pytest.mark.parametrize("seed", range(3))
@@ -367,8 +446,8 @@ def _rows_mask(bands, n):
 class _Ranks:
     """The ranks of one partition as contexts in one process on one device, driven in lockstep: every step goes to every rank
     before the next one.  Each rank has its own targets and its own caller buffers; the one exchange between them is the
-    all-reduce of a count buffer behind every frr_visible_pixels, which is what a multi-GPU caller does before it feeds the
-    counts to frr_draw_list_if."""
+    all-reduce of a count buffer behind every frr_visible_pixels, frr_query_pixels and frr_query_boxes, which is what a
+    multi-GPU caller does before it feeds the buffer to frr_draw_list_if."""
 
     def __init__(self, seed, world, blocked, tiny):
         import torch
@@ -394,18 +473,19 @@ class _Ranks:
 
     def step(self, s):
         """one step on every rank; returns the ranks' answers"""
-        if s["op"] == "count":
-            self.settle()                       # (frr_visible_pixels waits for no frr_frame_wait: it writes no target)
+        if s["op"] in ("count", "query", "boxes"):
+            self.settle()                       # (frr_visible_pixels waits for no frr_frame_wait: it writes no target; nor do the queries)
         out = [x.step(s) for x in self.x]
-        if s["op"] in ("geom", "draw"):
-            self.open_geom = s["op"] == "geom"
-        elif s["op"] in ("raster", "clear"):
-            self.open_geom = False
-        if s["op"] == "count":
+        self.open_geom = _open_after(s, self.open_geom)
+        if s["op"] in ("count", "query"):
             self.all_reduce(s["buf"], s["entries"])
+        elif s["op"] == "boxes":
+            # each rank's own answer is kept for the comparison with the rule under its rows; then the same sum: it is zero
+            # exactly where the unpartitioned answer is, which is all a frr_draw_list_if under min_value 1 reads
+            return self.all_reduce(s["buf"], s["entries"], keep=True)
         return out
 
-    def all_reduce(self, name, entries):
+    def all_reduce(self, name, entries, keep=False):
         """the ranks' counts summed on the device and written back into every rank's buffer: behind each rank's command
         (frr_frame_fence), in front of its next one (frr_frame_wait).  A count behind a geometry pass that is not rastered yet
         is guaranteed only once a synchronisation point has passed (a work list may have been too small: the count wrote
@@ -416,12 +496,14 @@ class _Ranks:
                 x.r.sync()
             x.r.frame_fence(self.st.cuda_stream)
         with torch.cuda.stream(self.st):
+            own = [x.bufs[name][:entries].clone() for x in self.x] if keep else None
             total = torch.stack([x.bufs[name][:entries] for x in self.x]).sum(dim=0, dtype=torch.int32)
             for x in self.x:
                 x.bufs[name][:entries].copy_(total)
         for x in self.x:
             x.r.frame_wait(self.st.cuda_stream)
         self.reduced = True
+        return own
 
     def settle(self):
         """the host waits for an all-reduce that may still be running (before the buffers are copied at a frame's end)"""
@@ -501,12 +583,14 @@ class _Buffers:
         self.stitched = M.new_buffers()
         self.touched = [{k: np.zeros(v.shape[0], bool) for k, v in self.stitched.items() if M.buffer_k(k)} for _ in range(world)]
 
-    def frame(self, got, want, window, local, what):
+    def frame(self, got, want, window, local, what, counts=None):
+        """counts: the count buffers as the ranks hold them where they differ from the model's (box answers, summed)"""
         x0, x1, y0, y1 = window
         row = np.arange(M.ENTRIES) // x1
         inside = row < y1 - y0
         for name, b in want["bufs"].items():
             if not M.buffer_k(name):
+                b = counts[name] if counts and name in counts else b
                 for rank, g in enumerate(got):
                     np.testing.assert_array_equal(g["bufs"][name], b, err_msg=f"{what}: count buffer {name} of rank {rank}")
                 continue
@@ -526,9 +610,11 @@ _EXPECTED_X = {}
 
 
 def _expected_x(oracle, key):
-    """the frames of an extended seed, or of a fixed sequence of frame_model, with what the partitioned model says they leave"""
+    """the frames of an extended seed, of a query seed (key: ("queries", seed)) or of a fixed sequence of frame_model, with what
+    the partitioned model says they leave"""
     if key not in _EXPECTED_X:
-        frames = getattr(M, key)() if isinstance(key, str) else M.generate(key, oracle, extended=True)
+        frames = getattr(M, key)() if isinstance(key, str) else M.generate(key[1], oracle, queries=True) if isinstance(key, tuple) else \
+            M.generate(key, oracle, extended=True)
         _EXPECTED_X[key] = (frames, M.run_model(oracle, frames, partitioned=True))
     return _EXPECTED_X[key]
 
@@ -540,14 +626,23 @@ def _run_partitioned(oracle, seed, world, blocked, tiny, key):
     bound = p.x[0].mode == "bound"
     log = [f"{key} world={world} blocked={blocked} mode={p.x[0].mode} lists={'tiny' if tiny else 'default'}"]
     bufs, replays, pending = _Buffers(world), {}, []
+    # the ranks' count buffers where they are not the model's: behind a box query a buffer holds the SUM of the ranks' own
+    # answers (include/frr.h: "The ranks' values do NOT add up to the unpartitioned ones"), until a count or a query replaces it
+    box_sum = {name: np.zeros(M.COUNT_CAP, np.uint32) for name in M.buffer_names() if not M.buffer_k(name)}
+    box_on = {name: np.zeros(M.COUNT_CAP, bool) for name in box_sum}
+    own_answers = []                            # (what, the ranks' own device answers, the rule's under each rank's rows)
     try:
+        for x in p.x:
+            x.prepare(frames)
         ever = [np.zeros(M.W * M.H, bool) for _ in range(world)]
         for window in {tuple(steps[0]["window"]) for steps in frames}:
             for rank, rows in enumerate(p.owners(window)[1]):
                 ever[rank] |= _entries_of(rows, window)
         for fi, steps in enumerate(frames):
             answers = iter(want[fi]["answers"])
+            boxes = iter(want[fi]["boxes"])
             window = tuple(steps[0]["window"])
+            rows = [M.rank_tile_rows(window, rank, world, bool(blocked)) for rank in range(world)]
             for s in steps[:-1]:
                 log.append(f"  frame {fi}: " + M.describe(s))
                 if s.get("refused"):
@@ -557,21 +652,38 @@ def _run_partitioned(oracle, seed, world, blocked, tiny, key):
                         assert err.value.code == fr.FRR_ERR_INVALID, f"rank {rank}: {err.value}"
                     continue
                 got = p.step(s)
+                if s["op"] in ("count", "query"):
+                    box_on[s["buf"]][:s["entries"]] = False
+                elif s["op"] == "boxes":
+                    b = next(boxes)
+                    assert b["buf"] == s["buf"] and b["out"].size == s["entries"]
+                    mine = [M.box_answer(b["args"], rows[rank])[0] for rank in range(world)]
+                    own_answers.append((f"frame {fi}, {M.describe(s)}", got, mine))
+                    box_sum[s["buf"]][:s["entries"]] = np.sum(mine, axis=0, dtype=np.uint64).astype(np.uint32)
+                    box_on[s["buf"]][:s["entries"]] = True
                 if s["op"] in M.QUERIES:
                     op, w = next(answers)
                     assert op == s["op"]
                     if op == "stats":
                         _sum_stats(got, w, f"frame {fi}, stats")
+                    elif op == "query_host":    # (the ranks' counts add up to the unpartitioned ones)
+                        np.testing.assert_array_equal(np.sum([a["out"] for a in got], axis=0, dtype=np.uint64), w["out"], err_msg=f"frame {fi}, query_host: the ranks' sum")
+                    elif op == "boxes_host":    # (a rank's answer is its own: the rule under the rows it owns)
+                        for rank, a in enumerate(got):
+                            np.testing.assert_array_equal(a["out"], M.box_answer(w["args"], rows[rank])[0], err_msg=f"frame {fi}, boxes_host, rank {rank}")
                     else:
                         for rank, a in enumerate(got):
                             _same_answer(op, a, w, f"frame {fi}, {op}, rank {rank}")
             log.append(f"  frame {fi}: " + steps[-1]["op"])
             plane, local = p.owners(window)
+            for rank in range(world):
+                np.testing.assert_array_equal(np.repeat(rows[rank], 32)[:window[3] - window[2]], local[rank], err_msg="the tile rows the rule is asked under")
             p.settle()
+            counts = {name: np.where(box_on[name], box_sum[name], want[fi]["bufs"][name]) for name in box_sum if box_on[name].any()}
             if steps[-1]["op"] == "readback":
                 got = [x.end_readback() for x in p.x]
                 replays[fi] = [g["stats"]["replays"] for g in got]
-                pending.append((fi, window, plane, local, got, None))
+                pending.append((fi, window, plane, local, got, None, counts))
             else:
                 # (include/frr.h: what is issued behind a frr_geometry* that no frr_raster has followed is guaranteed only once a
                 # synchronisation point has passed -- frr_frame_fence is none, and seed 109 met it: with the tiny lists an
@@ -579,20 +691,23 @@ def _run_partitioned(oracle, seed, world, blocked, tiny, key):
                 if p.open_geom:
                     for x in p.x:
                         x.r.sync()
-                pending.append((fi, window, plane, local, None, [x.end_fenced() for x in p.x]))
+                pending.append((fi, window, plane, local, None, [x.end_fenced() for x in p.x], counts))
                 if tiny:
                     pending[-1] += ([x.r.stats() for x in p.x],)
-                    replays[fi] = [st["replays"] for st in pending[-1][6]]
+                    replays[fi] = [st["replays"] for st in pending[-1][7]]
         p.torch.cuda.synchronize()
         last = [x.r.stats() for x in p.x]
         replays[len(frames) - 1] = [st["replays"] for st in last]
         # (the frames are compared in their order: a varyings buffer carries what earlier frames wrote)
-        for fi, window, plane, local, got, fenced, *stats in pending:
+        for what, got, mine in own_answers:
+            for rank, (g, w) in enumerate(zip(got, mine)):
+                np.testing.assert_array_equal(g.cpu().numpy().view(np.uint32), w, err_msg=f"{what}: rank {rank}'s own answer")
+        for fi, window, plane, local, got, fenced, counts, *stats in pending:
             if got is None:
                 got = [_Run.fenced_as_host(f) for f in fenced]
                 for rank, g in enumerate(got):
                     g["stats"] = stats[0][rank] if stats else last[rank] if fi == len(frames) - 1 else None
-            _check_partitioned_frame(got, want[fi], window, plane, local, bound, bufs, f"frame {fi} ({'fenced copy' if fenced else 'read back'})", ever)
+            _check_partitioned_frame(got, want[fi], window, plane, local, bound, bufs, f"frame {fi} ({'fenced copy' if fenced else 'read back'})", ever, counts)
         for x in p.x:
             for name, mask in x.masks.items():
                 np.testing.assert_array_equal(mask.cpu().numpy().view(np.uint32), M.MASKS[name], err_msg=f"the uploaded keep mask {name} changed")
@@ -612,11 +727,11 @@ def _run_partitioned(oracle, seed, world, blocked, tiny, key):
     return replays
 
 
-def _check_partitioned_frame(got, want, window, plane, local, bound, bufs, what, ever=None):
+def _check_partitioned_frame(got, want, window, plane, local, bound, bufs, what, ever=None, counts=None):
     _stitch_frame(got, want, window, plane, local, bound, what, ever)
     if got[0]["stats"] is not None:
         _sum_stats([g["stats"] for g in got], want["stats"], what)
-    bufs.frame(got, want, window, local, what)
+    bufs.frame(got, want, window, local, what, counts)
 
 
 def _partition_of(seed):
@@ -646,6 +761,29 @@ def test_frame_model_partitioned(oracle, seed):
     world, blocked, tiny = _partition_of(seed)
     replays = _run_partitioned(oracle, seed, world, blocked, tiny, seed)
     print(f"seed {seed}: world {world}, replays per frame and rank: {replays}")
+
+
+@pytest.mark.parametrize("seed", [pytest.param(s, marks=pytest.mark.xfail(strict=True, reason=XFAIL[s])) if s in XFAIL else s for s in M.QSEEDS])
+def test_frame_model_queries_partitioned(oracle, seed):
+    """The query sequences on the ranks of a partition, held to the unpartitioned model like the extended ones.  Behind a
+    frr_query_pixels the count buffer is all-reduced as behind a frr_visible_pixels: the ranks' counts add up to the model's.
+    Behind a frr_query_boxes every rank's own answer is first held to the rule under the tile rows that rank owns
+    (frame_model.box_answer with row_owned), then the buffer is all-reduced by the same sum: the ranks' answers do not add up to
+    the unpartitioned one, but the sum is zero exactly where it is (tests/test_frame_model_cpu.py holds that for these very
+    queries), so a frr_draw_list_if under min_value 1 -- the only one the generator feeds with box answers -- keeps the model's
+    items on every rank and the stitched frame is the model's.  At a frame's end such a buffer is compared with the sum of the
+    rule's per-rank answers."""
+    world, blocked, tiny = _partition_of(seed)
+    replays = _run_partitioned(oracle, seed, world, blocked, tiny, ("queries", seed))
+    print(f"seed {seed}: world {world}, replays per frame and rank: {replays}")
+
+
+@pytest.mark.parametrize("fixed", ["query_overflows_a_rung", "boxes_around_a_draw"])
+@pytest.mark.parametrize("seed", range(3))
+def test_the_fixed_query_sequences_on_every_rank(oracle, seed, fixed):
+    """the two fixed query sequences in worlds of 2, 3 and 4 ranks (tiny lists in the world of 3)"""
+    world, blocked, tiny = _partition_of(seed)
+    _run_partitioned(oracle, seed, world, blocked, tiny, fixed)
 
 
 @pytest.mark.parametrize("seed", range(3))
